@@ -2,6 +2,7 @@
 """bench.py -- images/sec of the fused int8 conv3x3+relu+conv1x1(+relu) block.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload res2a] [--dst s32]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (one dfx_conv_submit) over one batch of
 synthetic input already resident in HBM.  Default workload = BASELINE.json
@@ -11,14 +12,25 @@ block, N=128 per GPU, 56x56, 64->64->256, u8 x s8, s32 output.  With N>1 GPUs
 own 128 images -- images are independent, so the conv path has no collective --
 and the value is the whole-job aggregate ("scaling": "weak").  The RCCL
 all-gather + op_concat exchange of configs[3] is measured after the timed region
-and reported beside it (key "concat_allgather"), never inside `value`.
+(with --full) and reported beside it (key "concat_allgather"), never inside `value`.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps,
+writes the last step's output if asked (--dump-outputs) and prints the line:
   roofline     dominant kernel vs its binding roof (HBM for s32/f32 output),
                achieved = algorithmic bytes per launch / mean launch duration
                measured with HIP events on the launching stream
+Everything else runs after the timed region only with --full:
   cpu_baseline the CPU oracle's AVX-512-VNNI/OpenMP port (or its scalar OpenMP
-               form) timed on this host's cores on a bounded sample
+               form) timed on this host's cores on a bounded sample; the oracle
+               output of that sample also checks what the timed path wrote
+  u8_out       the default workload's block with 1-byte output (and a second
+               conv1 scale), timed and checked the same way
+  concat_allgather  (N > 1) the configs[3] exchange
+
+--dump-outputs DIR writes what the last timed step computed as DIR/dst.npy
+(float64 for s32 output, float32 otherwise; outputs over DUMP_BYTES as a fixed
+seeded sample of flat indices).  Inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 import argparse
 import importlib
@@ -36,10 +48,35 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 INT8_PEAK_TOPS = 5033.0    # dense: 2048 op/clk/SIMD (v_mfma_i32_32x32x32_i8 in 32 clk) x 1024 SIMDs x 2.4 GHz
+DUMP_BYTES = 48 << 20      # --dump-outputs: largest file written whole (the option promises at most 64 MB in all)
+DUMP_SEED = 20240607       # --dump-outputs: fixed seed of the sample of a larger output
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_output(dirname, name, t):
+    """Write tensor `t` (what the timed path handed its caller) as dirname/<name>.npy: float64 for
+    32-bit integers (exact), float32 for the 1-byte types and f32.  An output larger than DUMP_BYTES
+    is written as its values at a sorted sample of flat indices drawn with DUMP_SEED: the sample depends
+    on the output's size only, so runs with the same arguments write the same elements.  Returns what
+    was written, for the result line."""
+    import torch
+    f64 = t.dtype == torch.int32
+    es = 8 if f64 else 4
+    n = t.numel()
+    desc = {"file": name + ".npy", "dtype": "float64" if f64 else "float32", "shape": list(t.shape)}
+    if n * es <= DUMP_BYTES:
+        vals = t.cpu().numpy()
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_BYTES // es))
+        vals = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        desc["sample"] = "%d of %d elements at sorted flat indices np.unique(default_rng(%d).integers(0, %d, %d))" % (
+            idx.size, n, DUMP_SEED, n, DUMP_BYTES // es)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), vals.astype(np.float64 if f64 else np.float32))
+    return desc
 
 
 def workloads():
@@ -216,8 +253,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="res2a")
     ap.add_argument("--dst", default=None, help="override dst dtype: u8|s8|s32|f32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-u8-out", action="store_true", help="skip the u8-output leg of the default workload")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the CPU baseline and oracle check, the u8-output leg of "
+                         "the default workload and (N > 1) the all-gather + concat exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32/float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-u8-out", action="store_true", help="with --full: skip the u8-output leg of the default workload")
     ap.add_argument("--fuse-pool", action="store_true",
                     help="unfused conv workloads: 2x2/2 max pooling fused into the conv kernel (conv+relu+pool roadmap op)")
     ap.add_argument("--device-ramp-ms", type=float, default=150.0,
@@ -231,6 +273,8 @@ def main():
                     help="testing aid: stop right after the process group is up (exercises the --gpus N "
                          "launcher and rendezvous without touching a GPU; with DFX_BENCH_BACKEND=gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- N > 1 typed as `python bench.py --gpus N`: start the ranks ourselves.  Decided BEFORE
     #      torch is imported or any HIP call is made: the parent never touches the GPU, the ranks
@@ -338,6 +382,8 @@ def main():
         elapsed, kern_ms = float(tt[0]), float(tt[1])
 
     extra = {}
+    if args.dump_outputs and rank == 0:  # before anything else reuses the buffers
+        extra["dump_outputs"] = [dump_output(args.dump_outputs, "dst", dsts[(args.steps - 1) % nbuf])]
     if args.launch_stats:  # outside the timed region: per-launch durations (their spread, not the mean)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.launch_stats)]
         for i, (a0, a1) in enumerate(evs):
@@ -351,7 +397,7 @@ def main():
     # the same block with 1-byte output: the variant north_star's ">= 40 % of int8-MFMA peak" is about (the s32
     # headline is bound by its 411 MB output stream, cap 15.7 % of the MFMA peak).  Measured after the timed
     # region, same protocol (rotating buffers, HIP events on the launching stream), checked against the oracle.
-    if args.workload == "res2a" and case.dst_dt == C.S32 and not args.no_u8_out:
+    if args.full and args.workload == "res2a" and case.dst_dt == C.S32 and not args.no_u8_out:
         try:
             extra["u8_out"] = bench_u8_out(torch, hipref, C, case, data, args, world, dist, rank)
         except Exception as ex:  # never lose the main line
@@ -363,7 +409,7 @@ def main():
     else:
         extra["ranks_seen"] = 1
     # configs[3]: op_concat + RCCL all-gather, measured outside the timed region
-    if world > 1 and dist.get_backend() == "nccl":
+    if args.full and world > 1 and dist.get_backend() == "nccl":
         try:
             extra["concat_allgather"] = bench_concat_allgather(dfa, torch, dist, dsts[0], world, rank)
         except Exception as ex:  # never lose the main line
@@ -386,6 +432,7 @@ def main():
                        "per_gpu_batch": case.bs, "global_batch": case.bs * world,
                        "parallelism": "batch-sharded x%d, no data-path collective" % world,
                        "device_ramp_ms": args.device_ramp_ms, "fuse_pool": bool(args.fuse_pool),
+                       "full": bool(args.full),
                        "kernel": info.kernel_name.decode(), "grid": info.grid,
                        "split": False,  # one launch (the two-launch execution of small fused ops was removed in round 3)
                        "lds_bytes": info.lds_bytes, "rows_per_unit": info.rows_per_unit},
@@ -407,7 +454,7 @@ def main():
                          "int8_TOPs": round(tops, 2), "mfma_frac_of_int8_peak": round(tops / INT8_PEAK_TOPS, 4)},
         }
         out.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             gpu_head = dsts[0][:128].cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(case, data, args.cpu_threads or min(os.cpu_count() or 1, 16), gpu_head,
                                                fuse_pool=args.fuse_pool)
@@ -587,9 +634,12 @@ def bench_concat(args, torch, dist, dfa, C, world, rank):
                           device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, kern_ms = float(tt[0]), float(tt[1])
-    # checker + CPU baseline (oracle = restatement of op_concat.cc:22-72, pinned by test_concat.cc:31-87)
+    # with --full: checker + CPU baseline (oracle = restatement of op_concat.cc:22-72, pinned by test_concat.cc:31-87)
     cpu = None
-    if rank == 0:
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = [dump_output(args.dump_outputs, "dst", sets[(args.steps - 1) % nbuf][1])]
+    if rank == 0 and args.full:
         from oracle import oracle as orc
         srcs, dst = sets[(args.steps - 1) % nbuf]
         h_srcs = [s_.cpu().numpy() for s_ in srcs]
@@ -605,6 +655,7 @@ def bench_concat(args, torch, dist, dfa, C, world, rank):
             el = time.perf_counter() - t1
             cpu = {"value": round(bs * reps / el, 2), "unit": "images/sec", "cores": 1, "kind": "port",
                    "sample": "%d reps of the same {4,384,244,244} concat+relu, scalar C oracle" % reps}
+    if rank == 0:
         achieved = 2 * dst_bytes / (kern_ms * 1e-3) / 1e9
         out = {"metric": "concat+relu images/sec", "value": round(bs * world * args.steps / elapsed, 1),
                "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -613,13 +664,15 @@ def bench_concat(args, torch, dist, dfa, C, world, rank):
                "config": {"workload": "concat+relu {4,128,244,244}+{4,256,244,244} NHWC %s "
                                       "(reference benchmark/bench_concat.cc:226-242)" % np.dtype(np_dt).name,
                           "buffer_sets_rotated": nbuf, "working_set_bytes": 2 * dst_bytes * nbuf,
-                          "device_ramp_ms": args.device_ramp_ms},
+                          "device_ramp_ms": args.device_ramp_ms, "full": bool(args.full)},
                "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                             "frac": round(achieved / HBM_PEAK_GBS, 4),
                             "traffic": load_traffic("concat", np.dtype(np_dt).name),
                             "traffic_source": TRAFFIC_SOURCE if load_traffic("concat", np.dtype(np_dt).name) else None,
                             "kernel_ms": round(kern_ms, 5), "algorithmic_bytes_per_launch": 2 * dst_bytes},
                "cpu_baseline": cpu}
+        if dumped:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,4 +1,5 @@
 """ctypes binding of include/dfx.h (the drop-in C ABI).  Plumbing, not product."""
+import collections
 import ctypes
 import os
 import re
@@ -52,6 +53,11 @@ class PoolDesc(ctypes.Structure):
 class EltwiseDesc(ctypes.Structure):
     _fields_ = [("n_inputs", ctypes.c_int32), ("elems", ctypes.c_int64), ("dt", ctypes.c_int32),
                 ("post_relu", ctypes.c_int32)]
+
+
+# order of dfx_debug_conv_sched (include/dfx.h)
+ConvSched = collections.namedtuple("ConvSched", "th tw linear uy ux total_units half_from static_rounds lazy_queue "
+                                                "pool teams roles ring_waits")
 
 
 def lib_path():
@@ -136,6 +142,7 @@ def lib():
         "dfx_eltwise_destroy": (i32, [vp]),
         "dfx_debug_scribble_lds": (i32, [ctypes.c_uint, vp]),
         "dfx_debug_set_tuning": (i32, [ctypes.c_char_p, ctypes.c_char_p]),
+        "dfx_debug_conv_sched": (i32, [vp, ctypes.POINTER(ctypes.c_int32), i32]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -237,6 +244,12 @@ class Conv:
         i = ConvInfo()
         _check(lib().dfx_conv_query(self._h, ctypes.byref(i)))
         return i
+
+    def sched(self):
+        """unit hand-out of a resident-weight op (dfx_debug_conv_sched): a ConvSched; launches nothing."""
+        v = (ctypes.c_int32 * len(ConvSched._fields))()
+        _check(lib().dfx_debug_conv_sched(self._h, v, len(v)))
+        return ConvSched(*v)
 
     def close(self):
         if self._h:

@@ -122,6 +122,25 @@ const char *tune(const char *key) {
   held = it->second;
   return held.c_str();
 }
+// Streams made by dfx_stream_create that are still alive, each with a serial number that is never reused.  A conv
+// handle remembers the serial of the first stream it was submitted on, so that it never hands the runtime a
+// stream that dfx_stream_destroy has destroyed since (hipEventRecord on such a handle crashes: the runtime
+// looks into the stream object before it validates it).  Streams made elsewhere have serial 0: not tracked.
+struct StreamRegistry {
+  std::mutex mu;
+  std::map<hipStream_t, unsigned long long> live;
+  unsigned long long next = 1;
+};
+StreamRegistry &streams() {
+  static StreamRegistry r;
+  return r;
+}
+unsigned long long stream_serial(hipStream_t st) {
+  StreamRegistry &r = streams();
+  std::lock_guard<std::mutex> lk(r.mu);
+  auto it = r.live.find(st);
+  return it == r.live.end() ? 0ull : it->second;
+}
 }  // namespace
 
 // launches of one MFMA-variant handle that may be in flight at the same time (any streams)
@@ -163,13 +182,19 @@ struct dfx_conv {
   // In-flight guard of the queue ring.  Launches on ONE stream are ordered by the stream; as soon as a handle
   // has been submitted on a second stream every launch records its slot's event, and a launch that finds its
   // slot last used on another stream first waits (on the device) for that launch: a 17th concurrent launch
-  // queues up behind the 1st instead of sharing its queue words.
+  // queues up behind the 1st instead of sharing its queue words.  The launches made while there was one stream
+  // only carry no events of their own: when the second stream appears, ONE event recorded on first_stream
+  // (first_ev, owned by the handle, shared by their slots) stands for all of them, so that a third, fourth ...
+  // stream that reuses one of those slots waits as well.
   std::mutex *ring_mu;
   hipEvent_t slot_ev[DFX_QUEUE_RING];
   hipStream_t slot_stream[DFX_QUEUE_RING];
   unsigned char slot_state[DFX_QUEUE_RING];  // 0 never used, 1 used (no event recorded), 2 used + event recorded
   bool multi_stream;
   hipStream_t first_stream;
+  unsigned long long first_serial;  // stream_serial(first_stream) at the first launch (0: not one of dfx_stream_create's)
+  hipEvent_t first_ev;  // see above; slot_ev[i] == first_ev marks a slot that borrows it (never destroyed per slot)
+  int ring_waits;       // hipStreamWaitEvent calls the guard has issued so far (dfx_debug_conv_sched)
   int *trace_host;  // DFX_TRACE builds only
   unsigned long long *d_prof;  // DFX_STAMPS builds only
   bool weights_set;
@@ -246,11 +271,22 @@ int dfx_memset_device(void *dst, int value, size_t bytes, dfx_stream_t s) {
 int dfx_stream_create(dfx_stream_t *s) {
   hipStream_t st;
   HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  {
+    StreamRegistry &r = streams();
+    std::lock_guard<std::mutex> lk(r.mu);
+    r.live[st] = r.next++;
+  }
   *s = st;
   return DFX_OK;
 }
 int dfx_stream_destroy(dfx_stream_t s) {
-  if (s) HIP_TRY(hipStreamDestroy((hipStream_t)s));
+  if (!s) return DFX_OK;
+  {
+    StreamRegistry &r = streams();
+    std::lock_guard<std::mutex> lk(r.mu);
+    r.live.erase((hipStream_t)s);
+  }
+  HIP_TRY(hipStreamDestroy((hipStream_t)s));
   return DFX_OK;
 }
 int dfx_stream_sync(dfx_stream_t s) {
@@ -712,7 +748,8 @@ static void conv_release(dfx_conv *h) {
   (void)hipFree(h->d_src); (void)hipFree(h->d_dst); (void)hipFree(h->d_queue);
   (void)hipFree(h->d_prof);
   for (unsigned i = 0; i < DFX_QUEUE_RING; ++i)
-    if (h->slot_ev[i]) (void)hipEventDestroy(h->slot_ev[i]);
+    if (h->slot_ev[i] && h->slot_ev[i] != h->first_ev) (void)hipEventDestroy(h->slot_ev[i]);
+  if (h->first_ev) (void)hipEventDestroy(h->first_ev);
   delete h->ring_mu;
   delete h;
 }
@@ -1041,8 +1078,12 @@ int dfx_conv_create(const dfx_conv_desc *desc, dfx_conv_t **out) {
       // (224-pixel rows) 325.5-325.9 us with the last 2048 units split against 327.2-328.6; the headline's
       // half units have 2 tiles and cost it 0.3 % (256 units split) to 13 % (2048): profiles/r03/ab_half_units.txt.
       // DFX_HALF_UNITS = number of units to split (0: none) overrides the rule.
+      // Only conv_mfma.cuh decodes half-unit ids: conv_mfma_roles.cuh would take an id >= the real unit count for a
+      // whole unit of an image behind the batch.  Which of the two kernels runs is decided by the weights
+      // (dfx_conv_set_weights), after total_units is fixed, so every op whose SHAPE fits the role-specialised
+      // kernel goes without half units, also where it later falls back to conv_mfma.cuh.
       h->geom.half_from = 0x7fffffff;
-      if (h->geom.lazy_queue && !h->geom.pool && h->geom.th % 2 == 0) {
+      if (h->geom.lazy_queue && !h->geom.pool && h->geom.th % 2 == 0 && !h->roles_ok) {
         const int half_tiles = h->geom.linear ? ((h->geom.th / 2) * h->geom.tw + 31) / 32 : (h->geom.th / 2) * (h->geom.tw / 32);
         long long nh = half_tiles >= 7 ? 4LL * teams : 0;
         if (const char *e = tune("DFX_HALF_UNITS")) nh = std::max(0, atoi(e));
@@ -1638,27 +1679,49 @@ int dfx_conv_submit(dfx_conv_t *h, const void *src_dev, void *dst_dev, dfx_strea
     const hipStream_t st = (hipStream_t)s;
     std::lock_guard<std::mutex> lk(*h->ring_mu);
     const unsigned slot = h->launch_seq++ % DFX_QUEUE_RING;
-    if (h->launch_seq == 1) h->first_stream = st;
+    if (h->launch_seq == 1) {
+      h->first_stream = st;
+      h->first_serial = stream_serial(st);
+    }
     if (!h->multi_stream && st != h->first_stream) {
       // second stream seen: the launches so far (all on first_stream, no events) are covered by ONE event
-      // recorded there now -- a stream event stands for everything submitted before it
+      // recorded there now -- a stream event stands for everything submitted before it.  This stream waits for
+      // it here; the slots of those launches keep it, so that any OTHER stream that reuses one waits too.
       h->multi_stream = true;
       hipEvent_t e0 = nullptr;
       HIP_TRY(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-      hipError_t r = hipEventRecord(e0, h->first_stream);
+      // (a first stream of dfx_stream_create's that dfx_stream_destroy has destroyed since must not be touched)
+      const bool gone = h->first_serial != 0 && stream_serial(h->first_stream) != h->first_serial;
+      hipError_t r = gone ? hipErrorContextIsDestroyed : hipEventRecord(e0, h->first_stream);
       if (r == hipSuccess) r = hipStreamWaitEvent(st, e0, 0);
-      (void)hipEventDestroy(e0);
-      if (r != hipSuccess) HIP_TRY(hipDeviceSynchronize());  // (first_stream already destroyed by the caller)
-      for (unsigned i = 0; i < DFX_QUEUE_RING; ++i)
-        if (h->slot_state[i] == 1) h->slot_state[i] = 0;  // their launches are ordered before this one now
+      if (r == hipSuccess) {
+        ++h->ring_waits;
+        h->first_ev = e0;
+        for (unsigned i = 0; i < DFX_QUEUE_RING; ++i)
+          if (h->slot_state[i] == 1) {
+            h->slot_state[i] = 2;
+            h->slot_stream[i] = h->first_stream;
+            h->slot_ev[i] = e0;
+          }
+      } else {  // first_stream already destroyed by the caller: nothing to record on, wait for the device instead
+        (void)hipEventDestroy(e0);
+        if (!gone) (void)hipGetLastError();
+        HIP_TRY(hipDeviceSynchronize());
+        for (unsigned i = 0; i < DFX_QUEUE_RING; ++i)
+          if (h->slot_state[i] == 1) h->slot_state[i] = 0;  // their launches have finished
+      }
     }
-    if (h->slot_state[slot] == 2 && h->slot_stream[slot] != st) HIP_TRY(hipStreamWaitEvent(st, h->slot_ev[slot], 0));
+    if (h->slot_state[slot] == 2 && h->slot_stream[slot] != st) {
+      HIP_TRY(hipStreamWaitEvent(st, h->slot_ev[slot], 0));
+      ++h->ring_waits;
+    }
     g.queue += 2 * slot;
     if (mfma_dispatch(h, a, g, st, 0) != 0) return fail(DFX_ERR_UNSUPPORTED, "conv_submit: no kernel instance for this op");
     HIP_TRY(hipGetLastError());
     h->slot_stream[slot] = st;
     h->slot_state[slot] = 1;
     if (h->multi_stream) {
+      if (h->slot_ev[slot] == h->first_ev) h->slot_ev[slot] = nullptr;  // (borrowed: this launch needs its own)
       if (!h->slot_ev[slot]) HIP_TRY(hipEventCreateWithFlags(&h->slot_ev[slot], hipEventDisableTiming));
       HIP_TRY(hipEventRecord(h->slot_ev[slot], st));
       h->slot_state[slot] = 2;
@@ -1712,6 +1775,22 @@ int dfx_conv_query(const dfx_conv_t *h, dfx_conv_info *info) {
   info->algorithmic_bytes = conv_src_bytes(d) + conv_dst_bytes(d) +
                             (uint64_t)d.oc * d.ic * d.kh * d.kw + (uint64_t)d.oc1x1 * d.oc;
   snprintf(info->kernel_name, sizeof(info->kernel_name), "%s", h->kernel_name);
+  return DFX_OK;
+}
+
+// test hook: the unit hand-out of a resident-weight op as the host decided it (include/dfx.h lists the order)
+int dfx_debug_conv_sched(const dfx_conv_t *h, int32_t *out, int n) {
+  if (!h || !out || n < 0) return fail(DFX_ERR_INVALID, "conv_sched: null argument");
+  if (!h->geom.queue) return fail(DFX_ERR_UNSUPPORTED, "conv_sched: this op has no unit queue (%s)", h->kernel_name);
+  const MfmaGeom &g = h->geom;
+  int waits;
+  {
+    std::lock_guard<std::mutex> lk(*h->ring_mu);
+    waits = h->ring_waits;
+  }
+  const int32_t v[13] = {g.th, g.tw, g.linear, g.uy, g.ux, g.total_units, g.half_from, g.static_rounds, g.lazy_queue,
+                         g.pool, h->grid * MFMA_TEAMS, (h->roles_ok && h->roles) ? 1 : 0, waits};
+  for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
   return DFX_OK;
 }
 

@@ -155,7 +155,9 @@ int dfx_memcpy_h2d(void *dst_dev, const void *src_host, size_t bytes, dfx_stream
 int dfx_memcpy_d2h(void *dst_host, const void *src_dev, size_t bytes, dfx_stream_t s);
 int dfx_memset_device(void *dst_dev, int value, size_t bytes, dfx_stream_t s);
 int dfx_stream_create(dfx_stream_t *s);
-int dfx_stream_destroy(dfx_stream_t s);
+int dfx_stream_destroy(dfx_stream_t s);   /* the way to destroy a stream of dfx_stream_create's: a conv handle that was
+                                             submitted on it learns of it here.  A stream made elsewhere (a hipStream_t of
+                                             the caller's) must outlive the handles submitted on it. */
 int dfx_stream_sync(dfx_stream_t s);
 /* work enqueued on `waiter` after this call starts only when everything enqueued on `producer`
  * before it has finished (chains of asynchronous submits on different streams) */
@@ -192,7 +194,8 @@ int dfx_conv_set_weights(dfx_conv_t *h, const int8_t *wei_blocked, const void *b
  * host threads and on several streams at once: every launch works on its own copy of the
  * arguments and its own unit-queue slot.  There are 16 slots per handle: launches on one stream are
  * ordered anyway; with several streams a launch that finds its slot last used on ANOTHER stream first
- * waits, on the device, for that launch (a 17th concurrent launch queues behind the 1st).  Every op is ONE
+ * waits, on the device, for that launch (a 17th concurrent launch queues behind the 1st); the launches made
+ * while the handle had seen one stream only are covered by one event recorded when the second stream appears.  Every op is ONE
  * kernel launch (the two-launch "split:" ops of earlier versions are gone); dfx_conv_info.kernel_name names
  * the kernel, for the role-specialised one also its stage-1 requant route ("/fma", "/magic"), and says so
  * when an op runs on the scalar kernel because its dst reaches 4 GiB. */
@@ -233,6 +236,21 @@ int dfx_debug_scribble_lds(unsigned pattern, dfx_stream_t s);
  * it is first used; this is how a test reaches another code path afterwards.  Affects handles
  * created after the call. */
 int dfx_debug_set_tuning(const char *key, const char *value);
+/* Read-only: how the host hands out the units of a resident-weight op (conv_mfma.cuh, conv_mfma_roles.cuh); launches
+ * nothing.  Fills out[0 .. min(n, 13) - 1], in this order:
+ *    0 th, 1 tw        unit size in output rows / columns
+ *    2 linear          1: a unit spans whole rows (tw == ow); 0: column-split units
+ *    3 uy, 4 ux        units per image along y / x
+ *    5 total_units     ids the loaders run through (whole units + half units)
+ *    6 half_from       ids >= half_from are half units; INT32_MAX: none
+ *    7 static_rounds   units a loader owns before it turns to the queue
+ *    8 lazy_queue      1: lazy draws (store-bound ops)
+ *    9 pool            1: fused 2x2 max pooling
+ *   10 teams           loader streams of one launch (grid x 2)
+ *   11 roles           1: the role-specialised kernel runs the op (valid after dfx_conv_set_weights)
+ *   12 ring_waits      stream waits the queue-ring guard of dfx_conv_submit has issued on this handle so far
+ * DFX_ERR_UNSUPPORTED for an op without a unit queue (any other kernel). */
+int dfx_debug_conv_sched(const dfx_conv_t *h, int32_t *out, int n);
 
 #ifdef __cplusplus
 }

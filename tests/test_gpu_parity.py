@@ -87,10 +87,14 @@ def test_resident_kernel_cooperative_first_tile(hip, oracle, case):
     """enough units per team that the first ones are owned statically: the compute waves stage
     each team's first tile together with the weights (conv_mfma.cuh, coop0)."""
     data = C.generate(case)
-    got, info = hip.hip_conv(case, data)
+    got, info, s = hip.hip_conv_guarded(case, data)
     assert info.variant in (hip.dfa.VARIANT_MFMA_FUSED, hip.dfa.VARIANT_MFMA_CONV), info.kernel_name
-    units = case.bs * -(-case.oh // max(info.rows_per_unit, 1))   # (lower bound: x 1 column unit)
-    assert units >= 2 * 2 * info.grid, "shape too small to reach the statically owned first units"
+    # the hand-out as the library reports it (Conv.sched()): whole units only, at least two per loader, and a
+    # static split, which is what makes the first tiles cooperative
+    assert s.teams == 2 * info.grid and s.th == info.rows_per_unit, (s, info.grid, info.rows_per_unit)
+    assert s.total_units == case.bs * -(-case.oh // s.th) * -(-case.ow // s.tw) == case.bs * s.uy * s.ux, s
+    assert s.total_units >= 2 * s.teams, "shape too small to reach the statically owned first units"
+    assert s.static_rounds >= 1, s
     hip.assert_bit_equal(got, hip.oracle_conv(oracle, case, data), info.kernel_name.decode())
 
 
@@ -773,6 +777,8 @@ def test_repeated_submits_rearm_queue(hip, oracle):
         for o in outs:
             op.submit(src, o)
         torch.cuda.synchronize()
+        # one stream: the queue-ring guard issues no event call at all (the path bench.py measures)
+        assert op.sched().ring_waits == 0
         for o in outs:
             hip.assert_bit_equal(o.cpu().numpy(), ref, "repeat " + case.name)
         op.close()

@@ -14,6 +14,8 @@ _HEADER = os.path.join(_ROOT, "include", "dfx.h")
 
 DFX_UNDEF, DFX_F32, DFX_S32, DFX_S8, DFX_U8 = 0, 1, 2, 3, 4
 ROUND_NEAREST, ROUND_DOWN = 0, 1
+FMT_NHWC, FMT_NCHW = 0, 1
+REORDER_FLAT, REORDER_GENERIC, REORDER_SMALLC, REORDER_TRANSPOSE = 0, 1, 2, 3
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -53,6 +55,17 @@ class PoolDesc(ctypes.Structure):
 class EltwiseDesc(ctypes.Structure):
     _fields_ = [("n_inputs", ctypes.c_int32), ("elems", ctypes.c_int64), ("dt", ctypes.c_int32),
                 ("post_relu", ctypes.c_int32)]
+
+
+class ReorderDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "h", "w", "src_c", "dst_c", "src_fmt", "dst_fmt", "src_dt",
+                                             "dst_dt", "round_mode", "n_scales")]
+
+
+class ReorderInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device", "tile_pixels",
+                                             "channel_block", "vec_plane", "vec_pixel")] + \
+               [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
 
 
 # order of dfx_debug_conv_sched (include/dfx.h)
@@ -140,6 +153,11 @@ def lib():
         "dfx_eltwise_create": (i32, [ctypes.POINTER(EltwiseDesc), ctypes.POINTER(vp)]),
         "dfx_eltwise_submit": (i32, [vp, ctypes.POINTER(vp), vp, vp]),
         "dfx_eltwise_destroy": (i32, [vp]),
+        "dfx_reorder_create": (i32, [ctypes.POINTER(ReorderDesc), vp, ctypes.POINTER(vp)]),
+        "dfx_reorder_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_reorder_submit_host": (i32, [vp, vp, vp]),
+        "dfx_reorder_query": (i32, [vp, ctypes.POINTER(ReorderInfo)]),
+        "dfx_reorder_destroy": (i32, [vp]),
         "dfx_debug_scribble_lds": (i32, [ctypes.c_uint, vp]),
         "dfx_debug_set_tuning": (i32, [ctypes.c_char_p, ctypes.c_char_p]),
         "dfx_debug_conv_sched": (i32, [vp, ctypes.POINTER(ctypes.c_int32), i32]),
@@ -305,6 +323,54 @@ class EltwiseSum:
     def close(self):
         if self._h:
             lib().dfx_eltwise_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Reorder:
+    """dfx_reorder_* handle: layout (NHWC <-> NCHW), dtype and scale conversion of an activation tensor with
+    channel pad / crop (include/dfx.h).  `shape` is the logical (bs, c, h, w) of the source; the physical order
+    of src and dst follows src_fmt / dst_fmt."""
+
+    def __init__(self, shape_nchw, src_dtype, dst_dtype, src_fmt=FMT_NCHW, dst_fmt=FMT_NHWC, dst_c=None,
+                 scales=None, round_mode=ROUND_NEAREST):
+        bs, c, h, w = shape_nchw
+        dst_c = c if dst_c is None else dst_c
+        src_dt = src_dtype if isinstance(src_dtype, int) else _DT[np.dtype(src_dtype)]
+        dst_dt = dst_dtype if isinstance(dst_dtype, int) else _DT[np.dtype(dst_dtype)]
+        sc = None if scales is None else np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+        d = ReorderDesc(bs, h, w, c, dst_c, src_fmt, dst_fmt, src_dt, dst_dt, round_mode, 0 if sc is None else sc.size)
+        self.desc = d
+        self.src_shape = (bs, h, w, c) if src_fmt == FMT_NHWC else (bs, c, h, w)
+        self.dst_shape = (bs, h, w, dst_c) if dst_fmt == FMT_NHWC else (bs, dst_c, h, w)
+        self.src_np_dtype, self.dst_np_dtype = _NP.get(src_dt), _NP.get(dst_dt)
+        self._h = ctypes.c_void_p()
+        _check(lib().dfx_reorder_create(ctypes.byref(d), _p(sc), ctypes.byref(self._h)))
+
+    def submit(self, src_dev, dst_dev, stream=None):
+        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers), 16-byte aligned."""
+        _check(lib().dfx_reorder_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
+
+    def submit_host(self, src_np):
+        src = np.ascontiguousarray(src_np, dtype=self.src_np_dtype)
+        assert src.shape == self.src_shape, (src.shape, self.src_shape)
+        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
+        _check(lib().dfx_reorder_submit_host(self._h, _p(src), _p(dst)))
+        return dst
+
+    def info(self):
+        i = ReorderInfo()
+        _check(lib().dfx_reorder_query(self._h, ctypes.byref(i)))
+        return i
+
+    def close(self):
+        if self._h:
+            lib().dfx_reorder_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -29,6 +29,7 @@
 #include "conv_pw.cuh"
 #include "conv_mfma_roles.cuh"
 #include "dfx_device.cuh"
+#include "dfx_internal.h"
 
 namespace dfx {
 int launch_conv_generic(const ConvArgs &a, hipStream_t s, int *grid_out, int *lds_out);
@@ -74,23 +75,13 @@ using namespace dfx;
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char *fmt, ...) {
+int dfx::fail(int code, const char *fmt, ...) {  // (declared in dfx_internal.h)
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return fail(e_ == hipErrorNoDevice ? DFX_ERR_NO_DEVICE : DFX_ERR_HIP, "%s: %s",   \
-                  #expr, hipGetErrorString(e_));                                        \
-  } while (0)
-
-static size_t dt_size(int dt) { return (dt == DFX_F32 || dt == DFX_S32) ? 4 : 1; }
 
 // ---- testing / tuning switches.  The environment is read ONCE, when the
 //      library is first used; tests flip a switch afterwards with dfx_debug_set_tuning(). ----
@@ -145,19 +136,6 @@ unsigned long long stream_serial(hipStream_t st) {
 
 // launches of one MFMA-variant handle that may be in flight at the same time (any streams)
 constexpr unsigned DFX_QUEUE_RING = 16;
-
-// every entry point that takes a handle runs on the device the handle was created on
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (dev >= 0 && dev != prev) (void)hipSetDevice(dev);
-    else prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 struct dfx_conv {
   int device;  // ordinal the handle lives on (current device at dfx_conv_create)

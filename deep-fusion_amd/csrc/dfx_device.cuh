@@ -128,4 +128,23 @@ struct EltwiseArgs {
   long long elems;
 };
 
+// kernel arguments of reorder.hip (filled by reorder_api.hip)
+constexpr int SMALLC_PX = 1024;  // pixels per workgroup of the smallc kernel
+enum { REORDER_FLAT = 0, REORDER_GENERIC = 1, REORDER_SMALLC = 2, REORDER_TRANSPOSE = 3 };
+struct ReorderArgs {
+  const unsigned char *src;
+  unsigned char *dst;
+  const float *scales;  // device, src_c entries (a single or absent scale is expanded by the host)
+  int bs, hw, src_c, dst_c, src_fmt, dst_fmt, src_dt, dst_dt, rm;
+  int uniform_scale;    // every entry of scales is the same: the flat kernel skips the channel arithmetic
+  int inner;            // flat: elements between channel changes (1 for NHWC, h*w for NCHW)
+  int path;             // REORDER_*
+  int grid, lds_bytes;
+  int tp, cb;           // transpose: pixels per tile (64 | 32), channels per block (32 | 64, or the whole depth)
+  int cblocks, ptiles;  // transpose / smallc: channel blocks, pixel tiles per image
+  int vec_plane, vec_pixel;  // transpose: 16-byte accesses on the NCHW / NHWC side (else one element per lane)
+  int flat_pixel;       // transpose: the block is the whole depth, a tile's NHWC side is indexed as one contiguous span
+  long long total;      // flat: elements; generic: dst elements
+};
+
 }  // namespace dfx

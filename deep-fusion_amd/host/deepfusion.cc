@@ -832,7 +832,143 @@ private:
   detail::op_state st_;
 };
 
+// ---- activation reorder (dfx_reorder_*): layout / dtype / scale conversion, channel pad and crop ----
+class op_reorder : public op {
+public:
+  op_reorder(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &dst, const std::vector<float> &scales,
+             round_mode rm)
+      : src_(src.get()), dst_(dst.get()), scales_(scales), h_(nullptr) {
+    using fmt = memory::format;
+    if (!src_ || !dst_) error_and_exit("Init Reorder op failed! (null tensor)");
+    for (memory *m : {src_, dst_})
+      if (m->dim_format() != fmt::nchw && m->dim_format() != fmt::nhwc) error_and_exit("Init Reorder op failed! (format)");
+    auto s = src_->std_dims(), o = dst_->std_dims();
+    if (s[0] != o[0]) error_and_exit("Init Reorder op failed! (Batch size do not equal)");
+    if (s[2] != o[2] || s[3] != o[3]) error_and_exit("Init Reorder op failed! (shape)");
+    dfx_reorder_desc d;
+    memset(&d, 0, sizeof(d));
+    d.bs = s[0]; d.h = s[2]; d.w = s[3]; d.src_c = s[1]; d.dst_c = o[1];
+    d.src_fmt = src_->dim_format() == fmt::nhwc ? DFX_FMT_NHWC : DFX_FMT_NCHW;
+    d.dst_fmt = dst_->dim_format() == fmt::nhwc ? DFX_FMT_NHWC : DFX_FMT_NCHW;
+    d.src_dt = to_dfx_dtype(src_->data_type());
+    d.dst_dt = to_dfx_dtype(dst_->data_type());
+    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.n_scales = (int)scales_.size();
+    // both layouts are batch-major: a batch shard is a contiguous byte range of src and of dst
+    const size_t src_img = (size_t)d.h * d.w * d.src_c * dtype_size(src_->data_type());
+    const size_t dst_img = (size_t)d.h * d.w * d.dst_c * dtype_size(dst_->data_type());
+    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
+      shard sh;
+      sh.r = r;
+      sh.src_off = r.n0 * src_img; sh.src_bytes = r.n * src_img;
+      sh.dst_off = r.n0 * dst_img; sh.dst_bytes = r.n * dst_img;
+      dfx_reorder_desc ds = d;
+      ds.bs = r.n;
+      check_dfx(dfx_set_device(r.device), "set device");
+      if (dfx_reorder_create(&ds, scales_.data(), &sh.h) != DFX_OK) error_and_exit("Init Reorder op failed! (%s)", dfx_last_error());
+      check_dfx(dfx_stream_create(&sh.stream), "stream create");
+      check_dfx(dfx_mem_alloc_device(&sh.src, sh.src_bytes), "device alloc");
+      check_dfx(dfx_mem_alloc_device(&sh.dst, sh.dst_bytes), "device alloc");
+      shards_.push_back(sh);
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    if (dfx_reorder_create(&d, scales_.data(), &h_) != DFX_OK) error_and_exit("Init Reorder op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_reorder() override {
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      dfx_reorder_destroy(sh.h);
+      dfx_stream_destroy(sh.stream);
+      dfx_mem_free_device(sh.src);
+      dfx_mem_free_device(sh.dst);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire(*dst_);
+    dfx_reorder_destroy(h_);
+  }
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  // (sharded: host in -> host out like submit(), without the final wait -- see op_conv)
+  void submit_async() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(false);
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled(*dst_);
+    }
+  }
+
+protected:
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  void enqueue_shards() {
+    const char *hs = static_cast<const char *>(src_->host_data());
+    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.src_off, sh.src_bytes, sh.stream), "H2D copy");
+      check_dfx(dfx_reorder_submit(sh.h, sh.src, sh.dst, sh.stream), "reorder submit");
+      check_dfx(dfx_memcpy_d2h(hd + sh.dst_off, sh.dst, sh.dst_bytes, sh.stream), "D2H copy");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    detail::op_state::host_is_current(*dst_);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  void run(bool sync_host) {
+    void *s = st_.sync_in(*src_, sync_host);
+    void *o = st_.device_out(*dst_);
+    st_.profile_begin();
+    check_dfx(dfx_reorder_submit(h_, s, o, st_.stream), "reorder submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "reorder"; }
+
+private:
+  struct shard {
+    detail::shard_range r;
+    dfx_reorder_t *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    void *src = nullptr, *dst = nullptr;
+    size_t src_off = 0, src_bytes = 0, dst_off = 0, dst_bytes = 0;
+  };
+  memory *src_, *dst_;
+  std::vector<float> scales_;
+  dfx_reorder_t *h_;
+  detail::op_state st_;
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
+};
+
 }  // namespace
+
+std::unique_ptr<op> reorder(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &dst,
+                            const std::vector<float> &scales, round_mode rm) {
+  return std::unique_ptr<op>(new op_reorder(src, dst, scales, rm));
+}
 
 std::unique_ptr<op> conv_relu_pool(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei,
                                    const std::unique_ptr<memory> &bia, std::array<int, 2> conv_stride,

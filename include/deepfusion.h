@@ -211,7 +211,17 @@ std::unique_ptr<op> eltwise_sum(const std::vector<std::unique_ptr<memory>> &srcs
                                 std::unique_ptr<memory> &dst,
                                 bool post_relu = true);
 
-// ---- extension: the reorder the reference never shipped (deepfusion.cc:44-50) ----
+// ---- extension: activation reorder on the device -- layout (nchw <-> nhwc), dtype and scale conversion with
+// channel padding / cropping (dfx_reorder_* in dfx.h; the reference's tests use MKL-DNN's reorder for this,
+// parity unpinned).  For every channel k of dst: k < src channels ? cvt(float(src) * scale[k]) : 0, where cvt
+// for u8 / s8 rounds (ties to even, or down), maps NaN to 0 and saturates the value; f32 stores the product.
+// src: f32 | s32 | s8 | u8, dst: f32 | u8 | s8, each nchw or nhwc; channel counts come from std_dims()[1] and
+// may differ (dst wider: zero channels are appended; narrower: the rest is dropped); batch, height and width
+// must match.  scales: none (1.0f), one, or one per source channel. ----
+std::unique_ptr<op> reorder(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &dst,
+                            const std::vector<float> &scales = {}, round_mode rm = round_mode::nearest);
+
+// ---- extension: the weight reorder the reference never shipped (deepfusion.cc:44-50) ----
 // Writes plain oihw s8 weights into `blocked` (an OIhw4i16o4i memory of the same
 // logical dims) in the [O/16][I/16][kh][kw][4i][16o][4i] byte order.
 void reorder_weights(const s8 *oihw, const std::unique_ptr<memory> &blocked);

@@ -135,6 +135,46 @@ typedef struct dfx_eltwise_desc {
                                dtype's range, f32 sums left to right */
 } dfx_eltwise_desc;
 typedef struct dfx_eltwise dfx_eltwise_t;
+
+/* ---- activation reorder: layout (NHWC <-> NCHW), dtype and scale conversion, channel pad / crop, on the
+ *      device.  The reference ships no reorder (its tests and benches use MKL-DNN's reorder primitive):
+ *      parity unpinned; the semantics are MKL-DNN's saturating reorder.  Over a logical {bs, c, h, w}
+ *      tensor, for every destination channel k < dst_c:
+ *        k >= src_c:  dst = 0 (+0.0f)                                      (channel padding)
+ *        else         v = (float)src[n,k,y,x]     u8 / s8 exact, s32 round-to-nearest-even, f32 as is
+ *                     v = v * scale[k]            ONE separately rounded f32 multiply; n_scales 0: 1.0f,
+ *                                                 1: scale[0] for every channel, src_c: per channel
+ *                     f32 dst: store v
+ *                     u8 / s8 dst: rint(v) (ties to even; DFX_ROUND_NEAREST) or floor(v) (DFX_ROUND_DOWN),
+ *                                  NaN -> 0, else clamped to [0,255] / [-128,127]
+ *      Source channels >= dst_c are dropped.  This is NOT the conv epilogue's conversion (vcvtps2dq +
+ *      vpmovusdb on the bit pattern): a reorder saturates the value, +inf becomes 255.  Denormal values
+ *      are kept (the library is not built with flush-to-zero). ---- */
+enum { DFX_FMT_NHWC = 0, DFX_FMT_NCHW = 1 };
+typedef struct dfx_reorder_desc {
+  int32_t bs, h, w, src_c, dst_c;
+  int32_t src_fmt, dst_fmt;  /* DFX_FMT_*; all four combinations */
+  int32_t src_dt, dst_dt;    /* src: DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8; dst: DFX_F32 | DFX_U8 | DFX_S8
+                                (DFX_S32: DFX_ERR_UNSUPPORTED) */
+  int32_t round_mode;        /* DFX_ROUND_* */
+  int32_t n_scales;          /* 0 | 1 | src_c */
+} dfx_reorder_desc;
+enum {  /* dfx_reorder_info.path */
+  DFX_REORDER_FLAT = 0,      /* same layout, same channel count: 16 bytes of the wider side per lane */
+  DFX_REORDER_GENERIC = 1,   /* same layout with channel pad / crop: one element per lane */
+  DFX_REORDER_SMALLC = 2,    /* NCHW, src_c <= 4 -> NHWC, dst_c <= 16 (images): no LDS */
+  DFX_REORDER_TRANSPOSE = 3  /* NCHW <-> NHWC through an LDS tile */
+};
+typedef struct dfx_reorder_info {
+  int32_t path;
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  int32_t tile_pixels, channel_block;  /* transpose path: pixels x channels of one workgroup's tile */
+  int32_t vec_plane, vec_pixel;        /* transpose path: 1 = 16-byte accesses on the NCHW / NHWC side */
+  uint64_t algorithmic_bytes;          /* bytes read of the channels kept + bytes written, one submit */
+  char kernel_name[96];
+} dfx_reorder_info;
+typedef struct dfx_reorder dfx_reorder_t;
 typedef void *dfx_stream_t; /* a hipStream_t; NULL = the default stream */
 typedef void *dfx_event_t;  /* a hipEvent_t */
 
@@ -226,6 +266,20 @@ int dfx_pool_destroy(dfx_pool_t *h);
 int dfx_eltwise_create(const dfx_eltwise_desc *desc, dfx_eltwise_t **out);
 int dfx_eltwise_submit(dfx_eltwise_t *h, const void *const *srcs_dev, void *dst_dev, dfx_stream_t s);
 int dfx_eltwise_destroy(dfx_eltwise_t *h);
+
+/* ---- activation reorder (dfx_reorder_desc above).  The descriptor is validated before anything touches the
+ *      device: DFX_ERR_INVALID for a non-positive dimension, a bad format / dtype / round mode, an n_scales
+ *      other than 0, 1 or src_c, a missing or non-finite scale; DFX_ERR_UNSUPPORTED for an s32 dst and for
+ *      one image of 2^31 elements or more (whole tensors beyond 2^31 bytes are fine).  The scales are copied;
+ *      the handle owns them and lives on the device current at create time.  submit is asynchronous on any
+ *      stream, several submits of one handle may be in flight at once.  src_dev and dst_dev must be
+ *      16-byte aligned (DFX_ERR_INVALID otherwise, nothing is launched): the kernels use 16-byte accesses
+ *      relative to them.  No CPU fallback. ---- */
+int dfx_reorder_create(const dfx_reorder_desc *desc, const float *scales_host, dfx_reorder_t **out);
+int dfx_reorder_submit(dfx_reorder_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_reorder_submit_host(dfx_reorder_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_reorder_query(const dfx_reorder_t *h, dfx_reorder_info *info);
+int dfx_reorder_destroy(dfx_reorder_t *h);
 
 /* ---- test hooks (not part of the reference's surface; used by tests/ only) ---- */
 /* Overwrites the LDS of every CU with a pattern (asynchronous, on `s`): makes a kernel that

@@ -16,6 +16,7 @@ DFX_UNDEF, DFX_F32, DFX_S32, DFX_S8, DFX_U8 = 0, 1, 2, 3, 4
 ROUND_NEAREST, ROUND_DOWN = 0, 1
 FMT_NHWC, FMT_NCHW = 0, 1
 REORDER_FLAT, REORDER_GENERIC, REORDER_SMALLC, REORDER_TRANSPOSE = 0, 1, 2, 3
+CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -66,6 +67,18 @@ class ReorderInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device", "tile_pixels",
                                              "channel_block", "vec_plane", "vec_pixel")] + \
                [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
+
+
+class CatConvDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_inputs", "bs", "h", "w", "oc", "dst_dt", "bia_dt", "relu", "round_mode",
+                                             "nscales", "force_path")] + \
+               [("channels", ctypes.POINTER(ctypes.c_int32))]
+
+
+class CatConvInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
 
 
 # order of dfx_debug_conv_sched (include/dfx.h)
@@ -158,6 +171,12 @@ def lib():
         "dfx_reorder_submit_host": (i32, [vp, vp, vp]),
         "dfx_reorder_query": (i32, [vp, ctypes.POINTER(ReorderInfo)]),
         "dfx_reorder_destroy": (i32, [vp]),
+        "dfx_catconv_create": (i32, [ctypes.POINTER(CatConvDesc), ctypes.POINTER(vp)]),
+        "dfx_catconv_set_weights": (i32, [vp, vp, vp, vp]),
+        "dfx_catconv_submit": (i32, [vp, ctypes.POINTER(vp), vp, vp]),
+        "dfx_catconv_submit_host": (i32, [vp, ctypes.POINTER(vp), vp]),
+        "dfx_catconv_query": (i32, [vp, ctypes.POINTER(CatConvInfo)]),
+        "dfx_catconv_destroy": (i32, [vp]),
         "dfx_debug_scribble_lds": (i32, [ctypes.c_uint, vp]),
         "dfx_debug_set_tuning": (i32, [ctypes.c_char_p, ctypes.c_char_p]),
         "dfx_debug_conv_sched": (i32, [vp, ctypes.POINTER(ctypes.c_int32), i32]),
@@ -371,6 +390,59 @@ class Reorder:
     def close(self):
         if self._h:
             lib().dfx_reorder_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ConcatConv:
+    """dfx_catconv_* handle: channel concat of NHWC u8 branches + pointwise conv in one launch (include/dfx.h).
+    The result equals Concat followed by the unfused 1x1 Conv bit for bit; the concatenated tensor is never
+    written on the fused path."""
+
+    def __init__(self, bs, h, w, channels, oc, dst_dt=DFX_U8, bia_dt=DFX_UNDEF, relu=False, rm=ROUND_NEAREST,
+                 nscales=1, force_path=CATCONV_AUTO):
+        self.channels = list(channels)
+        self._ch = (ctypes.c_int32 * len(self.channels))(*self.channels)
+        d = CatConvDesc(len(self.channels), bs, h, w, oc, dst_dt, bia_dt, int(relu), rm, nscales, force_path, self._ch)
+        self.desc = d
+        self.dst_shape = (bs, h, w, oc)
+        self.src_shapes = [(bs, h, w, c) for c in self.channels]
+        self.dst_np_dtype = _NP.get(dst_dt)
+        self._h = ctypes.c_void_p()
+        _check(lib().dfx_catconv_create(ctypes.byref(d), ctypes.byref(self._h)))
+
+    def set_weights(self, wei_blk, scales, bia=None):
+        """wei_blk: {oc, sum(channels), 1, 1} in OIhw4i16o4i order (reorder_oihw_to_blocked)"""
+        ws = [np.ascontiguousarray(wei_blk, dtype=np.int8), None if bia is None else np.ascontiguousarray(bia),
+              np.ascontiguousarray(scales, dtype=np.float32)]
+        _check(lib().dfx_catconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+    def submit(self, srcs_dev, dst_dev, stream=None):
+        """asynchronous; srcs_dev: one torch CUDA tensor (or raw pointer) per branch, 16-byte aligned"""
+        ptrs = (ctypes.c_void_p * len(srcs_dev))(*[_dev_ptr(s).value for s in srcs_dev])
+        _check(lib().dfx_catconv_submit(self._h, ptrs, _dev_ptr(dst_dev), _stream_ptr(stream)))
+
+    def submit_host(self, srcs_np):
+        srcs = [np.ascontiguousarray(s, dtype=np.uint8) for s in srcs_np]
+        assert [s.shape for s in srcs] == self.src_shapes, ([s.shape for s in srcs], self.src_shapes)
+        ptrs = (ctypes.c_void_p * len(srcs))(*[s.ctypes.data for s in srcs])
+        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
+        _check(lib().dfx_catconv_submit_host(self._h, ptrs, _p(dst)))
+        return dst
+
+    def info(self):
+        i = CatConvInfo()
+        _check(lib().dfx_catconv_query(self._h, ctypes.byref(i)))
+        return i
+
+    def close(self):
+        if self._h:
+            lib().dfx_catconv_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -134,6 +134,8 @@ unsigned long long stream_serial(hipStream_t st) {
 }
 }  // namespace
 
+unsigned long long dfx::stream_serial_of(hipStream_t st) { return stream_serial(st); }  // (declared in dfx_internal.h)
+
 // launches of one MFMA-variant handle that may be in flight at the same time (any streams)
 constexpr unsigned DFX_QUEUE_RING = 16;
 
@@ -589,6 +591,16 @@ static int direct_dispatch(dfx_conv *h, const ConvArgs &a, hipStream_t s, int mo
     case DFX_U8: return launch_conv_direct_u8(a, h->dgeom, h->nw, h->wo, h->G, h->wo1, h->grid, h->lds, s, mode);
   }
   return -1;
+}
+
+bool dfx::conv_pw_view(const dfx_conv *h, ConvArgs *args, PwGeom *geom, int *lds) {  // (declared in dfx_internal.h)
+  if (!h || !h->pw || h->variant != DFX_VARIANT_MFMA_STREAM) return false;
+  *args = h->args;
+  *geom = h->pwgeom;
+  geom->fast = h->dgeom.fast;
+  geom->m0 = h->dgeom.m0;
+  *lds = h->lds;
+  return true;
 }
 
 // ---- streamed-weight variant (conv_stream.cuh) ----

@@ -1,5 +1,5 @@
 // dfx_internal.h -- the few host-side helpers the translation units behind include/dfx.h share
-// (dfx_api.hip, reorder_api.hip).  Not installed, not part of the C ABI.
+// (dfx_api.hip, reorder_api.hip, catconv_api.hip).  Not installed, not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +11,18 @@ namespace dfx {
 
 // records the thread's dfx_last_error() message and returns `code` (defined in dfx_api.hip)
 __attribute__((visibility("hidden"))) int fail(int code, const char *fmt, ...);
+
+// The pointwise kernel's view of a conv handle (defined in dfx_api.hip): its kernel arguments without src / dst (packed
+// weight image, constants, flags), its geometry with the requant-route proofs of the last dfx_conv_set_weights (fast,
+// m0) and its LDS size.  false when the handle is not served by conv_pw.cuh.  catconv_api.hip launches its own kernel
+// on these, so that neither the packing nor the proofs exist twice.
+struct ConvArgs;
+struct PwGeom;
+__attribute__((visibility("hidden"))) bool conv_pw_view(const dfx_conv *h, ConvArgs *args, PwGeom *geom, int *lds);
+
+// serial number of a live stream of dfx_stream_create's (never reused), 0 for any other stream: how a handle that
+// remembers a stream finds out that dfx_stream_destroy has destroyed it since (defined in dfx_api.hip)
+__attribute__((visibility("hidden"))) unsigned long long stream_serial_of(hipStream_t st);
 
 inline size_t dt_size(int dt) { return (dt == DFX_F32 || dt == DFX_S32) ? 4 : 1; }
 

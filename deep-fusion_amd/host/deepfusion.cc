@@ -963,7 +963,201 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- concat + pointwise conv in one launch (dfx_catconv_*): the branches are read in place, the concatenated
+// tensor is never written.  Checks are op_concat's for the branches and op_conv's for weights, bias and dst. ----
+class op_concat_conv : public op {
+public:
+  op_concat_conv(const std::vector<std::unique_ptr<memory>> &srcs, const std::unique_ptr<memory> &wei,
+                 const std::unique_ptr<memory> &bia, std::unique_ptr<memory> &dst, bool relu,
+                 const std::vector<float> &scales, round_mode rm)
+      : wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0), packed_versions_(0) {
+    using fmt = memory::format;
+    if (!wei_ || !dst_ || srcs.empty()) error_and_exit("Init ConcatConv op failed! (null tensor)");
+    if (wei_->data_type() != memory::dtype::s8 || dst_->dim_format() != fmt::nhwc ||
+        (wei_->dim_format() != fmt::OIhw4i16o4i && wei_->dim_format() != fmt::gOIhw4i16o4i) ||
+        (bia_ && bia_->dim_format() != fmt::x))
+      error_and_exit("Init ConcatConv op failed! (data type / format)");
+    auto w = wei_->std_dims(), o = dst_->std_dims();
+    std::vector<int32_t> ch;
+    int total = 0;
+    for (auto &m : srcs) {
+      if (!m || m->dim_format() != fmt::nhwc || m->data_type() != memory::dtype::u8)
+        error_and_exit("Init ConcatConv op failed! (branches must be nhwc u8)");
+      auto sd = m->std_dims();
+      if (sd[0] != o[0]) error_and_exit("Init ConcatConv op failed! (Batch size do not equal)");
+      if (sd[2] != o[2] || sd[3] != o[3]) error_and_exit("Init ConcatConv op failed! (shape)");
+      srcs_.push_back(m.get());
+      ch.push_back(sd[1]);
+      total += sd[1];
+    }
+    if (total != w[1]) error_and_exit("Init ConcatConv op failed! (Input channel do not match)");
+    if (w[2] != 1 || w[3] != 1) error_and_exit("Init ConcatConv op failed! (conv must be 1x1 kernel)");
+    if (o[1] != w[0]) error_and_exit("Init ConcatConv op failed! (Output channel do not match)");
+    if (bia_ && (int)bia_->size() != w[0]) error_and_exit("Init ConcatConv op failed! (Bias channel do not match)");
+    dfx_catconv_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n_inputs = (int)ch.size();
+    d.bs = o[0]; d.h = o[2]; d.w = o[3]; d.oc = w[0];
+    d.dst_dt = to_dfx_dtype(dst_->data_type());
+    d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
+    d.relu = relu;
+    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.nscales = (int)scales_.size();
+    d.force_path = -1;
+    d.channels = ch.data();
+    const size_t px = (size_t)d.h * d.w;
+    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
+      shard sh;
+      sh.r = r;
+      dfx_catconv_desc ds = d;
+      ds.bs = r.n;
+      check_dfx(dfx_set_device(r.device), "set device");
+      if (dfx_catconv_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init ConcatConv op failed! (%s)", dfx_last_error());
+      check_dfx(dfx_stream_create(&sh.stream), "stream create");
+      for (int c : ch) {
+        void *p = nullptr;
+        check_dfx(dfx_mem_alloc_device(&p, (size_t)r.n * px * c), "device alloc");
+        sh.srcs.push_back(p);
+        sh.src_img.push_back(px * c);
+      }
+      sh.dst_img = px * d.oc * dtype_size(dst_->data_type());
+      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * sh.dst_img), "device alloc");
+      shards_.push_back(sh);
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    if (dfx_catconv_create(&d, &h_) != DFX_OK) error_and_exit("Init ConcatConv op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_concat_conv() override {
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      dfx_catconv_destroy(sh.h);
+      dfx_stream_destroy(sh.stream);
+      for (void *p : sh.srcs) dfx_mem_free_device(p);
+      dfx_mem_free_device(sh.dst);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire(*dst_);
+    dfx_catconv_destroy(h_);
+  }
+
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  void submit_async() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(false);
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled(*dst_);
+    }
+  }
+
+protected:
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  unsigned long long weights_hash() {
+    using detail::hash_bytes;
+    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
+    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
+    return v | 1ull;
+  }
+  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
+  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard; a shard is an offset into every branch)
+    const unsigned long long v = weights_hash();
+    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      if (v != sh.wei_seen) {
+        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+        check_dfx(dfx_catconv_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
+                  "concat_conv set_weights");
+        sh.wei_seen = v;
+      }
+      std::vector<const void *> p;
+      for (size_t k = 0; k < srcs_.size(); ++k) {
+        const char *hs = static_cast<const char *>(srcs_[k]->host_data());
+        check_dfx(dfx_memcpy_h2d(sh.srcs[k], hs + sh.r.n0 * sh.src_img[k], sh.r.n * sh.src_img[k], sh.stream), "H2D copy");
+        p.push_back(sh.srcs[k]);
+      }
+      check_dfx(dfx_catconv_submit(sh.h, p.data(), sh.dst, sh.stream), "concat_conv submit");
+      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * sh.dst_img, sh.dst, sh.r.n * sh.dst_img, sh.stream), "D2H copy");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    detail::op_state::host_is_current(*dst_);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
+    const unsigned long long vers = weights_versions();
+    if (sync_host || vers != packed_versions_) {
+      const unsigned long long hash = weights_hash();
+      if (hash != packed_hash_) {
+        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
+        check_dfx(dfx_catconv_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
+                  "concat_conv set_weights");
+        packed_hash_ = hash;
+      }
+      packed_versions_ = vers;
+    }
+    std::vector<const void *> p;
+    for (memory *m : srcs_) p.push_back(st_.sync_in(*m, sync_host));
+    void *o = st_.device_out(*dst_);
+    st_.profile_begin();
+    check_dfx(dfx_catconv_submit(h_, p.data(), o, st_.stream), "concat_conv submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "concat_conv"; }
+
+private:
+  struct shard {
+    detail::shard_range r;
+    dfx_catconv_t *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    std::vector<void *> srcs;
+    std::vector<size_t> src_img;  // bytes per image of each branch
+    void *dst = nullptr;
+    size_t dst_img = 0;
+    unsigned long long wei_seen = 0;
+  };
+  std::vector<memory *> srcs_;
+  memory *wei_, *bia_, *dst_;
+  std::vector<float> scales_;
+  dfx_catconv_t *h_;
+  unsigned long long packed_hash_, packed_versions_;
+  detail::op_state st_;
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
+};
+
 }  // namespace
+
+std::unique_ptr<op> concat_conv(const std::vector<std::unique_ptr<memory>> &srcs, const std::unique_ptr<memory> &wei,
+                                const std::unique_ptr<memory> &bia, std::unique_ptr<memory> &dst, bool relu,
+                                std::vector<float> scales, round_mode rm) {
+  return std::unique_ptr<op>(new op_concat_conv(srcs, wei, bia, dst, relu, scales, rm));
+}
 
 std::unique_ptr<op> reorder(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &dst,
                             const std::vector<float> &scales, round_mode rm) {

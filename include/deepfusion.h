@@ -221,6 +221,22 @@ std::unique_ptr<op> eltwise_sum(const std::vector<std::unique_ptr<memory>> &srcs
 std::unique_ptr<op> reorder(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &dst,
                             const std::vector<float> &scales = {}, round_mode rm = round_mode::nearest);
 
+// ---- extension: channel concat + pointwise (1x1, stride 1, unpadded) conv in ONE launch (dfx_catconv_* in dfx.h): the
+// join of an Inception module, a DenseNet bottleneck or a SqueezeNet squeeze layer.  The conv reads the nhwc u8
+// branches in place; the concatenated tensor is never written.  dst holds, bit for bit, what concat(srcs, tmp) followed
+// by conv(tmp, wei, bia, {1,1}, {0,0}, dst, relu, scales, rm) produces (ReLU on u8 branches is the identity, so a
+// post_relu concat is covered too).  wei: OIhw4i16o4i {oc, sum of the branches' channels, 1, 1}; every branch a multiple
+// of 16 channels.  Shapes outside the one-launch kernel's class (dfx.h, DFX_CATCONV_FUSED) run as two launches behind
+// the same call.  submit / submit_async / wait behave like conv's; borrowed weights are hashed and re-packed like
+// conv's.  Under DEEPFUSION_DEVICES the batch is sharded as conv() and concat() shard it (all tensors are batch-major:
+// a shard is an offset into every branch); the bytes are the same either way. ----
+std::unique_ptr<op> concat_conv(const std::vector<std::unique_ptr<memory>> &srcs,   // nhwc u8
+                                const std::unique_ptr<memory> &wei,
+                                const std::unique_ptr<memory> &bia,
+                                std::unique_ptr<memory> &dst,
+                                bool relu = false, std::vector<float> scales = {1.f},
+                                round_mode rm = round_mode::nearest);
+
 // ---- extension: the weight reorder the reference never shipped (deepfusion.cc:44-50) ----
 // Writes plain oihw s8 weights into `blocked` (an OIhw4i16o4i memory of the same
 // logical dims) in the [O/16][I/16][kh][kw][4i][16o][4i] byte order.

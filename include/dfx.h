@@ -175,6 +175,41 @@ typedef struct dfx_reorder_info {
   char kernel_name[96];
 } dfx_reorder_info;
 typedef struct dfx_reorder dfx_reorder_t;
+
+/* ---- channel concat + pointwise conv in one launch: the join of an Inception module, a DenseNet bottleneck, a
+ *      SqueezeNet squeeze layer.  n_inputs NHWC u8 branches {bs,h,w,channels[i]} are read IN PLACE by a 1x1
+ *      stride-1 unpadded conv over their concatenated channels; the concatenated tensor is never written.  The
+ *      result is, bit for bit, dfx_concat_submit of the branches followed by dfx_conv_submit of the unfused
+ *      pointwise conv with the same weights, bias, scales and flags (ReLU on a u8 source is the identity, so
+ *      the reference's concat(..., post_relu) + conv() pair is covered as well).  Parity unpinned: the
+ *      reference ships the two ops only. ---- */
+typedef struct dfx_catconv_desc {
+  int32_t n_inputs;            /* 2 .. 16 */
+  int32_t bs, h, w;            /* shared by all branches and dst; 1x1 window, stride 1, no padding */
+  int32_t oc;
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t bia_dt;              /* DFX_UNDEF = none */
+  int32_t relu, round_mode;
+  int32_t nscales;             /* 1 or oc */
+  int32_t force_path;          /* -1 auto, else DFX_CATCONV_* (testing) */
+  const int32_t *channels;     /* n_inputs entries, each % 16 == 0; ic = their sum */
+} dfx_catconv_desc;
+enum {  /* dfx_catconv_info.path */
+  DFX_CATCONV_FUSED = 0,       /* one launch (catconv_pw.cuh).  Covers: every branch a multiple of 32 channels, ic a
+                                  multiple of 256, oc in {64, 128, 256}, oc * ic <= 96 KB, bs*h*w * (widest branch)
+                                  < 2^31 */
+  DFX_CATCONV_TWO_LAUNCH = 1   /* everything else: concat into a buffer the handle owns, then the unfused conv, both
+                                  on the caller's stream */
+};
+typedef struct dfx_catconv_info {
+  int32_t path;
+  int32_t grid, block, lds_bytes;  /* of the fused kernel / of the conv kernel of the two-launch path */
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2*MAC of one submit */
+  uint64_t algorithmic_bytes;  /* branches + weights + dst; two-launch path: + 2 x the concatenated tensor */
+  char kernel_name[96];        /* two-launch path: the conv kernel's */
+} dfx_catconv_info;
+typedef struct dfx_catconv dfx_catconv_t;
 typedef void *dfx_stream_t; /* a hipStream_t; NULL = the default stream */
 typedef void *dfx_event_t;  /* a hipEvent_t */
 
@@ -280,6 +315,30 @@ int dfx_reorder_submit(dfx_reorder_t *h, const void *src_dev, void *dst_dev, dfx
 int dfx_reorder_submit_host(dfx_reorder_t *h, const void *src_host, void *dst_host); /* synchronous */
 int dfx_reorder_query(const dfx_reorder_t *h, dfx_reorder_info *info);
 int dfx_reorder_destroy(dfx_reorder_t *h);
+
+/* ---- concat + pointwise conv (dfx_catconv_desc above).  The descriptor is validated before anything touches a
+ *      device: DFX_ERR_INVALID for a non-positive size, n_inputs outside 2..16, a branch that is not a multiple
+ *      of 16 channels, a bad dtype / round mode / nscales, and whatever dfx_conv_create rejects for the
+ *      equivalent pointwise conv; DFX_ERR_UNSUPPORTED only for force_path = DFX_CATCONV_FUSED on a shape outside
+ *      the fused class.  On auto everything outside that class takes the two-launch path, so the op is total.
+ *      set_weights: host pointers, copied; wei_blocked is {oc, ic, 1, 1} OIhw4i16o4i over the CONCATENATED ic;
+ *      it may be called again (not while a submit of the handle is in flight).  submit: asynchronous on `s`;
+ *      every branch pointer and dst must be non-null and 16-byte aligned (DFX_ERR_INVALID otherwise, nothing is
+ *      launched); branches may alias each other; DFX_ERR_STATE before set_weights.  A handle may be submitted
+ *      from several host threads and on several streams at once.  Fused path: every launch has its own copy of
+ *      the arguments, launches are independent.  Two-launch path: the handle owns ONE buffer for the
+ *      concatenated tensor, so its submits are SERIALISED, as the conv handle's slot ring serialises the 17th
+ *      launch: submits on one stream are ordered by the stream; once the handle has seen a second stream, every
+ *      submit records an event behind its conv and a submit on a stream other than the previous one's first
+ *      waits, on the device, for that event (the submits made while there was one stream only are covered by
+ *      one event recorded on it when the second stream appears).  The host never blocks.  A stream made
+ *      elsewhere than dfx_stream_create must outlive the handles submitted on it, as for dfx_conv_submit. ---- */
+int dfx_catconv_create(const dfx_catconv_desc *desc, dfx_catconv_t **out);
+int dfx_catconv_set_weights(dfx_catconv_t *h, const int8_t *wei_blocked, const void *bia, const float *scales);
+int dfx_catconv_submit(dfx_catconv_t *h, const void *const *srcs_dev, void *dst_dev, dfx_stream_t s);
+int dfx_catconv_submit_host(dfx_catconv_t *h, const void *const *srcs_host, void *dst_host); /* synchronous */
+int dfx_catconv_query(const dfx_catconv_t *h, dfx_catconv_info *info);
+int dfx_catconv_destroy(dfx_catconv_t *h);
 
 /* ---- test hooks (not part of the reference's surface; used by tests/ only) ---- */
 /* Overwrites the LDS of every CU with a pattern (asynchronous, on `s`): makes a kernel that

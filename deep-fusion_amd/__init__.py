@@ -14,6 +14,7 @@ from .capi import (  # noqa: F401
     DFX_F32, DFX_S32, DFX_S8, DFX_U8, DFX_UNDEF, ROUND_NEAREST, ROUND_DOWN,
     VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM, DfxError, ConvDesc, ConvInfo, ConvSched, Conv, Concat, Pool, EltwiseSum,
     FMT_NHWC, FMT_NCHW, REORDER_FLAT, REORDER_GENERIC, REORDER_SMALLC, REORDER_TRANSPOSE, ReorderDesc, ReorderInfo, Reorder,
+    ROUTE_EXACT, ROUTE_FAST, ROUTE_MAGIC, ROUTE_FMA,
     CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH, CatConvDesc, CatConvInfo, ConcatConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

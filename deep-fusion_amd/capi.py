@@ -81,6 +81,9 @@ class CatConvInfo(ctypes.Structure):
                 ("kernel_name", ctypes.c_char * 96)]
 
 
+# route numbering of dfx_debug_conv_requant (include/dfx.h)
+ROUTE_EXACT, ROUTE_FAST, ROUTE_MAGIC, ROUTE_FMA = 0, 1, 2, 3
+
 # order of dfx_debug_conv_sched (include/dfx.h)
 ConvSched = collections.namedtuple("ConvSched", "th tw linear uy ux total_units half_from static_rounds lazy_queue "
                                                 "pool teams roles ring_waits")
@@ -180,6 +183,8 @@ def lib():
         "dfx_debug_scribble_lds": (i32, [ctypes.c_uint, vp]),
         "dfx_debug_set_tuning": (i32, [ctypes.c_char_p, ctypes.c_char_p]),
         "dfx_debug_conv_sched": (i32, [vp, ctypes.POINTER(ctypes.c_int32), i32]),
+        "dfx_debug_conv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_debug_catconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -287,6 +292,13 @@ class Conv:
         v = (ctypes.c_int32 * len(ConvSched._fields))()
         _check(lib().dfx_debug_conv_sched(self._h, v, len(v)))
         return ConvSched(*v)
+
+    def requant(self):
+        """requant route of stage 0 and stage 1 as set_weights proved it (dfx_debug_conv_requant): a tuple of
+        ROUTE_EXACT / ROUTE_FAST / ROUTE_MAGIC / ROUTE_FMA, -1 for a stage the op does not have; launches nothing."""
+        v = (ctypes.c_int32 * 2)()
+        _check(lib().dfx_debug_conv_requant(self._h, v))
+        return (v[0], v[1])
 
     def close(self):
         if self._h:
@@ -439,6 +451,12 @@ class ConcatConv:
         i = CatConvInfo()
         _check(lib().dfx_catconv_query(self._h, ctypes.byref(i)))
         return i
+
+    def requant(self):
+        """requant route of the inner pointwise conv (dfx_debug_catconv_requant), as Conv.requant()"""
+        v = (ctypes.c_int32 * 2)()
+        _check(lib().dfx_debug_catconv_requant(self._h, v))
+        return (v[0], v[1])
 
     def close(self):
         if self._h:

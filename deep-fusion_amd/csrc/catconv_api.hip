@@ -312,6 +312,12 @@ int dfx_catconv_query(const dfx_catconv_t *h, dfx_catconv_info *info) {
   return DFX_OK;
 }
 
+// test hook: the requant route of the inner conv handle -- the fused kernel reads the same proofs (conv_pw_view)
+int dfx_debug_catconv_requant(const dfx_catconv_t *h, int32_t out[2]) {
+  if (!h || !out) return fail(DFX_ERR_INVALID, "catconv_requant: null argument");
+  return dfx_debug_conv_requant(h->conv, out);
+}
+
 int dfx_catconv_destroy(dfx_catconv_t *h) {
   release(h);
   return DFX_OK;

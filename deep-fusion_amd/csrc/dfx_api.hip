@@ -1784,6 +1784,29 @@ int dfx_debug_conv_sched(const dfx_conv_t *h, int32_t *out, int n) {
   return DFX_OK;
 }
 
+// test hook: the requant route dfx_conv_set_weights proved for each stage, in ONE numbering for every kernel family
+// (include/dfx.h): 0 exact, 1 fast, 2 magic, 3 fma, -1 no such stage.  Launches nothing.
+int dfx_debug_conv_requant(const dfx_conv_t *h, int32_t out[2]) {
+  if (!h || !out) return fail(DFX_ERR_INVALID, "conv_requant: null argument");
+  if (!h->weights_set) return fail(DFX_ERR_STATE, "conv_requant: dfx_conv_set_weights not called");
+  const bool fused = h->d.oc1x1 > 0;
+  if (h->variant == DFX_VARIANT_MFMA_STREAM && h->direct) {  // conv_direct.cuh, conv_pw.cuh (and catconv_pw.cuh through conv_pw_view)
+    const DirectGeom &g = h->dgeom;
+    out[0] = g.m0 ? 3 : g.fast ? 1 : 0;
+    out[1] = !fused ? -1 : g.m1 ? g.m1 : g.fast ? 1 : 0;
+  } else if (h->variant == DFX_VARIANT_MFMA_STREAM) {  // conv_stream.cuh: one switch for both stages
+    out[0] = h->sgeom.fast ? 1 : 0;
+    out[1] = fused ? out[0] : -1;
+  } else if (h->variant != DFX_VARIANT_GENERIC) {  // conv_mfma.cuh, conv_mfma_roles.cuh
+    out[0] = h->geom.mode0;
+    out[1] = fused ? h->geom.mode1 : -1;
+  } else {  // the scalar kernel follows the reference's arithmetic step by step
+    out[0] = 0;
+    out[1] = fused ? 0 : -1;
+  }
+  return DFX_OK;
+}
+
 #ifdef DK_DEBUG
 // bounds-checking diagnostic build of conv_direct.cuh: 32 x {offset, size} of the first violation per tag (-1 = none)
 int dfx_debug_read_bounds(dfx_conv_t *h, long long *out) {

@@ -364,6 +364,18 @@ int dfx_debug_set_tuning(const char *key, const char *value);
  *   12 ring_waits      stream waits the queue-ring guard of dfx_conv_submit has issued on this handle so far
  * DFX_ERR_UNSUPPORTED for an op without a unit queue (any other kernel). */
 int dfx_debug_conv_sched(const dfx_conv_t *h, int32_t *out, int n);
+/* Read-only: the requant route dfx_conv_set_weights proved for stage 0 (out[0]) and stage 1 (out[1]) from the
+ * actual weights, bias and scales; launches nothing.  One numbering for every kernel family:
+ *    0 exact   the reference's arithmetic step by step (x86 conversion semantics emulated)
+ *    1 fast    hardware conversions, nearest-even, nothing near +-2^31
+ *    2 magic   accumulator started from a float bit pattern, v_add_f32 + v_mul_f32
+ *    3 fma     accumulator started from a float bit pattern, one v_fma_f32
+ *   -1         the op has no such stage (out[1] of an unfused op)
+ * Resident-weight kernels report their mode0 / mode1, the streamed kernel its one `fast` switch for both stages,
+ * the direct-weight and pointwise kernels fast / m0 / m1, the scalar kernel 0.  dfx_debug_catconv_requant forwards
+ * to the op's inner conv handle, whose proofs the fused kernel reads too.  DFX_ERR_STATE before set_weights. */
+int dfx_debug_conv_requant(const dfx_conv_t *h, int32_t out[2]);
+int dfx_debug_catconv_requant(const dfx_catconv_t *h, int32_t out[2]);
 
 #ifdef __cplusplus
 }

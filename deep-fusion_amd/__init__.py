@@ -16,5 +16,6 @@ from .capi import (  # noqa: F401
     FMT_NHWC, FMT_NCHW, REORDER_FLAT, REORDER_GENERIC, REORDER_SMALLC, REORDER_TRANSPOSE, ReorderDesc, ReorderInfo, Reorder,
     ROUTE_EXACT, ROUTE_FAST, ROUTE_MAGIC, ROUTE_FMA,
     CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH, CatConvDesc, CatConvInfo, ConcatConv,
+    DWCONV_AUTO, DWCONV_WINDOW, DWCONV_GENERIC, DwConvDesc, DwConvInfo, DwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

@@ -17,6 +17,7 @@ ROUND_NEAREST, ROUND_DOWN = 0, 1
 FMT_NHWC, FMT_NCHW = 0, 1
 REORDER_FLAT, REORDER_GENERIC, REORDER_SMALLC, REORDER_TRANSPOSE = 0, 1, 2, 3
 CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH = -1, 0, 1
+DWCONV_AUTO, DWCONV_WINDOW, DWCONV_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -76,6 +77,17 @@ class CatConvDesc(ctypes.Structure):
 
 
 class CatConvInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
+class DwConvDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t", "pad_l",
+                                             "dst_dt", "bia_dt", "relu", "round_mode", "nscales", "force_path")]
+
+
+class DwConvInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
@@ -180,11 +192,18 @@ def lib():
         "dfx_catconv_submit_host": (i32, [vp, ctypes.POINTER(vp), vp]),
         "dfx_catconv_query": (i32, [vp, ctypes.POINTER(CatConvInfo)]),
         "dfx_catconv_destroy": (i32, [vp]),
+        "dfx_dwconv_create": (i32, [ctypes.POINTER(DwConvDesc), ctypes.POINTER(vp)]),
+        "dfx_dwconv_set_weights": (i32, [vp, vp, vp, vp]),
+        "dfx_dwconv_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_dwconv_submit_host": (i32, [vp, vp, vp]),
+        "dfx_dwconv_query": (i32, [vp, ctypes.POINTER(DwConvInfo)]),
+        "dfx_dwconv_destroy": (i32, [vp]),
         "dfx_debug_scribble_lds": (i32, [ctypes.c_uint, vp]),
         "dfx_debug_set_tuning": (i32, [ctypes.c_char_p, ctypes.c_char_p]),
         "dfx_debug_conv_sched": (i32, [vp, ctypes.POINTER(ctypes.c_int32), i32]),
         "dfx_debug_conv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_catconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_debug_dwconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -461,6 +480,68 @@ class ConcatConv:
     def close(self):
         if self._h:
             lib().dfx_catconv_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DwConv:
+    """dfx_dwconv_* handle: depthwise int8 conv over NHWC u8 (include/dfx.h).  For c a multiple of 16 the result equals
+    the unfused Conv with ic = oc = c and block-diagonal weights bit for bit.  out_hw defaults to the conv's
+    (in + 2 * pad - k) // stride + 1; give it for windows that hang over the bottom / right edge."""
+
+    def __init__(self, src_shape_nhwc, kernel, stride=(1, 1), pad=(1, 1), out_hw=None, dst_dt=DFX_U8, bia_dt=DFX_UNDEF,
+                 relu=False, rm=ROUND_NEAREST, nscales=1, force_path=DWCONV_AUTO):
+        bs, ih, iw, c = src_shape_nhwc
+        kh, kw = kernel
+        if out_hw is None:
+            out_hw = ((ih + 2 * pad[0] - kh) // stride[0] + 1, (iw + 2 * pad[1] - kw) // stride[1] + 1)
+        d = DwConvDesc(bs, c, ih, iw, out_hw[0], out_hw[1], kh, kw, stride[0], stride[1], pad[0], pad[1], dst_dt, bia_dt,
+                       int(relu), rm, nscales, force_path)
+        self.desc = d
+        self.src_shape = (bs, ih, iw, c)
+        self.dst_shape = (bs, out_hw[0], out_hw[1], c)
+        self.dst_np_dtype = _NP.get(dst_dt)
+        self._h = ctypes.c_void_p()
+        _check(lib().dfx_dwconv_create(ctypes.byref(d), ctypes.byref(self._h)))
+
+    def set_weights(self, wei, scales, bia=None):
+        """wei: int8 {c, kh, kw}; scales: 1 or c floats; bia: c entries of the descriptor's bias dtype"""
+        ws = [np.ascontiguousarray(wei, dtype=np.int8), None if bia is None else np.ascontiguousarray(bia),
+              np.ascontiguousarray(scales, dtype=np.float32)]
+        assert ws[0].size == self.desc.c * self.desc.kh * self.desc.kw, ws[0].shape
+        assert ws[2].size == self.desc.nscales and (bia is None or ws[1].size == self.desc.c)
+        _check(lib().dfx_dwconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+    def submit(self, src_dev, dst_dev, stream=None):
+        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers), 16-byte aligned"""
+        _check(lib().dfx_dwconv_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
+
+    def submit_host(self, src_np):
+        src = np.ascontiguousarray(src_np, dtype=np.uint8)
+        assert src.shape == self.src_shape, (src.shape, self.src_shape)
+        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
+        _check(lib().dfx_dwconv_submit_host(self._h, _p(src), _p(dst)))
+        return dst
+
+    def info(self):
+        i = DwConvInfo()
+        _check(lib().dfx_dwconv_query(self._h, ctypes.byref(i)))
+        return i
+
+    def requant(self):
+        """requant route as set_weights proved it (dfx_debug_dwconv_requant): ROUTE_EXACT or ROUTE_FAST"""
+        v = (ctypes.c_int32 * 1)()
+        _check(lib().dfx_debug_dwconv_requant(self._h, v))
+        return v[0]
+
+    def close(self):
+        if self._h:
+            lib().dfx_dwconv_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -1,5 +1,5 @@
 // dfx_internal.h -- the few host-side helpers the translation units behind include/dfx.h share
-// (dfx_api.hip, reorder_api.hip, catconv_api.hip).  Not installed, not part of the C ABI.
+// (dfx_api.hip, reorder_api.hip, catconv_api.hip, dwconv_api.hip).  Not installed, not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,6 +23,9 @@ __attribute__((visibility("hidden"))) bool conv_pw_view(const dfx_conv *h, ConvA
 // serial number of a live stream of dfx_stream_create's (never reused), 0 for any other stream: how a handle that
 // remembers a stream finds out that dfx_stream_destroy has destroyed it since (defined in dfx_api.hip)
 __attribute__((visibility("hidden"))) unsigned long long stream_serial_of(hipStream_t st);
+
+// value of a testing / tuning switch or nullptr; use it at once (defined in dfx_api.hip)
+__attribute__((visibility("hidden"))) const char *tuning_value(const char *key);
 
 inline size_t dt_size(int dt) { return (dt == DFX_F32 || dt == DFX_S32) ? 4 : 1; }
 

@@ -237,6 +237,24 @@ std::unique_ptr<op> concat_conv(const std::vector<std::unique_ptr<memory>> &srcs
                                 bool relu = false, std::vector<float> scales = {1.f},
                                 round_mode rm = round_mode::nearest);
 
+// ---- extension: depthwise conv (dfx_dwconv_* in dfx.h): every channel is convolved with its own window -- the other
+// half of a MobileNet / EfficientNet / Xception block (the reference asserts ngroups == 1).  src: nhwc u8; wei: plain
+// oihw s8 of dims {c, 1, kh, kw}; bia: format x, c entries, or null; dst: nhwc u8 / s8 / s32 / f32 with src's batch and
+// channels -- ITS height and width are the output size, so windows may hang over the bottom / right edge (TF "SAME"
+// padding of a stride-2 layer with padding {0, 0}); padding is {top, left}.  Arithmetic, scales, ReLU and rounding are
+// conv()'s: for c a multiple of 16 dst holds, bit for bit, what conv() gives with block-diagonal weights.  3x3 / 5x5
+// windows with stride 1 / 2 and c % 16 == 0 run on the sliding-window kernel, everything else on a generic one.
+// submit / submit_async / wait behave like conv's; borrowed weights are hashed and re-packed like conv's; under
+// DEEPFUSION_DEVICES the batch is sharded as concat_conv() shards it. ----
+std::unique_ptr<op> depthwise_conv(const std::unique_ptr<memory> &src,
+                                   const std::unique_ptr<memory> &wei,
+                                   const std::unique_ptr<memory> &bia,
+                                   std::array<int, 2> sz_stride,
+                                   std::array<int, 2> sz_padding,
+                                   std::unique_ptr<memory> &dst,
+                                   bool relu = false, std::vector<float> scales = {1.f},
+                                   round_mode rm = round_mode::nearest);
+
 // ---- extension: the weight reorder the reference never shipped (deepfusion.cc:44-50) ----
 // Writes plain oihw s8 weights into `blocked` (an OIhw4i16o4i memory of the same
 // logical dims) in the [O/16][I/16][kh][kw][4i][16o][4i] byte order.

@@ -210,6 +210,45 @@ typedef struct dfx_catconv_info {
   char kernel_name[96];        /* two-launch path: the conv kernel's */
 } dfx_catconv_info;
 typedef struct dfx_catconv dfx_catconv_t;
+
+/* ---- depthwise int8 conv: every channel is convolved with its own kh x kw window (groups = channels, no channel
+ *      multiplier, no dilation): the other half of a MobileNet / EfficientNet / Xception block.  src NHWC u8
+ *      {bs,ih,iw,c}; weights s8 {c,kh,kw} plain row-major (goihw with o = i = 1); dst NHWC {bs,oh,ow,c}.
+ *        acc[n,oy,ox,k] = sum over ky,kx of src[n, oy*sh - pad_t + ky, ox*sw - pad_l + kx, k] * w[k,ky,kx]
+ *                         (taps outside the input are skipped)
+ *        f = float(acc);  f = f + bias[k] (if any);  f = f * scale[k or 0];  ReLU (asked for, or dst is u8):
+ *        f = (0 > f) ? 0 : f;  dst = store(f, dst_dt, round_mode)
+ *      with the conv's arithmetic: separately rounded add and multiply, the bias converted like the conv's, the x86
+ *      conversion (NaN / out of range -> 0x80000000 -> u8 255, s8 -128).  For c a multiple of 16 the result is, bit
+ *      for bit, the unfused dfx_conv with ic = oc = c and W[o][i][ky][kx] = (o == i) ? w[o][ky][kx] : 0.  oh and ow
+ *      are given by the caller as in dfx_pool_desc: windows may hang over the bottom / right edge (TF "SAME" padding
+ *      of a stride-2 layer with pad_t = pad_l = 0).  Parity unpinned: the reference asserts ngroups == 1. ---- */
+typedef struct dfx_dwconv_desc {
+  int32_t bs, c, ih, iw;
+  int32_t oh, ow;              /* (oh - 1) * sh - pad_t <= ih - 1, likewise in x */
+  int32_t kh, kw;              /* 1 .. 255 */
+  int32_t sh, sw;
+  int32_t pad_t, pad_l;
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t bia_dt;              /* DFX_UNDEF = none */
+  int32_t relu, round_mode;
+  int32_t nscales;             /* 1 or c */
+  int32_t force_path;          /* -1 auto, else DFX_DWCONV_* (testing) */
+} dfx_dwconv_desc;
+enum {  /* dfx_dwconv_info.path */
+  DFX_DWCONV_WINDOW = 0,       /* the sliding-window kernel (dwconv.cuh).  Covers: 3x3 or 5x5, stride (1,1) or (2,2),
+                                  c a multiple of 16, one image below 2^31 bytes on either side */
+  DFX_DWCONV_GENERIC = 1       /* everything else: one thread per output element, any window / stride / channel count */
+};
+typedef struct dfx_dwconv_info {
+  int32_t path;
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2*MAC of one submit */
+  uint64_t algorithmic_bytes;  /* src + weights + dst */
+  char kernel_name[96];        /* path, window, stride and requant route (valid after set_weights) */
+} dfx_dwconv_info;
+typedef struct dfx_dwconv dfx_dwconv_t;
 typedef void *dfx_stream_t; /* a hipStream_t; NULL = the default stream */
 typedef void *dfx_event_t;  /* a hipEvent_t */
 
@@ -340,6 +379,26 @@ int dfx_catconv_submit_host(dfx_catconv_t *h, const void *const *srcs_host, void
 int dfx_catconv_query(const dfx_catconv_t *h, dfx_catconv_info *info);
 int dfx_catconv_destroy(dfx_catconv_t *h);
 
+/* ---- depthwise conv (dfx_dwconv_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for a non-positive size or stride, a negative padding, a window beyond 255 x 255 (the
+ *      accumulator then cannot leave s32), an output row / column whose window starts below / right of the input,
+ *      a bad dtype / round mode / nscales / force_path, a tensor of 2^31 pixels or more; DFX_ERR_UNSUPPORTED only for
+ *      force_path = DFX_DWCONV_WINDOW on a shape outside that class.  On auto everything outside it takes the generic
+ *      path, so the op is total.  set_weights: host pointers, copied; wei is s8 {c,kh,kw}; bia has c entries of
+ *      bia_dt (NULL when DFX_UNDEF); it may be called again (not while a submit of the handle is in flight) and
+ *      chooses the requant route from the actual numbers: "fast" (hardware conversions) when, for every channel,
+ *      bias and scale are finite and (255 * max(P, N) + |bias|) * |scale| <= 2^30 (P, N: sums of the channel's
+ *      positive / negative weights' magnitudes), the round mode is nearest and DFX_NO_FAST is not set; else "exact".
+ *      submit: asynchronous on `s`; src and dst must be non-null and 16-byte aligned (DFX_ERR_INVALID otherwise,
+ *      nothing is launched); DFX_ERR_STATE before set_weights.  Every launch has its own copy of the arguments: one
+ *      handle serves several streams and host threads at once.  No CPU fallback. ---- */
+int dfx_dwconv_create(const dfx_dwconv_desc *desc, dfx_dwconv_t **out);
+int dfx_dwconv_set_weights(dfx_dwconv_t *h, const int8_t *wei, const void *bia, const float *scales);
+int dfx_dwconv_submit(dfx_dwconv_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_dwconv_submit_host(dfx_dwconv_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_dwconv_query(const dfx_dwconv_t *h, dfx_dwconv_info *info);
+int dfx_dwconv_destroy(dfx_dwconv_t *h);
+
 /* ---- test hooks (not part of the reference's surface; used by tests/ only) ---- */
 /* Overwrites the LDS of every CU with a pattern (asynchronous, on `s`): makes a kernel that
  * reads LDS before publishing it fail deterministically (tests/test_gpu_first_launch.py). */
@@ -376,6 +435,8 @@ int dfx_debug_conv_sched(const dfx_conv_t *h, int32_t *out, int n);
  * to the op's inner conv handle, whose proofs the fused kernel reads too.  DFX_ERR_STATE before set_weights. */
 int dfx_debug_conv_requant(const dfx_conv_t *h, int32_t out[2]);
 int dfx_debug_catconv_requant(const dfx_catconv_t *h, int32_t out[2]);
+/* the depthwise conv's one stage, same numbering (0 exact, 1 fast) */
+int dfx_debug_dwconv_requant(const dfx_dwconv_t *h, int32_t out[1]);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,7 @@ FMT_NHWC, FMT_NCHW = 0, 1
 REORDER_FLAT, REORDER_GENERIC, REORDER_SMALLC, REORDER_TRANSPOSE = 0, 1, 2, 3
 CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH = -1, 0, 1
 DWCONV_AUTO, DWCONV_WINDOW, DWCONV_GENERIC = -1, 0, 1
+DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -88,6 +89,18 @@ class DwConvDesc(ctypes.Structure):
 
 
 class DwConvInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
+class DwPwDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t", "pad_l",
+                                             "oc", "dst_dt", "bia0_dt", "bia1_dt", "relu", "round_mode0", "round_mode1",
+                                             "nscales0", "nscales1", "force_path")]
+
+
+class DwPwInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
@@ -198,12 +211,19 @@ def lib():
         "dfx_dwconv_submit_host": (i32, [vp, vp, vp]),
         "dfx_dwconv_query": (i32, [vp, ctypes.POINTER(DwConvInfo)]),
         "dfx_dwconv_destroy": (i32, [vp]),
+        "dfx_dwpw_create": (i32, [ctypes.POINTER(DwPwDesc), ctypes.POINTER(vp)]),
+        "dfx_dwpw_set_weights": (i32, [vp] * 7),
+        "dfx_dwpw_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_dwpw_submit_host": (i32, [vp, vp, vp]),
+        "dfx_dwpw_query": (i32, [vp, ctypes.POINTER(DwPwInfo)]),
+        "dfx_dwpw_destroy": (i32, [vp]),
         "dfx_debug_scribble_lds": (i32, [ctypes.c_uint, vp]),
         "dfx_debug_set_tuning": (i32, [ctypes.c_char_p, ctypes.c_char_p]),
         "dfx_debug_conv_sched": (i32, [vp, ctypes.POINTER(ctypes.c_int32), i32]),
         "dfx_debug_conv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_catconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_debug_dwpw_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -542,6 +562,71 @@ class DwConv:
     def close(self):
         if self._h:
             lib().dfx_dwconv_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DwPwConv:
+    """dfx_dwpw_* handle: depthwise conv (dst u8) + pointwise 1x1 conv over NHWC u8, the tensor between the two kept on
+    chip on the fused path (include/dfx.h).  The result equals DwConv (u8) followed by the unfused 1x1 Conv bit for bit.
+    out_hw defaults to the conv's (in + 2 * pad - k) // stride + 1."""
+
+    def __init__(self, src_shape_nhwc, kernel, oc, stride=(1, 1), pad=(1, 1), out_hw=None, dst_dt=DFX_U8, bia0_dt=DFX_UNDEF,
+                 bia1_dt=DFX_UNDEF, relu=False, rm0=ROUND_NEAREST, rm1=ROUND_NEAREST, nscales0=1, nscales1=1,
+                 force_path=DWPW_AUTO):
+        bs, ih, iw, c = src_shape_nhwc
+        kh, kw = kernel
+        if out_hw is None:
+            out_hw = ((ih + 2 * pad[0] - kh) // stride[0] + 1, (iw + 2 * pad[1] - kw) // stride[1] + 1)
+        d = DwPwDesc(bs, c, ih, iw, out_hw[0], out_hw[1], kh, kw, stride[0], stride[1], pad[0], pad[1], oc, dst_dt,
+                     bia0_dt, bia1_dt, int(relu), rm0, rm1, nscales0, nscales1, force_path)
+        self.desc = d
+        self.src_shape = (bs, ih, iw, c)
+        self.dst_shape = (bs, out_hw[0], out_hw[1], oc)
+        self.dst_np_dtype = _NP.get(dst_dt)
+        self._h = ctypes.c_void_p()
+        _check(lib().dfx_dwpw_create(ctypes.byref(d), ctypes.byref(self._h)))
+
+    def set_weights(self, wei_dw, scales0, wei_pw_blk, scales1, bia0=None, bia1=None):
+        """wei_dw: int8 {c, kh, kw}; wei_pw_blk: {oc, c, 1, 1} in OIhw4i16o4i order (reorder_oihw_to_blocked)"""
+        ws = [np.ascontiguousarray(wei_dw, dtype=np.int8), None if bia0 is None else np.ascontiguousarray(bia0),
+              np.ascontiguousarray(scales0, dtype=np.float32), np.ascontiguousarray(wei_pw_blk, dtype=np.int8),
+              None if bia1 is None else np.ascontiguousarray(bia1), np.ascontiguousarray(scales1, dtype=np.float32)]
+        assert ws[0].size == self.desc.c * self.desc.kh * self.desc.kw, ws[0].shape
+        assert ws[2].size == self.desc.nscales0 and ws[5].size == self.desc.nscales1
+        assert (bia0 is None or ws[1].size == self.desc.c) and (bia1 is None or ws[4].size == self.desc.oc)
+        _check(lib().dfx_dwpw_set_weights(self._h, *[_p(w) for w in ws]))
+
+    def submit(self, src_dev, dst_dev, stream=None):
+        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers), 16-byte aligned"""
+        _check(lib().dfx_dwpw_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
+
+    def submit_host(self, src_np):
+        src = np.ascontiguousarray(src_np, dtype=np.uint8)
+        assert src.shape == self.src_shape, (src.shape, self.src_shape)
+        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
+        _check(lib().dfx_dwpw_submit_host(self._h, _p(src), _p(dst)))
+        return dst
+
+    def info(self):
+        i = DwPwInfo()
+        _check(lib().dfx_dwpw_query(self._h, ctypes.byref(i)))
+        return i
+
+    def requant(self):
+        """requant routes of stage 0 and stage 1 as set_weights proved them (dfx_debug_dwpw_requant)"""
+        v = (ctypes.c_int32 * 2)()
+        _check(lib().dfx_debug_dwpw_requant(self._h, v))
+        return (v[0], v[1])
+
+    def close(self):
+        if self._h:
+            lib().dfx_dwpw_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

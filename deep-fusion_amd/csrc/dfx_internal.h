@@ -20,6 +20,13 @@ struct ConvArgs;
 struct PwGeom;
 __attribute__((visibility("hidden"))) bool conv_pw_view(const dfx_conv *h, ConvArgs *args, PwGeom *geom, int *lds);
 
+// The window kernel's view of a depthwise handle (defined in dwconv_api.hip): its kernel arguments without src / dst
+// (packed weights, compensation, bias, scale) with the requant-route proof of the last dfx_dwconv_set_weights (fast).
+// false when the handle is not on the window path or has no weights yet.  dwpw_api.hip launches its fused kernel on
+// these, so that neither the packing nor the proof exist twice.
+struct DwArgs;
+__attribute__((visibility("hidden"))) bool dwconv_window_view(const dfx_dwconv *h, DwArgs *args);
+
 // serial number of a live stream of dfx_stream_create's (never reused), 0 for any other stream: how a handle that
 // remembers a stream finds out that dfx_stream_destroy has destroyed it since (defined in dfx_api.hip)
 __attribute__((visibility("hidden"))) unsigned long long stream_serial_of(hipStream_t st);

@@ -115,6 +115,12 @@ size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 
+bool dfx::dwconv_window_view(const dfx_dwconv *h, DwArgs *args) {  // (declared in dfx_internal.h)
+  if (!h || h->path != DFX_DWCONV_WINDOW || !h->weights_set) return false;
+  *args = h->args;
+  return true;
+}
+
 extern "C" {
 
 int dfx_dwconv_create(const dfx_dwconv_desc *desc, dfx_dwconv_t **out) {

@@ -1314,6 +1314,184 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- depthwise + pointwise conv (dfx_dwpw_*): depthwise_conv() with a u8 result followed by a 1x1 conv(), behind one
+// handle.  force_path stays -1 (auto), so the path is the library's choice (dfx.h, AUTO RULE at DFX_DWPW_FUSED).  The depthwise weights are a plain oihw
+// {c, 1, kh, kw} tensor, the pointwise weights OIhw4i16o4i {oc, c, 1, 1}; dst's dims give the output size. ----
+class op_depthwise_separable_conv : public op {
+public:
+  op_depthwise_separable_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
+                              std::array<int, 2> stride, std::array<int, 2> padding, const std::unique_ptr<memory> &wei_pw,
+                              const std::unique_ptr<memory> &bia_pw, std::unique_ptr<memory> &dst, bool relu,
+                              const std::vector<float> &scales, const std::vector<float> &scales_pw, round_mode rm,
+                              round_mode rm_pw)
+      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), wei_pw_(wei_pw.get()), bia_pw_(bia_pw.get()), dst_(dst.get()),
+        scales_(scales), scales_pw_(scales_pw), h_(nullptr), packed_hash_(0), packed_versions_(0) {
+    using fmt = memory::format;
+    if (!src_ || !wei_ || !wei_pw_ || !dst_) error_and_exit("Init DepthwiseSeparableConv op failed! (null tensor)");
+    if (src_->data_type() != memory::dtype::u8 || wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc ||
+        dst_->dim_format() != fmt::nhwc || wei_->dim_format() != fmt::oihw || (bia_ && bia_->dim_format() != fmt::x) ||
+        wei_pw_->data_type() != memory::dtype::s8 || wei_pw_->dim_format() != fmt::OIhw4i16o4i ||
+        (bia_pw_ && bia_pw_->dim_format() != fmt::x))
+      error_and_exit("Init DepthwiseSeparableConv op failed! (data type / format)");
+    auto i = src_->std_dims(), w = wei_->std_dims(), o = dst_->std_dims(), p = wei_pw_->std_dims();
+    if (i[0] != o[0]) error_and_exit("Init DepthwiseSeparableConv op failed! (Batch size do not equal)");
+    if (w[0] != i[1] || w[1] != 1) error_and_exit("Init DepthwiseSeparableConv op failed! (weights must be {c, 1, kh, kw})");
+    if (p[1] != i[1] || p[2] != 1 || p[3] != 1) error_and_exit("Init DepthwiseSeparableConv op failed! (pointwise weights must be {oc, c, 1, 1})");
+    if (o[1] != p[0]) error_and_exit("Init DepthwiseSeparableConv op failed! (Output channel do not match)");
+    if (bia_pw_ && (int)bia_pw_->size() != p[0]) error_and_exit("Init DepthwiseSeparableConv op failed! (Bias channel do not match)");
+    if (bia_ && (int)bia_->size() != i[1]) error_and_exit("Init DepthwiseSeparableConv op failed! (Bias channel do not match)");
+    dfx_dwpw_desc d;
+    memset(&d, 0, sizeof(d));
+    d.bs = i[0]; d.c = i[1]; d.ih = i[2]; d.iw = i[3]; d.oh = o[2]; d.ow = o[3];
+    d.kh = w[2]; d.kw = w[3]; d.sh = stride[0]; d.sw = stride[1]; d.pad_t = padding[0]; d.pad_l = padding[1];
+    d.oc = p[0];
+    d.dst_dt = to_dfx_dtype(dst_->data_type());
+    d.bia0_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
+    d.bia1_dt = bia_pw_ ? to_dfx_dtype(bia_pw_->data_type()) : DFX_UNDEF;
+    d.relu = relu;
+    d.round_mode0 = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode1 = rm_pw == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.nscales0 = (int)scales_.size();
+    d.nscales1 = (int)scales_pw_.size();
+    d.force_path = -1;
+    src_img_ = (size_t)d.ih * d.iw * d.c;
+    dst_img_ = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
+    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
+      shard sh;
+      sh.r = r;
+      dfx_dwpw_desc ds = d;
+      ds.bs = r.n;
+      check_dfx(dfx_set_device(r.device), "set device");
+      if (dfx_dwpw_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init DepthwiseSeparableConv op failed! (%s)", dfx_last_error());
+      check_dfx(dfx_stream_create(&sh.stream), "stream create");
+      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
+      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
+      shards_.push_back(sh);
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    if (dfx_dwpw_create(&d, &h_) != DFX_OK) error_and_exit("Init DepthwiseSeparableConv op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_depthwise_separable_conv() override {
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      dfx_dwpw_destroy(sh.h);
+      dfx_stream_destroy(sh.stream);
+      dfx_mem_free_device(sh.src);
+      dfx_mem_free_device(sh.dst);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire(*dst_);
+    dfx_dwpw_destroy(h_);
+  }
+
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  void submit_async() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(false);
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled(*dst_);
+    }
+  }
+
+protected:
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  unsigned long long weights_hash() {
+    using detail::hash_bytes;
+    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
+    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
+    v = hash_bytes(wei_pw_->host_data(), wei_pw_->buffer_size(), v);
+    if (bia_pw_) v = hash_bytes(bia_pw_->host_data(), bia_pw_->buffer_size(), v);
+    return v | 1ull;
+  }
+  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0) + wei_pw_->host_version() + (bia_pw_ ? bia_pw_->host_version() : 0);
+  }
+  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
+    const unsigned long long v = weights_hash();
+    const char *hs = static_cast<const char *>(src_->host_data());
+    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      if (v != sh.wei_seen) {
+        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+        check_dfx(dfx_dwpw_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data(),
+                                       (const int8_t *)wei_pw_->host_data(), bia_pw_ ? bia_pw_->host_data() : nullptr, scales_pw_.data()),
+                  "depthwise_separable_conv set_weights");
+        sh.wei_seen = v;
+      }
+      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
+      check_dfx(dfx_dwpw_submit(sh.h, sh.src, sh.dst, sh.stream), "depthwise_separable_conv submit");
+      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    detail::op_state::host_is_current(*dst_);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
+    const unsigned long long vers = weights_versions();
+    if (sync_host || vers != packed_versions_) {
+      const unsigned long long hash = weights_hash();
+      if (hash != packed_hash_) {
+        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
+        check_dfx(dfx_dwpw_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data(),
+                                       (const int8_t *)wei_pw_->host_data(), bia_pw_ ? bia_pw_->host_data() : nullptr, scales_pw_.data()),
+                  "depthwise_separable_conv set_weights");
+        packed_hash_ = hash;
+      }
+      packed_versions_ = vers;
+    }
+    const void *in = st_.sync_in(*src_, sync_host);
+    void *o = st_.device_out(*dst_);
+    st_.profile_begin();
+    check_dfx(dfx_dwpw_submit(h_, in, o, st_.stream), "depthwise_separable_conv submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "depthwise_separable_conv"; }
+
+private:
+  struct shard {
+    detail::shard_range r;
+    dfx_dwpw_t *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    void *src = nullptr, *dst = nullptr;
+    unsigned long long wei_seen = 0;
+  };
+  memory *src_, *wei_, *bia_, *wei_pw_, *bia_pw_, *dst_;
+  std::vector<float> scales_, scales_pw_;
+  dfx_dwpw_t *h_;
+  unsigned long long packed_hash_, packed_versions_;
+  size_t src_img_, dst_img_;  // bytes per image
+  detail::op_state st_;
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
+};
+
 }  // namespace
 
 std::unique_ptr<op> depthwise_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei,
@@ -1321,6 +1499,16 @@ std::unique_ptr<op> depthwise_conv(const std::unique_ptr<memory> &src, const std
                                    std::array<int, 2> sz_padding, std::unique_ptr<memory> &dst, bool relu,
                                    std::vector<float> scales, round_mode rm) {
   return std::unique_ptr<op>(new op_depthwise_conv(src, wei, bia, sz_stride, sz_padding, dst, relu, scales, rm));
+}
+
+std::unique_ptr<op> depthwise_separable_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei_dw,
+                                             const std::unique_ptr<memory> &bia_dw, std::array<int, 2> sz_stride,
+                                             std::array<int, 2> sz_padding, const std::unique_ptr<memory> &wei_pw,
+                                             const std::unique_ptr<memory> &bia_pw, std::unique_ptr<memory> &dst, bool relu,
+                                             std::vector<float> scales_dw, std::vector<float> scales_pw, round_mode rm_dw,
+                                             round_mode rm_pw) {
+  return std::unique_ptr<op>(new op_depthwise_separable_conv(src, wei_dw, bia_dw, sz_stride, sz_padding, wei_pw, bia_pw, dst, relu,
+                                                             scales_dw, scales_pw, rm_dw, rm_pw));
 }
 
 std::unique_ptr<op> concat_conv(const std::vector<std::unique_ptr<memory>> &srcs, const std::unique_ptr<memory> &wei,

@@ -255,6 +255,27 @@ std::unique_ptr<op> depthwise_conv(const std::unique_ptr<memory> &src,
                                    bool relu = false, std::vector<float> scales = {1.f},
                                    round_mode rm = round_mode::nearest);
 
+// ---- extension: depthwise conv + pointwise conv, the depthwise-separable block (dfx_dwpw_* in dfx.h).  Stage 0 is
+// depthwise_conv() with a u8 result (ReLU implied), stage 1 a 1x1 stride-1 unpadded conv() on that tensor; dst holds,
+// bit for bit, what the two ops give one after the other.  wei_dw: plain oihw s8 {c, 1, kh, kw}; wei_pw: OIhw4i16o4i
+// {oc, c, 1, 1}; biases: format x or null; dst: nhwc {bs, oc, oh, ow}, its height and width are the output size.
+// `relu` is stage 1's.  3x3 windows with stride 1 / 2, c % 32 == 0, c <= 256, oc 64 / 128 / 256 and c * oc <= 64 KB
+// are the class of a ONE-launch kernel that keeps the u8 tensor in LDS (dfx.h, DFX_DWPW_FUSED); this call leaves the
+// path to the library's auto rule, which today takes two launches for every shape (the kernel is not timed yet).  submit / submit_async / wait, weight hashing and DEEPFUSION_DEVICES sharding are
+// depthwise_conv()'s. ----
+std::unique_ptr<op> depthwise_separable_conv(const std::unique_ptr<memory> &src,
+                                             const std::unique_ptr<memory> &wei_dw,
+                                             const std::unique_ptr<memory> &bia_dw,
+                                             std::array<int, 2> sz_stride,
+                                             std::array<int, 2> sz_padding,
+                                             const std::unique_ptr<memory> &wei_pw,
+                                             const std::unique_ptr<memory> &bia_pw,
+                                             std::unique_ptr<memory> &dst,
+                                             bool relu = false, std::vector<float> scales_dw = {1.f},
+                                             std::vector<float> scales_pw = {1.f},
+                                             round_mode rm_dw = round_mode::nearest,
+                                             round_mode rm_pw = round_mode::nearest);
+
 // ---- extension: the weight reorder the reference never shipped (deepfusion.cc:44-50) ----
 // Writes plain oihw s8 weights into `blocked` (an OIhw4i16o4i memory of the same
 // logical dims) in the [O/16][I/16][kh][kw][4i][16o][4i] byte order.

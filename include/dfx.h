@@ -249,6 +249,51 @@ typedef struct dfx_dwconv_info {
   char kernel_name[96];        /* path, window, stride and requant route (valid after set_weights) */
 } dfx_dwconv_info;
 typedef struct dfx_dwconv dfx_dwconv_t;
+
+/* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
+ *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
+ *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
+ *                 dst type u8 -- ReLU and unsigned saturation are implied; it has bia0_dt, nscales0 (1 or c) and
+ *                 round_mode0.
+ *        stage 1: a 1x1 stride-1 unpadded conv c -> oc on that u8 tensor with bia1_dt, nscales1 (1 or oc), relu,
+ *                 round_mode1 and dst_dt.
+ *      dst NHWC {bs,oh,ow,oc}.  The result is, bit for bit, dfx_dwconv_submit (dst u8) followed by dfx_conv_submit of
+ *      the unfused pointwise conv with the same numbers; where a dense conv can express the shape (c % 16 == 0, oh /
+ *      ow equal to the conv formula) it also equals the FUSED dfx_conv with ic = oc = c, block-diagonal conv0 weights
+ *      and oc1x1 = oc.  Parity unpinned: the reference asserts ngroups == 1. ---- */
+typedef struct dfx_dwpw_desc {
+  int32_t bs, c, ih, iw;
+  int32_t oh, ow;              /* (oh - 1) * sh - pad_t <= ih - 1, likewise in x */
+  int32_t kh, kw;              /* 1 .. 255 */
+  int32_t sh, sw;
+  int32_t pad_t, pad_l;
+  int32_t oc;
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t bia0_dt, bia1_dt;    /* DFX_UNDEF = none */
+  int32_t relu;                /* stage 1 (stage 0 always has one: its dst is u8) */
+  int32_t round_mode0, round_mode1;
+  int32_t nscales0;            /* 1 or c */
+  int32_t nscales1;            /* 1 or oc */
+  int32_t force_path;          /* -1 auto, else DFX_DWPW_* (testing) */
+} dfx_dwpw_desc;
+enum {  /* dfx_dwpw_info.path */
+  DFX_DWPW_FUSED = 0,          /* one launch (dwpw.cuh).  Class: 3x3, stride (1,1) or (2,2), c a multiple of 32 and
+                                  <= 256, oc in {64, 128, 256}, c * oc <= 64 KB, one image below 2^31 bytes on either
+                                  side.  AUTO RULE: auto takes this path only where it was measured faster than the two
+                                  ops by more than the +-4 % box spread; no shape has such a measurement yet (DESIGN.md
+                                  4.8), so today it is reached through force_path only */
+  DFX_DWPW_TWO_LAUNCH = 1      /* everything else the two ops accept: dfx_dwconv + dfx_conv through ONE u8 buffer the
+                                  handle owns, both on the caller's stream */
+};
+typedef struct dfx_dwpw_info {
+  int32_t path;
+  int32_t grid, block, lds_bytes;  /* of the fused kernel / of the conv kernel of the two-launch path */
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2*MAC of one submit, both stages */
+  uint64_t algorithmic_bytes;  /* src + weights + dst; two-launch path: + 2 x the u8 tensor between the stages */
+  char kernel_name[96];        /* path, window, stride, channel counts, both requant routes (valid after set_weights) */
+} dfx_dwpw_info;
+typedef struct dfx_dwpw dfx_dwpw_t;
 typedef void *dfx_stream_t; /* a hipStream_t; NULL = the default stream */
 typedef void *dfx_event_t;  /* a hipEvent_t */
 
@@ -399,6 +444,36 @@ int dfx_dwconv_submit_host(dfx_dwconv_t *h, const void *src_host, void *dst_host
 int dfx_dwconv_query(const dfx_dwconv_t *h, dfx_dwconv_info *info);
 int dfx_dwconv_destroy(dfx_dwconv_t *h);
 
+/* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
+ *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
+ *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
+ *      whatever dfx_conv_create rejects for the pointwise conv; DFX_ERR_UNSUPPORTED only for force_path =
+ *      DFX_DWPW_FUSED on a shape outside the fused class.  On auto everything outside it takes the two-launch path,
+ *      so the op is total over what the two ops accept.  set_weights: host pointers, copied; wei_dw is s8 {c,kh,kw}
+ *      as for dfx_dwconv_set_weights, wei_pw is {oc,c,1,1} in OIhw4i16o4i as for dfx_conv_set_weights; bias pointers
+ *      may be NULL when the dtype is DFX_UNDEF; it may be called again (not while a submit of the handle is in
+ *      flight).  It chooses each stage's requant route from the actual numbers, independently: "fast" when, for every
+ *      output channel of the stage, bias and scale are finite and (255 * max(P, N) + |bias|) * |scale| <= 2^30 (P, N:
+ *      sums of the channel's positive / negative weights' magnitudes), the stage's round mode is nearest and
+ *      DFX_NO_FAST is not set; else "exact" (the two-launch path: the routes of its two ops).  submit: asynchronous
+ *      on `s`; src and dst must be non-null and 16-byte aligned (DFX_ERR_INVALID otherwise, nothing is launched);
+ *      DFX_ERR_STATE before set_weights.  A handle may be submitted from several host threads and on several streams
+ *      at once.  Fused path: every launch has its own copy of the arguments, launches are independent.  Two-launch
+ *      path: the handle owns ONE buffer for the u8 tensor between the stages, so its submits are SERIALISED, as
+ *      dfx_catconv's: submits on one stream are ordered by the stream; once the handle has seen a second stream, every
+ *      submit records an event behind its conv and a submit on a stream other than the previous one's first waits, on
+ *      the device, for that event (the submits made while there was one stream only are covered by one event recorded
+ *      on it when the second stream appears).  The host never blocks.  A stream made elsewhere than dfx_stream_create
+ *      must outlive the handles submitted on it.  No CPU fallback.
+ *      Auto: see the AUTO RULE at DFX_DWPW_FUSED above. ---- */
+int dfx_dwpw_create(const dfx_dwpw_desc *desc, dfx_dwpw_t **out);
+int dfx_dwpw_set_weights(dfx_dwpw_t *h, const int8_t *wei_dw, const void *bia0, const float *scales0,
+                         const int8_t *wei_pw_blocked, const void *bia1, const float *scales1);
+int dfx_dwpw_submit(dfx_dwpw_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_dwpw_submit_host(dfx_dwpw_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_dwpw_query(const dfx_dwpw_t *h, dfx_dwpw_info *info);
+int dfx_dwpw_destroy(dfx_dwpw_t *h);
+
 /* ---- test hooks (not part of the reference's surface; used by tests/ only) ---- */
 /* Overwrites the LDS of every CU with a pattern (asynchronous, on `s`): makes a kernel that
  * reads LDS before publishing it fail deterministically (tests/test_gpu_first_launch.py). */
@@ -437,6 +512,9 @@ int dfx_debug_conv_requant(const dfx_conv_t *h, int32_t out[2]);
 int dfx_debug_catconv_requant(const dfx_catconv_t *h, int32_t out[2]);
 /* the depthwise conv's one stage, same numbering (0 exact, 1 fast) */
 int dfx_debug_dwconv_requant(const dfx_dwconv_t *h, int32_t out[1]);
+/* the depthwise + pointwise op's two stages {route0, route1}, same numbering; on the two-launch path the routes of
+ * the owned depthwise and conv handles */
+int dfx_debug_dwpw_requant(const dfx_dwpw_t *h, int32_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ from .capi import (  # noqa: F401
     ROUTE_EXACT, ROUTE_FAST, ROUTE_MAGIC, ROUTE_FMA,
     CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH, CatConvDesc, CatConvInfo, ConcatConv,
     DWCONV_AUTO, DWCONV_WINDOW, DWCONV_GENERIC, DwConvDesc, DwConvInfo, DwConv,
+    GCONV_AUTO, GCONV_MFMA, GCONV_GENERIC, GConvDesc, GConvInfo, GroupConv,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

@@ -18,6 +18,7 @@ FMT_NHWC, FMT_NCHW = 0, 1
 REORDER_FLAT, REORDER_GENERIC, REORDER_SMALLC, REORDER_TRANSPOSE = 0, 1, 2, 3
 CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH = -1, 0, 1
 DWCONV_AUTO, DWCONV_WINDOW, DWCONV_GENERIC = -1, 0, 1
+GCONV_AUTO, GCONV_MFMA, GCONV_GENERIC = -1, 0, 1
 DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
@@ -89,6 +90,18 @@ class DwConvDesc(ctypes.Structure):
 
 
 class DwConvInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
+class GConvDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "ic", "ih", "iw", "oc", "oh", "ow", "groups", "kh", "kw", "sh", "sw",
+                                             "pad_t", "pad_l", "dst_dt", "bia_dt", "relu", "round_mode", "nscales",
+                                             "force_path")]
+
+
+class GConvInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
@@ -211,6 +224,12 @@ def lib():
         "dfx_dwconv_submit_host": (i32, [vp, vp, vp]),
         "dfx_dwconv_query": (i32, [vp, ctypes.POINTER(DwConvInfo)]),
         "dfx_dwconv_destroy": (i32, [vp]),
+        "dfx_gconv_create": (i32, [ctypes.POINTER(GConvDesc), ctypes.POINTER(vp)]),
+        "dfx_gconv_set_weights": (i32, [vp, vp, vp, vp]),
+        "dfx_gconv_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_gconv_submit_host": (i32, [vp, vp, vp]),
+        "dfx_gconv_query": (i32, [vp, ctypes.POINTER(GConvInfo)]),
+        "dfx_gconv_destroy": (i32, [vp]),
         "dfx_dwpw_create": (i32, [ctypes.POINTER(DwPwDesc), ctypes.POINTER(vp)]),
         "dfx_dwpw_set_weights": (i32, [vp] * 7),
         "dfx_dwpw_submit": (i32, [vp, vp, vp, vp]),
@@ -223,6 +242,7 @@ def lib():
         "dfx_debug_conv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_catconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_debug_gconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwpw_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
     for name, (res, args) in sig.items():
@@ -562,6 +582,70 @@ class DwConv:
     def close(self):
         if self._h:
             lib().dfx_dwconv_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GroupConv:
+    """dfx_gconv_* handle: grouped int8 conv over NHWC u8 (include/dfx.h), weights plain oihw {oc, ic/groups, kh, kw}.
+    Where ic and oc are multiples of 16 and the output size is the conv's, the result equals the unfused Conv on
+    block-diagonal weights bit for bit.  out_hw defaults to the conv's (in + 2 * pad - k) // stride + 1; give it for
+    windows that hang over the bottom / right edge."""
+
+    def __init__(self, src_shape_nhwc, oc, groups, kernel, stride=(1, 1), pad=(1, 1), out_hw=None, dst_dt=DFX_U8,
+                 bia_dt=DFX_UNDEF, relu=False, rm=ROUND_NEAREST, nscales=1, force_path=GCONV_AUTO):
+        bs, ih, iw, ic = src_shape_nhwc
+        kh, kw = kernel
+        if out_hw is None:
+            out_hw = ((ih + 2 * pad[0] - kh) // stride[0] + 1, (iw + 2 * pad[1] - kw) // stride[1] + 1)
+        d = GConvDesc(bs, ic, ih, iw, oc, out_hw[0], out_hw[1], groups, kh, kw, stride[0], stride[1], pad[0], pad[1],
+                      dst_dt, bia_dt, int(relu), rm, nscales, force_path)
+        self.desc = d
+        self.src_shape = (bs, ih, iw, ic)
+        self.dst_shape = (bs, out_hw[0], out_hw[1], oc)
+        self.dst_np_dtype = _NP.get(dst_dt)
+        self._h = ctypes.c_void_p()
+        _check(lib().dfx_gconv_create(ctypes.byref(d), ctypes.byref(self._h)))
+
+    def set_weights(self, wei, scales, bia=None):
+        """wei: int8 {oc, ic/groups, kh, kw}; scales: 1 or oc floats; bia: oc entries of the descriptor's bias dtype"""
+        d = self.desc
+        ws = [np.ascontiguousarray(wei, dtype=np.int8), None if bia is None else np.ascontiguousarray(bia),
+              np.ascontiguousarray(scales, dtype=np.float32)]
+        assert ws[0].size == d.oc * (d.ic // d.groups) * d.kh * d.kw, ws[0].shape
+        assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
+        _check(lib().dfx_gconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+    def submit(self, src_dev, dst_dev, stream=None):
+        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers), 16-byte aligned"""
+        _check(lib().dfx_gconv_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
+
+    def submit_host(self, src_np):
+        src = np.ascontiguousarray(src_np, dtype=np.uint8)
+        assert src.shape == self.src_shape, (src.shape, self.src_shape)
+        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
+        _check(lib().dfx_gconv_submit_host(self._h, _p(src), _p(dst)))
+        return dst
+
+    def info(self):
+        i = GConvInfo()
+        _check(lib().dfx_gconv_query(self._h, ctypes.byref(i)))
+        return i
+
+    def requant(self):
+        """requant route as set_weights proved it (dfx_debug_gconv_requant): ROUTE_EXACT or ROUTE_FAST"""
+        v = (ctypes.c_int32 * 1)()
+        _check(lib().dfx_debug_gconv_requant(self._h, v))
+        return v[0]
+
+    def close(self):
+        if self._h:
+            lib().dfx_gconv_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

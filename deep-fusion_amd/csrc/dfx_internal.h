@@ -1,5 +1,5 @@
 // dfx_internal.h -- the few host-side helpers the translation units behind include/dfx.h share
-// (dfx_api.hip, reorder_api.hip, catconv_api.hip, dwconv_api.hip).  Not installed, not part of the C ABI.
+// (dfx_api.hip, reorder_api.hip, catconv_api.hip, dwconv_api.hip, gconv_api.hip).  Not installed, not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -255,6 +255,25 @@ std::unique_ptr<op> depthwise_conv(const std::unique_ptr<memory> &src,
                                    bool relu = false, std::vector<float> scales = {1.f},
                                    round_mode rm = round_mode::nearest);
 
+// ---- extension: grouped conv (dfx_gconv_* in dfx.h), 1 <= groups <= ic: output channel o reads only the ic / groups
+// input channels of its group o / (oc / groups) -- the 3x3 of a ResNeXt / RegNet block (the reference asserts
+// ngroups == 1).  src: nhwc u8; wei: plain oihw s8 of dims {oc, ic / groups, kh, kw}; bia: format x, oc entries, or
+// null; dst: nhwc u8 / s8 / s32 / f32 with src's batch and oc channels -- ITS height and width are the output size, as
+// for depthwise_conv(); padding is {top, left}.  Arithmetic, scales, ReLU and rounding are conv()'s: where ic and oc are
+// multiples of 16 and the output size is conv()'s, dst holds, bit for bit, what conv() gives with block-diagonal
+// weights.  3x3 windows with stride 1 / 2, ic == oc a multiple of 32 and ic / groups in {4, 8, 16, 32, 64} run on an
+// int8-MFMA kernel that does the groups' work only, everything else on a generic one.  submit / submit_async / wait,
+// weight hashing and DEEPFUSION_DEVICES sharding are depthwise_conv()'s. ----
+std::unique_ptr<op> grouped_conv(const std::unique_ptr<memory> &src,
+                                 const std::unique_ptr<memory> &wei,
+                                 const std::unique_ptr<memory> &bia,
+                                 int groups,
+                                 std::array<int, 2> sz_stride,
+                                 std::array<int, 2> sz_padding,
+                                 std::unique_ptr<memory> &dst,
+                                 bool relu = false, std::vector<float> scales = {1.f},
+                                 round_mode rm = round_mode::nearest);
+
 // ---- extension: depthwise conv + pointwise conv, the depthwise-separable block (dfx_dwpw_* in dfx.h).  Stage 0 is
 // depthwise_conv() with a u8 result (ReLU implied), stage 1 a 1x1 stride-1 unpadded conv() on that tensor; dst holds,
 // bit for bit, what the two ops give one after the other.  wei_dw: plain oihw s8 {c, 1, kh, kw}; wei_pw: OIhw4i16o4i

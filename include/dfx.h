@@ -250,6 +250,50 @@ typedef struct dfx_dwconv_info {
 } dfx_dwconv_info;
 typedef struct dfx_dwconv dfx_dwconv_t;
 
+/* ---- grouped int8 conv, 1 <= groups <= ic: output channel o reads only the ic / groups input channels of its group
+ *      g(o) = o / (oc / groups) -- the 3x3 of a ResNeXt / RegNet block.  src NHWC u8 {bs,ih,iw,ic}; weights s8
+ *      {oc, ic/groups, kh, kw} plain row-major (the layout frameworks keep them in); dst NHWC {bs,oh,ow,oc}.
+ *        acc[n,oy,ox,o] = sum over i < ic/groups, ky, kx of
+ *                         src[n, oy*sh - pad_t + ky, ox*sw - pad_l + kx, g(o) * (ic/groups) + i] * w[o,i,ky,kx]
+ *                         (taps outside the input are skipped)
+ *        f = float(acc);  f = f + bias[o] (if any);  f = f * scale[o or 0];  ReLU (asked for, or dst is u8):
+ *        f = (0 > f) ? 0 : f;  dst = store(f, dst_dt, round_mode)
+ *      with the depthwise op's arithmetic: separately rounded add and multiply, the bias converted like the conv's,
+ *      the x86 conversion (NaN / out of range -> 0x80000000 -> u8 255, s8 -128).  Where ic and oc are multiples of 16
+ *      and oh / ow follow the conv formula the result is, bit for bit, the unfused dfx_conv with
+ *      W[o][j] = w[o][j - g(o) * ic/groups] inside o's group and 0 outside.  oh and ow are given by the caller as in
+ *      dfx_dwconv_desc: windows may hang over the bottom / right edge.  Parity unpinned: the reference asserts
+ *      ngroups == 1. ---- */
+typedef struct dfx_gconv_desc {
+  int32_t bs, ic, ih, iw;
+  int32_t oc, oh, ow;          /* (oh - 1) * sh - pad_t <= ih - 1, likewise in x */
+  int32_t groups;              /* divides ic and oc; kh * kw * ic / groups <= 65025 */
+  int32_t kh, kw;
+  int32_t sh, sw;
+  int32_t pad_t, pad_l;
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t bia_dt;              /* DFX_UNDEF = none */
+  int32_t relu, round_mode;
+  int32_t nscales;             /* 1 or oc */
+  int32_t force_path;          /* -1 auto, else DFX_GCONV_* (testing) */
+} dfx_gconv_desc;
+enum {  /* dfx_gconv_info.path */
+  DFX_GCONV_MFMA = 0,          /* the int8-MFMA kernel (gconv.cuh).  Covers: 3x3 window; stride (1,1) or (2,2);
+                                  ic == oc, a multiple of 32; ic / groups in {4, 8, 16, 32, 64}; one image below 2^31
+                                  bytes on either side.  Auto takes it everywhere in this class. */
+  DFX_GCONV_GENERIC = 1        /* everything else: one thread per output element, any window / stride / channel
+                                  counts / groups (groups = 1 and groups = ic included), exact requant only */
+};
+typedef struct dfx_gconv_info {
+  int32_t path;
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2*MAC of one submit: 2 * kh * kw * ic/groups per output value */
+  uint64_t algorithmic_bytes;  /* src + weights + dst */
+  char kernel_name[96];        /* path, window, stride, cpg, dst type and requant route (valid after set_weights) */
+} dfx_gconv_info;
+typedef struct dfx_gconv dfx_gconv_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -444,6 +488,29 @@ int dfx_dwconv_submit_host(dfx_dwconv_t *h, const void *src_host, void *dst_host
 int dfx_dwconv_query(const dfx_dwconv_t *h, dfx_dwconv_info *info);
 int dfx_dwconv_destroy(dfx_dwconv_t *h);
 
+/* ---- grouped conv (dfx_gconv_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for a non-positive size or stride, a negative padding, groups < 1, ic or oc not divisible by
+ *      groups, kh * kw * ic/groups > 65025 (= 255^2, the depthwise op's bound: below it the accumulator cannot leave
+ *      s32), an output row / column whose window starts below / right of the input, a bad dtype / round mode /
+ *      nscales / force_path, a tensor of 2^31 pixels or more; DFX_ERR_UNSUPPORTED only for force_path =
+ *      DFX_GCONV_MFMA on a shape outside that class.  On auto everything outside it takes the generic path, groups = 1
+ *      and groups = ic included: the op is total and delegates to no other op.  set_weights: host pointers, copied;
+ *      wei is s8 {oc, ic/groups, kh, kw}; bia has oc entries of bia_dt (NULL when DFX_UNDEF); it may be called again
+ *      (not while a submit of the handle is in flight) and chooses the requant route from the actual numbers: "fast"
+ *      (hardware conversions) when, for every output channel, bias and scale are finite and
+ *      (255 * max(P, N) + |bias|) * |scale| <= 2^30 (P, N: sums of the channel's positive / negative weights'
+ *      magnitudes over its ic/groups * kh * kw taps), the round mode is nearest and DFX_NO_FAST is not set; else
+ *      "exact".  The generic kernel is always exact.  submit: asynchronous on `s`; src and dst must be non-null and
+ *      16-byte aligned (DFX_ERR_INVALID otherwise, nothing is launched); DFX_ERR_STATE before set_weights.  Every
+ *      launch has its own copy of the arguments: one handle serves several streams and host threads at once.  No CPU
+ *      fallback. ---- */
+int dfx_gconv_create(const dfx_gconv_desc *desc, dfx_gconv_t **out);
+int dfx_gconv_set_weights(dfx_gconv_t *h, const int8_t *wei, const void *bia, const float *scales);
+int dfx_gconv_submit(dfx_gconv_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_gconv_submit_host(dfx_gconv_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_gconv_query(const dfx_gconv_t *h, dfx_gconv_info *info);
+int dfx_gconv_destroy(dfx_gconv_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -512,6 +579,8 @@ int dfx_debug_conv_requant(const dfx_conv_t *h, int32_t out[2]);
 int dfx_debug_catconv_requant(const dfx_catconv_t *h, int32_t out[2]);
 /* the depthwise conv's one stage, same numbering (0 exact, 1 fast) */
 int dfx_debug_dwconv_requant(const dfx_dwconv_t *h, int32_t out[1]);
+/* the grouped conv's one stage, same numbering (0 exact, 1 fast) */
+int dfx_debug_gconv_requant(const dfx_gconv_t *h, int32_t out[1]);
 /* the depthwise + pointwise op's two stages {route0, route1}, same numbering; on the two-launch path the routes of
  * the owned depthwise and conv handles */
 int dfx_debug_dwpw_requant(const dfx_dwpw_t *h, int32_t out[2]);

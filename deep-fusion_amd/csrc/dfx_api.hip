@@ -1900,12 +1900,16 @@ int dfx_concat_create(const dfx_concat_desc *desc, dfx_concat_t **out) {
 int dfx_concat_submit(dfx_concat_t *h, const void *const *srcs_dev, void *dst_dev, dfx_stream_t s) {
   if (!h || !srcs_dev || !dst_dev) return fail(DFX_ERR_INVALID, "concat_submit: null argument");
   DeviceGuard dg(h->device);
-  for (int i = 0; i < h->d.n_inputs; ++i) {
+  ConcatArgs a = h->args;  // per-launch copy: h->args is written at create only, so submits on several
+                           // streams and from several host threads never see each other's pointers
+  for (int i = 0; i < a.n_inputs; ++i) {
     if (!srcs_dev[i]) return fail(DFX_ERR_INVALID, "concat_submit: null input %d", i);
-    h->args.src[i] = (const unsigned char *)srcs_dev[i];
+    if ((uintptr_t)srcs_dev[i] % 16) return fail(DFX_ERR_INVALID, "concat_submit: input %d not 16-byte aligned", i);
+    a.src[i] = (const unsigned char *)srcs_dev[i];
   }
-  h->args.dst = (unsigned char *)dst_dev;
-  launch_concat(h->args, (hipStream_t)s);
+  if ((uintptr_t)dst_dev % 16) return fail(DFX_ERR_INVALID, "concat_submit: dst not 16-byte aligned");
+  a.dst = (unsigned char *)dst_dev;
+  launch_concat(a, (hipStream_t)s);
   HIP_TRY(hipGetLastError());
   return DFX_OK;
 }
@@ -1914,6 +1918,8 @@ int dfx_concat_submit_gathered(dfx_concat_t *h, const void *gathered_dev, const 
                                void *dst_dev, dfx_stream_t s) {
   if (!h || !gathered_dev || !offsets || !dst_dev)
     return fail(DFX_ERR_INVALID, "concat_submit_gathered: null argument");
+  if ((uintptr_t)gathered_dev % 16)
+    return fail(DFX_ERR_INVALID, "concat_submit_gathered: base not 16-byte aligned");
   const void *ptrs[CONCAT_MAX_INPUTS];
   for (int i = 0; i < h->d.n_inputs; ++i) {
     if (offsets[i] % 16) return fail(DFX_ERR_INVALID, "concat_submit_gathered: offset %d not 16-byte aligned", i);
@@ -2011,6 +2017,9 @@ int dfx_pool_submit(dfx_pool_t *h, const void *src_dev, void *dst_dev, dfx_strea
   PoolArgs a = h->args;  // per-launch copy: concurrent submits on several streams are independent
   a.src = (const unsigned char *)src_dev;
   a.dst = (unsigned char *)dst_dev;
+  if (((uintptr_t)src_dev | (uintptr_t)dst_dev) % dt_size(a.dt))
+    return fail(DFX_ERR_INVALID, "pool_submit: src or dst not aligned to the element size (%d bytes)",
+                (int)dt_size(a.dt));
   if (a.vec && (((uintptr_t)src_dev | (uintptr_t)dst_dev) % 16)) {  // 16-byte vector path needs aligned buffers:
     a.vec = 0;                                                       // misaligned ones take the per-channel path
     a.groups = a.c;

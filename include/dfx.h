@@ -410,7 +410,18 @@ int dfx_conv_query(const dfx_conv_t *h, dfx_conv_info *info);
 int dfx_conv_destroy(dfx_conv_t *h);
 
 /* ---- concat: replaces op_concat<T> (src/op_concat.h:28-61, op_concat.cc:22-72)
- *      and jit_concat_kernel (src/jit_concat_kernel.cc:30-197) ---- */
+ *      and jit_concat_kernel (src/jit_concat_kernel.cc:30-197).  create: DFX_ERR_INVALID for a non-positive
+ *      size, a bad dtype, a branch whose channels are not a multiple of 16 (1-byte types) or 4 (4-byte types);
+ *      DFX_ERR_UNSUPPORTED for more than 64 branches.  submit: asynchronous on `s`; every branch pointer and dst
+ *      must be non-null and 16-byte aligned (DFX_ERR_INVALID otherwise, nothing is launched): the kernel moves
+ *      16-byte chunks relative to them.  submit_gathered asks the same of the base pointer and of every offset.
+ *      Branches may alias each other (one buffer may be given as several branches); dst must not overlap a branch.
+ *      Every launch has its own copy of the arguments and submit does not write to the handle: one handle may be
+ *      submitted from several host threads and on several streams at once, the launches are independent.
+ *      submit_host is synchronous and stages through device buffers and a stream that the handle owns: one thread
+ *      at a time per handle.  post_relu is max(0, x) in the element's own type; for f32 it is vmaxps(zero, x),
+ *      the second operand wins ties and NaNs: ReLU(-0) = -0 and a NaN passes through with its bits; without
+ *      post_relu every value is copied bit for bit. ---- */
 int dfx_concat_create(const dfx_concat_desc *desc, dfx_concat_t **out);
 int dfx_concat_submit(dfx_concat_t *h, const void *const *srcs_dev, void *dst_dev,
                       dfx_stream_t s);
@@ -422,7 +433,26 @@ int dfx_concat_submit_gathered(dfx_concat_t *h, const void *gathered_dev,
                                const uint64_t *offsets, void *dst_dev, dfx_stream_t s);
 int dfx_concat_destroy(dfx_concat_t *h);
 
-/* ---- pooling stage of conv+relu+pool, eltwise-sum(+relu) (see the descriptors above) ---- */
+/* ---- pooling stage of conv+relu+pool, eltwise-sum(+relu) (see the descriptors above).
+ *      pool create: DFX_ERR_INVALID for a non-positive size / window / stride, a negative padding, a bad dtype or
+ *      algorithm, and for an output window that lies entirely in the padding (so pad < window on each axis).
+ *      pool submit: asynchronous on `s`; src and dst must be non-null and aligned to the element size (4 bytes for
+ *      f32 / s32; DFX_ERR_INVALID otherwise, nothing is launched).  When c * sizeof(element) is a multiple of 16
+ *      and both pointers are 16-byte aligned the kernel moves 16 bytes per lane; otherwise it takes one element
+ *      per lane, with the same results.  dst must not overlap src.
+ *      f32 max pooling is vmaxps(acc, x) over the window positions inside the input, rows outer, columns inner,
+ *      starting from -Inf: the second operand wins ties and NaNs.  So a NaN is the result only if it is the LAST
+ *      value of its window (then with its bits), an earlier NaN is dropped, and of +0 / -0 the later one wins.
+ *      f32 averages and sums are plain IEEE binary32 operations in the documented order, denormals included; a NaN
+ *      that an operation PRODUCES (Inf - Inf) is the device's default NaN, not x86's.
+ *      eltwise create: DFX_ERR_UNSUPPORTED for n_inputs outside 2..8, DFX_ERR_INVALID for a non-positive size or
+ *      a bad dtype.  eltwise submit: asynchronous on `s`; every input and dst must be non-null and 16-byte aligned
+ *      (DFX_ERR_INVALID otherwise, nothing is launched).  dst may BE one of the inputs (in place: every element is
+ *      read from all inputs before it is written, by the same lane) and one buffer may be given as several
+ *      inputs; a dst that overlaps an input at any other offset is undefined.  post_relu for f32 is
+ *      vmaxps(zero, x) as for concat: ReLU(-0) = -0, ReLU(NaN) = NaN.
+ *      Both: every launch has its own copy of the arguments and submit does not write to the handle, so one
+ *      handle may be submitted from several host threads and on several streams at once. ---- */
 int dfx_pool_create(const dfx_pool_desc *desc, dfx_pool_t **out);
 int dfx_pool_submit(dfx_pool_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
 int dfx_pool_destroy(dfx_pool_t *h);

@@ -111,7 +111,8 @@ def avgpool(src, kernel, stride, pad, out_hw, include_padding):
         return (tot / div[None, :, :, None].astype(np.float32)).astype(np.float32)
     q = np.rint(tot.astype(np.float32) / div[None, :, :, None].astype(np.float32))
     info = np.iinfo(src.dtype)
-    return np.clip(q, info.min, info.max).astype(src.dtype)
+    # clip in f64: as an f32, INT32_MAX is 2^31, which a quotient of exactly 2^31 would pass and the cast wrap
+    return np.clip(q.astype(np.float64), info.min, info.max).astype(src.dtype)
 
 
 def eltwise_sum(srcs, post_relu=False):
@@ -128,3 +129,35 @@ def eltwise_sum(srcs, post_relu=False):
         acc = np.maximum(acc, 0)
     info = np.iinfo(srcs[0].dtype)
     return np.clip(acc, info.min, info.max).astype(srcs[0].dtype)
+
+
+def relu_select(x):
+    """f32 ReLU in the operand order of vmaxps(zero, x): the second operand wins ties and NaNs, so ReLU(-0) = -0 and
+    a NaN passes through with its bits"""
+    assert x.dtype == np.float32
+    return np.where(np.float32(0) > x, np.float32(0), x)
+
+
+def maxpool_select(src, kernel, stride, pad, out_hw):
+    """Second, independent formulation of NHWC max pooling that follows the select order of vmaxps(acc, v) (maxpool
+    above uses np.maximum, which propagates every NaN): start from the lowest value (-Inf), then
+    acc = where(acc > v, acc, v) over the shifted strided views, ky outer, kx inner; positions in the padding are
+    skipped through a mask, they take no part."""
+    bs, ih, iw, c = src.shape
+    oh, ow = out_hw
+    low = np.float32(-np.inf) if src.dtype == np.float32 else np.iinfo(src.dtype).min
+    need_h = (oh - 1) * stride[0] + kernel[0]
+    need_w = (ow - 1) * stride[1] + kernel[1]
+    buf = np.full((bs, max(need_h, pad[0] + ih), max(need_w, pad[1] + iw), c), low, dtype=src.dtype)
+    msk = np.zeros(buf.shape[1:3], dtype=bool)
+    buf[:, pad[0]:pad[0] + ih, pad[1]:pad[1] + iw, :] = src
+    msk[pad[0]:pad[0] + ih, pad[1]:pad[1] + iw] = True
+    acc = np.full((bs, oh, ow, c), low, dtype=src.dtype)
+    for ky in range(kernel[0]):
+        for kx in range(kernel[1]):
+            sl = (slice(ky, ky + (oh - 1) * stride[0] + 1, stride[0]), slice(kx, kx + (ow - 1) * stride[1] + 1, stride[1]))
+            v = buf[(slice(None),) + sl]
+            with np.errstate(invalid="ignore"):
+                pick = np.where(acc > v, acc, v)
+            acc = np.where(msk[sl][None, :, :, None], pick, acc)
+    return acc

@@ -291,8 +291,68 @@ def _stream_ptr(stream):
     return ctypes.c_void_p(stream if isinstance(stream, int) else stream.cuda_stream)
 
 
-class Conv:
+class _Handle:
+    """What the handle classes share: a dfx_<op>_* handle in _h, made by _create() and released by close(); query,
+    requant route and the single-source submits, each one call of the C entry point named after _OP.  An op that lacks
+    an entry point (dfx.h) raises AttributeError for it."""
+
+    _OP = None             # C symbol prefix, "dfx_conv"
+    _INFO = None           # struct of dfx_<op>_query
+    _ROUTES = 0            # requant routes dfx_debug_<op>_requant reports
+    src_np_dtype = np.uint8
+
+    def _fn(self, what):
+        return getattr(lib(), "%s_%s" % (self._OP, what))
+
+    def _create(self, desc, *more):
+        self._h = ctypes.c_void_p()
+        _check(self._fn("create")(ctypes.byref(desc), *more, ctypes.byref(self._h)))
+
+    def submit(self, src_dev, dst_dev, stream=None):
+        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers), 16-byte aligned"""
+        _check(self._fn("submit")(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
+
+    def submit_host(self, src_np):
+        src = np.ascontiguousarray(src_np, dtype=self.src_np_dtype)
+        want = getattr(self, "src_shape", src.shape)
+        assert src.shape == want, (src.shape, want)
+        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
+        _check(self._fn("submit_host")(self._h, _p(src), _p(dst)))
+        return dst
+
+    def info(self):
+        i = self._INFO()
+        _check(self._fn("query")(self._h, ctypes.byref(i)))
+        return i
+
+    def requant(self):
+        """requant route(s) as set_weights proved them (dfx_debug_<op>_requant; launches nothing): ROUTE_EXACT /
+        ROUTE_FAST / ROUTE_MAGIC / ROUTE_FMA, -1 for a stage the op does not have.  One value for an op of one stage,
+        the tuple (stage 0, stage 1) otherwise."""
+        v = (ctypes.c_int32 * self._ROUTES)()
+        _check(getattr(lib(), self._OP.replace("dfx_", "dfx_debug_") + "_requant")(self._h, v))
+        return v[0] if self._ROUTES == 1 else tuple(v)
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _ptr_array(arrays_or_tensors, ptr_of):
+    return (ctypes.c_void_p * len(arrays_or_tensors))(*[ptr_of(a) for a in arrays_or_tensors])
+
+
+class Conv(_Handle):
     """dfx_conv_* handle: the op_conv<T> of the reference (src/op_conv.h:34-96)."""
+
+    _OP, _INFO, _ROUTES = "dfx_conv", ConvInfo, 2
 
     def __init__(self, src_shape_nhwc, wei_shape_oihw, stride=(1, 1), pad=(1, 1), dst_dt=DFX_U8,
                  oc1x1=0, bia0_dt=DFX_UNDEF, bia1_dt=DFX_UNDEF, conv0_relu=False,
@@ -315,8 +375,7 @@ class Conv:
         d.force_variant = force_variant
         d.fuse_pool = fuse_pool
         self.desc = d
-        self._h = ctypes.c_void_p()
-        _check(lib().dfx_conv_create(ctypes.byref(d), ctypes.byref(self._h)))
+        self._create(d)
         self.dst_shape = ((bs, d.oh // 2, d.ow // 2, oc) if fuse_pool else (bs, d.oh, d.ow, oc1x1 if oc1x1 else oc))
         self.dst_np_dtype = _NP[dst_dt]
 
@@ -327,24 +386,7 @@ class Conv:
               None if wei1_blk is None else np.ascontiguousarray(wei1_blk, dtype=np.int8),
               None if bia1 is None else np.ascontiguousarray(bia1),
               None if scales1 is None else np.ascontiguousarray(scales1, dtype=np.float32)]
-        _check(lib().dfx_conv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2]), _p(ws[3]),
-                                          _p(ws[4]), _p(ws[5])))
-
-    def submit(self, src_dev, dst_dev, stream=None):
-        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers)."""
-        _check(lib().dfx_conv_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev),
-                                     _stream_ptr(stream)))
-
-    def submit_host(self, src_np):
-        src = np.ascontiguousarray(src_np, dtype=np.uint8)
-        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
-        _check(lib().dfx_conv_submit_host(self._h, _p(src), _p(dst)))
-        return dst
-
-    def info(self):
-        i = ConvInfo()
-        _check(lib().dfx_conv_query(self._h, ctypes.byref(i)))
-        return i
+        _check(lib().dfx_conv_set_weights(self._h, *[_p(w) for w in ws]))
 
     def sched(self):
         """unit hand-out of a resident-weight op (dfx_debug_conv_sched): a ConvSched; launches nothing."""
@@ -352,80 +394,39 @@ class Conv:
         _check(lib().dfx_debug_conv_sched(self._h, v, len(v)))
         return ConvSched(*v)
 
-    def requant(self):
-        """requant route of stage 0 and stage 1 as set_weights proved it (dfx_debug_conv_requant): a tuple of
-        ROUTE_EXACT / ROUTE_FAST / ROUTE_MAGIC / ROUTE_FMA, -1 for a stage the op does not have; launches nothing."""
-        v = (ctypes.c_int32 * 2)()
-        _check(lib().dfx_debug_conv_requant(self._h, v))
-        return (v[0], v[1])
 
-    def close(self):
-        if self._h:
-            lib().dfx_conv_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Pool:
+class Pool(_Handle):
     """dfx_pool_* handle: the pooling stage of the reference's planned conv+relu+pool op (max pooling, NHWC)."""
 
+    _OP = "dfx_pool"
     MAX, AVG_INCLUDE_PADDING, AVG_EXCLUDE_PADDING = 0, 1, 2
 
     def __init__(self, bs, c, ih, iw, oh, ow, kernel, stride, pad, np_dtype, algo=0):
         d = PoolDesc(bs, c, ih, iw, oh, ow, kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1],
                      _DT[np.dtype(np_dtype)], algo)
         self.dst_shape = (bs, oh, ow, c)
-        self._h = ctypes.c_void_p()
-        _check(lib().dfx_pool_create(ctypes.byref(d), ctypes.byref(self._h)))
-
-    def submit(self, src_dev, dst_dev, stream=None):
-        _check(lib().dfx_pool_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
-
-    def close(self):
-        if self._h:
-            lib().dfx_pool_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(d)
 
 
-class EltwiseSum:
+class EltwiseSum(_Handle):
     """dfx_eltwise_* handle: the reference's planned eltwise-sum + relu op."""
 
+    _OP = "dfx_eltwise"
+
     def __init__(self, n_inputs, elems, np_dtype, post_relu=False):
-        d = EltwiseDesc(n_inputs, elems, _DT[np.dtype(np_dtype)], int(post_relu))
-        self._h = ctypes.c_void_p()
-        _check(lib().dfx_eltwise_create(ctypes.byref(d), ctypes.byref(self._h)))
+        self._create(EltwiseDesc(n_inputs, elems, _DT[np.dtype(np_dtype)], int(post_relu)))
 
     def submit(self, srcs_dev, dst_dev, stream=None):
-        ptrs = (ctypes.c_void_p * len(srcs_dev))(*[_dev_ptr(s).value for s in srcs_dev])
+        ptrs = _ptr_array(srcs_dev, lambda t: _dev_ptr(t).value)
         _check(lib().dfx_eltwise_submit(self._h, ptrs, _dev_ptr(dst_dev), _stream_ptr(stream)))
 
-    def close(self):
-        if self._h:
-            lib().dfx_eltwise_destroy(self._h)
-            self._h = ctypes.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Reorder:
+class Reorder(_Handle):
     """dfx_reorder_* handle: layout (NHWC <-> NCHW), dtype and scale conversion of an activation tensor with
     channel pad / crop (include/dfx.h).  `shape` is the logical (bs, c, h, w) of the source; the physical order
     of src and dst follows src_fmt / dst_fmt."""
+
+    _OP, _INFO = "dfx_reorder", ReorderInfo
 
     def __init__(self, shape_nchw, src_dtype, dst_dtype, src_fmt=FMT_NCHW, dst_fmt=FMT_NHWC, dst_c=None,
                  scales=None, round_mode=ROUND_NEAREST):
@@ -439,41 +440,15 @@ class Reorder:
         self.src_shape = (bs, h, w, c) if src_fmt == FMT_NHWC else (bs, c, h, w)
         self.dst_shape = (bs, h, w, dst_c) if dst_fmt == FMT_NHWC else (bs, dst_c, h, w)
         self.src_np_dtype, self.dst_np_dtype = _NP.get(src_dt), _NP.get(dst_dt)
-        self._h = ctypes.c_void_p()
-        _check(lib().dfx_reorder_create(ctypes.byref(d), _p(sc), ctypes.byref(self._h)))
-
-    def submit(self, src_dev, dst_dev, stream=None):
-        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers), 16-byte aligned."""
-        _check(lib().dfx_reorder_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
-
-    def submit_host(self, src_np):
-        src = np.ascontiguousarray(src_np, dtype=self.src_np_dtype)
-        assert src.shape == self.src_shape, (src.shape, self.src_shape)
-        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
-        _check(lib().dfx_reorder_submit_host(self._h, _p(src), _p(dst)))
-        return dst
-
-    def info(self):
-        i = ReorderInfo()
-        _check(lib().dfx_reorder_query(self._h, ctypes.byref(i)))
-        return i
-
-    def close(self):
-        if self._h:
-            lib().dfx_reorder_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(d, _p(sc))
 
 
-class ConcatConv:
+class ConcatConv(_Handle):
     """dfx_catconv_* handle: channel concat of NHWC u8 branches + pointwise conv in one launch (include/dfx.h).
     The result equals Concat followed by the unfused 1x1 Conv bit for bit; the concatenated tensor is never
     written on the fused path."""
+
+    _OP, _INFO, _ROUTES = "dfx_catconv", CatConvInfo, 2  # (the routes of the inner pointwise conv, as Conv.requant())
 
     def __init__(self, bs, h, w, channels, oc, dst_dt=DFX_U8, bia_dt=DFX_UNDEF, relu=False, rm=ROUND_NEAREST,
                  nscales=1, force_path=CATCONV_AUTO):
@@ -484,8 +459,7 @@ class ConcatConv:
         self.dst_shape = (bs, h, w, oc)
         self.src_shapes = [(bs, h, w, c) for c in self.channels]
         self.dst_np_dtype = _NP.get(dst_dt)
-        self._h = ctypes.c_void_p()
-        _check(lib().dfx_catconv_create(ctypes.byref(d), ctypes.byref(self._h)))
+        self._create(d)
 
     def set_weights(self, wei_blk, scales, bia=None):
         """wei_blk: {oc, sum(channels), 1, 1} in OIhw4i16o4i order (reorder_oihw_to_blocked)"""
@@ -495,59 +469,41 @@ class ConcatConv:
 
     def submit(self, srcs_dev, dst_dev, stream=None):
         """asynchronous; srcs_dev: one torch CUDA tensor (or raw pointer) per branch, 16-byte aligned"""
-        ptrs = (ctypes.c_void_p * len(srcs_dev))(*[_dev_ptr(s).value for s in srcs_dev])
+        ptrs = _ptr_array(srcs_dev, lambda t: _dev_ptr(t).value)
         _check(lib().dfx_catconv_submit(self._h, ptrs, _dev_ptr(dst_dev), _stream_ptr(stream)))
 
     def submit_host(self, srcs_np):
         srcs = [np.ascontiguousarray(s, dtype=np.uint8) for s in srcs_np]
         assert [s.shape for s in srcs] == self.src_shapes, ([s.shape for s in srcs], self.src_shapes)
-        ptrs = (ctypes.c_void_p * len(srcs))(*[s.ctypes.data for s in srcs])
         dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
-        _check(lib().dfx_catconv_submit_host(self._h, ptrs, _p(dst)))
+        _check(lib().dfx_catconv_submit_host(self._h, _ptr_array(srcs, lambda a: a.ctypes.data), _p(dst)))
         return dst
 
-    def info(self):
-        i = CatConvInfo()
-        _check(lib().dfx_catconv_query(self._h, ctypes.byref(i)))
-        return i
 
-    def requant(self):
-        """requant route of the inner pointwise conv (dfx_debug_catconv_requant), as Conv.requant()"""
-        v = (ctypes.c_int32 * 2)()
-        _check(lib().dfx_debug_catconv_requant(self._h, v))
-        return (v[0], v[1])
-
-    def close(self):
-        if self._h:
-            lib().dfx_catconv_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _conv_out_hw(ih, iw, kernel, stride, pad):
+    return ((ih + 2 * pad[0] - kernel[0]) // stride[0] + 1, (iw + 2 * pad[1] - kernel[1]) // stride[1] + 1)
 
 
-class DwConv:
+class DwConv(_Handle):
     """dfx_dwconv_* handle: depthwise int8 conv over NHWC u8 (include/dfx.h).  For c a multiple of 16 the result equals
     the unfused Conv with ic = oc = c and block-diagonal weights bit for bit.  out_hw defaults to the conv's
     (in + 2 * pad - k) // stride + 1; give it for windows that hang over the bottom / right edge."""
+
+    _OP, _INFO, _ROUTES = "dfx_dwconv", DwConvInfo, 1
 
     def __init__(self, src_shape_nhwc, kernel, stride=(1, 1), pad=(1, 1), out_hw=None, dst_dt=DFX_U8, bia_dt=DFX_UNDEF,
                  relu=False, rm=ROUND_NEAREST, nscales=1, force_path=DWCONV_AUTO):
         bs, ih, iw, c = src_shape_nhwc
         kh, kw = kernel
         if out_hw is None:
-            out_hw = ((ih + 2 * pad[0] - kh) // stride[0] + 1, (iw + 2 * pad[1] - kw) // stride[1] + 1)
+            out_hw = _conv_out_hw(ih, iw, kernel, stride, pad)
         d = DwConvDesc(bs, c, ih, iw, out_hw[0], out_hw[1], kh, kw, stride[0], stride[1], pad[0], pad[1], dst_dt, bia_dt,
                        int(relu), rm, nscales, force_path)
         self.desc = d
         self.src_shape = (bs, ih, iw, c)
         self.dst_shape = (bs, out_hw[0], out_hw[1], c)
         self.dst_np_dtype = _NP.get(dst_dt)
-        self._h = ctypes.c_void_p()
-        _check(lib().dfx_dwconv_create(ctypes.byref(d), ctypes.byref(self._h)))
+        self._create(d)
 
     def set_weights(self, wei, scales, bia=None):
         """wei: int8 {c, kh, kw}; scales: 1 or c floats; bia: c entries of the descriptor's bias dtype"""
@@ -557,60 +513,28 @@ class DwConv:
         assert ws[2].size == self.desc.nscales and (bia is None or ws[1].size == self.desc.c)
         _check(lib().dfx_dwconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
 
-    def submit(self, src_dev, dst_dev, stream=None):
-        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers), 16-byte aligned"""
-        _check(lib().dfx_dwconv_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
 
-    def submit_host(self, src_np):
-        src = np.ascontiguousarray(src_np, dtype=np.uint8)
-        assert src.shape == self.src_shape, (src.shape, self.src_shape)
-        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
-        _check(lib().dfx_dwconv_submit_host(self._h, _p(src), _p(dst)))
-        return dst
-
-    def info(self):
-        i = DwConvInfo()
-        _check(lib().dfx_dwconv_query(self._h, ctypes.byref(i)))
-        return i
-
-    def requant(self):
-        """requant route as set_weights proved it (dfx_debug_dwconv_requant): ROUTE_EXACT or ROUTE_FAST"""
-        v = (ctypes.c_int32 * 1)()
-        _check(lib().dfx_debug_dwconv_requant(self._h, v))
-        return v[0]
-
-    def close(self):
-        if self._h:
-            lib().dfx_dwconv_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class GroupConv:
+class GroupConv(_Handle):
     """dfx_gconv_* handle: grouped int8 conv over NHWC u8 (include/dfx.h), weights plain oihw {oc, ic/groups, kh, kw}.
     Where ic and oc are multiples of 16 and the output size is the conv's, the result equals the unfused Conv on
     block-diagonal weights bit for bit.  out_hw defaults to the conv's (in + 2 * pad - k) // stride + 1; give it for
     windows that hang over the bottom / right edge."""
+
+    _OP, _INFO, _ROUTES = "dfx_gconv", GConvInfo, 1
 
     def __init__(self, src_shape_nhwc, oc, groups, kernel, stride=(1, 1), pad=(1, 1), out_hw=None, dst_dt=DFX_U8,
                  bia_dt=DFX_UNDEF, relu=False, rm=ROUND_NEAREST, nscales=1, force_path=GCONV_AUTO):
         bs, ih, iw, ic = src_shape_nhwc
         kh, kw = kernel
         if out_hw is None:
-            out_hw = ((ih + 2 * pad[0] - kh) // stride[0] + 1, (iw + 2 * pad[1] - kw) // stride[1] + 1)
+            out_hw = _conv_out_hw(ih, iw, kernel, stride, pad)
         d = GConvDesc(bs, ic, ih, iw, oc, out_hw[0], out_hw[1], groups, kh, kw, stride[0], stride[1], pad[0], pad[1],
                       dst_dt, bia_dt, int(relu), rm, nscales, force_path)
         self.desc = d
         self.src_shape = (bs, ih, iw, ic)
         self.dst_shape = (bs, out_hw[0], out_hw[1], oc)
         self.dst_np_dtype = _NP.get(dst_dt)
-        self._h = ctypes.c_void_p()
-        _check(lib().dfx_gconv_create(ctypes.byref(d), ctypes.byref(self._h)))
+        self._create(d)
 
     def set_weights(self, wei, scales, bia=None):
         """wei: int8 {oc, ic/groups, kh, kw}; scales: 1 or oc floats; bia: oc entries of the descriptor's bias dtype"""
@@ -621,44 +545,13 @@ class GroupConv:
         assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
         _check(lib().dfx_gconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
 
-    def submit(self, src_dev, dst_dev, stream=None):
-        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers), 16-byte aligned"""
-        _check(lib().dfx_gconv_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
 
-    def submit_host(self, src_np):
-        src = np.ascontiguousarray(src_np, dtype=np.uint8)
-        assert src.shape == self.src_shape, (src.shape, self.src_shape)
-        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
-        _check(lib().dfx_gconv_submit_host(self._h, _p(src), _p(dst)))
-        return dst
-
-    def info(self):
-        i = GConvInfo()
-        _check(lib().dfx_gconv_query(self._h, ctypes.byref(i)))
-        return i
-
-    def requant(self):
-        """requant route as set_weights proved it (dfx_debug_gconv_requant): ROUTE_EXACT or ROUTE_FAST"""
-        v = (ctypes.c_int32 * 1)()
-        _check(lib().dfx_debug_gconv_requant(self._h, v))
-        return v[0]
-
-    def close(self):
-        if self._h:
-            lib().dfx_gconv_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DwPwConv:
+class DwPwConv(_Handle):
     """dfx_dwpw_* handle: depthwise conv (dst u8) + pointwise 1x1 conv over NHWC u8, the tensor between the two kept on
     chip on the fused path (include/dfx.h).  The result equals DwConv (u8) followed by the unfused 1x1 Conv bit for bit.
     out_hw defaults to the conv's (in + 2 * pad - k) // stride + 1."""
+
+    _OP, _INFO, _ROUTES = "dfx_dwpw", DwPwInfo, 2
 
     def __init__(self, src_shape_nhwc, kernel, oc, stride=(1, 1), pad=(1, 1), out_hw=None, dst_dt=DFX_U8, bia0_dt=DFX_UNDEF,
                  bia1_dt=DFX_UNDEF, relu=False, rm0=ROUND_NEAREST, rm1=ROUND_NEAREST, nscales0=1, nscales1=1,
@@ -666,15 +559,14 @@ class DwPwConv:
         bs, ih, iw, c = src_shape_nhwc
         kh, kw = kernel
         if out_hw is None:
-            out_hw = ((ih + 2 * pad[0] - kh) // stride[0] + 1, (iw + 2 * pad[1] - kw) // stride[1] + 1)
+            out_hw = _conv_out_hw(ih, iw, kernel, stride, pad)
         d = DwPwDesc(bs, c, ih, iw, out_hw[0], out_hw[1], kh, kw, stride[0], stride[1], pad[0], pad[1], oc, dst_dt,
                      bia0_dt, bia1_dt, int(relu), rm0, rm1, nscales0, nscales1, force_path)
         self.desc = d
         self.src_shape = (bs, ih, iw, c)
         self.dst_shape = (bs, out_hw[0], out_hw[1], oc)
         self.dst_np_dtype = _NP.get(dst_dt)
-        self._h = ctypes.c_void_p()
-        _check(lib().dfx_dwpw_create(ctypes.byref(d), ctypes.byref(self._h)))
+        self._create(d)
 
     def set_weights(self, wei_dw, scales0, wei_pw_blk, scales1, bia0=None, bia1=None):
         """wei_dw: int8 {c, kh, kw}; wei_pw_blk: {oc, c, 1, 1} in OIhw4i16o4i order (reorder_oihw_to_blocked)"""
@@ -686,42 +578,11 @@ class DwPwConv:
         assert (bia0 is None or ws[1].size == self.desc.c) and (bia1 is None or ws[4].size == self.desc.oc)
         _check(lib().dfx_dwpw_set_weights(self._h, *[_p(w) for w in ws]))
 
-    def submit(self, src_dev, dst_dev, stream=None):
-        """asynchronous; src_dev / dst_dev are torch CUDA tensors (or raw pointers), 16-byte aligned"""
-        _check(lib().dfx_dwpw_submit(self._h, _dev_ptr(src_dev), _dev_ptr(dst_dev), _stream_ptr(stream)))
 
-    def submit_host(self, src_np):
-        src = np.ascontiguousarray(src_np, dtype=np.uint8)
-        assert src.shape == self.src_shape, (src.shape, self.src_shape)
-        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
-        _check(lib().dfx_dwpw_submit_host(self._h, _p(src), _p(dst)))
-        return dst
-
-    def info(self):
-        i = DwPwInfo()
-        _check(lib().dfx_dwpw_query(self._h, ctypes.byref(i)))
-        return i
-
-    def requant(self):
-        """requant routes of stage 0 and stage 1 as set_weights proved them (dfx_debug_dwpw_requant)"""
-        v = (ctypes.c_int32 * 2)()
-        _check(lib().dfx_debug_dwpw_requant(self._h, v))
-        return (v[0], v[1])
-
-    def close(self):
-        if self._h:
-            lib().dfx_dwpw_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Concat:
+class Concat(_Handle):
     """dfx_concat_* handle: the op_concat<T> of the reference (src/op_concat.h:28-61)."""
+
+    _OP = "dfx_concat"
 
     def __init__(self, bs, h, w, channels, np_dtype, post_relu=False):
         self.channels = list(channels)
@@ -729,11 +590,10 @@ class Concat:
         d = ConcatDesc(len(channels), bs, h, w, _DT[np.dtype(np_dtype)], int(post_relu), self._ch)
         self.np_dtype = np.dtype(np_dtype)
         self.dst_shape = (bs, h, w, sum(channels))
-        self._h = ctypes.c_void_p()
-        _check(lib().dfx_concat_create(ctypes.byref(d), ctypes.byref(self._h)))
+        self._create(d)
 
     def submit(self, srcs_dev, dst_dev, stream=None):
-        ptrs = (ctypes.c_void_p * len(srcs_dev))(*[_dev_ptr(s).value for s in srcs_dev])
+        ptrs = _ptr_array(srcs_dev, lambda t: _dev_ptr(t).value)
         _check(lib().dfx_concat_submit(self._h, ptrs, _dev_ptr(dst_dev), _stream_ptr(stream)))
 
     def submit_gathered(self, gathered_dev, offsets, dst_dev, stream=None):
@@ -743,18 +603,6 @@ class Concat:
 
     def submit_host(self, srcs_np):
         srcs = [np.ascontiguousarray(s, dtype=self.np_dtype) for s in srcs_np]
-        ptrs = (ctypes.c_void_p * len(srcs))(*[s.ctypes.data for s in srcs])
         dst = np.empty(self.dst_shape, dtype=self.np_dtype)
-        _check(lib().dfx_concat_submit_host(self._h, ptrs, _p(dst)))
+        _check(lib().dfx_concat_submit_host(self._h, _ptr_array(srcs, lambda a: a.ctypes.data), _p(dst)))
         return dst
-
-    def close(self):
-        if self._h:
-            lib().dfx_concat_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

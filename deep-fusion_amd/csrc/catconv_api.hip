@@ -24,33 +24,21 @@ using namespace dfx;
 struct dfx_catconv {
   dfx_catconv_desc d;
   std::vector<int> channels;
-  int device;
-  int ic;
-  long long px;
-  int path;
-  dfx_conv_t *conv;      // the equivalent pointwise conv: owns weights, constants, proofs (both paths)
-  bool weights_set;
+  int device = -1;
+  int ic = 0;
+  long long px = 0;
+  int path = 0;
+  dfx_conv_t *conv = nullptr;  // the equivalent pointwise conv: owns weights, constants, proofs (both paths)
+  bool weights_set = false;
   // fused path
-  int grid, lds;
+  int grid = 0, lds = 0;
   unsigned short kb_src[CAT_MAX_KB], kb_off[CAT_MAX_KB];  // k-block -> branch, byte offset inside its pixel row
   // two-launch path
-  dfx_concat_t *concat;
-  void *d_cat;           // the concatenated tensor
-  // One buffer, so the two-launch submits are SERIALISED on the device.  Submits on ONE stream are ordered by the
-  // stream and cost nothing extra (an event record behind every submit measured + 3 us per submit).  When a second
-  // stream appears, one event recorded on the first stream stands for everything submitted so far; from then on every
-  // submit records `ev` behind its conv and a submit on another stream than the previous one's first waits for it.
-  std::mutex mu;         // guards d_cat's hand-over and the fields below
-  hipEvent_t ev;
-  hipStream_t first_stream, last_stream;
-  unsigned long long first_serial;  // stream_serial_of(first_stream) at the first submit
-  bool have_last, multi_stream;
-  // dfx_catconv_submit_host
-  std::mutex host_mu;
-  std::vector<void *> d_srcs;
-  void *d_dst;
-  hipStream_t host_stream;
-  char kernel_name[96];
+  dfx_concat_t *concat = nullptr;
+  void *d_cat = nullptr;  // the concatenated tensor: ONE buffer, so the submits are serialised
+  TwoLaunchOrder order;
+  HostStaging host;       // dfx_catconv_submit_host
+  char kernel_name[96] = "";
 };
 
 namespace {
@@ -107,10 +95,8 @@ void release(dfx_catconv *h) {
   if (h->conv) (void)dfx_conv_destroy(h->conv);
   if (h->concat) (void)dfx_concat_destroy(h->concat);
   (void)hipFree(h->d_cat);
-  if (h->ev) (void)hipEventDestroy(h->ev);
-  for (void *p : h->d_srcs) (void)hipFree(p);
-  (void)hipFree(h->d_dst);
-  if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
+  h->order.destroy();
+  h->host.release();
   delete h;
 }
 
@@ -133,14 +119,8 @@ int dfx_catconv_create(const dfx_catconv_desc *desc, dfx_catconv_t **out) {
   h->d = d;
   h->channels.assign(d.channels, d.channels + d.n_inputs);
   h->d.channels = h->channels.data();
-  h->device = -1;
   h->ic = (int)ic;
   h->px = (long long)d.bs * d.h * d.w;
-  h->conv = nullptr; h->concat = nullptr; h->d_cat = nullptr; h->ev = nullptr;
-  h->first_stream = h->last_stream = nullptr; h->first_serial = 0;
-  h->have_last = h->multi_stream = false; h->weights_set = false;
-  h->d_dst = nullptr; h->host_stream = nullptr;
-  h->grid = h->lds = 0;
   // whatever dfx_conv_create rejects for the equivalent pointwise conv is rejected here (before it touches a device)
   const dfx_conv_desc cd = equivalent_conv(d, h->ic);
   rc = dfx_conv_create(&cd, &h->conv);
@@ -190,7 +170,7 @@ int dfx_catconv_create(const dfx_catconv_desc *desc, dfx_catconv_t **out) {
     rc = dfx_concat_create(&cc, &h->concat);
     if (rc) { release(h); return rc; }
     hipError_t e = hipMalloc(&h->d_cat, (size_t)h->px * h->ic);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = h->order.create();
     if (e != hipSuccess) {
       release(h);
       return fail(DFX_ERR_HIP, "catconv_create: buffer of the concatenated tensor: %s", hipGetErrorString(e));
@@ -242,32 +222,15 @@ int dfx_catconv_submit(dfx_catconv_t *h, const void *const *srcs_dev, void *dst_
     HIP_TRY(hipGetLastError());
     return DFX_OK;
   }
-  // two launches through the handle's one buffer: serialised (dfx.h)
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->have_last) {
-    h->first_stream = st;
-    h->first_serial = stream_serial_of(st);
-  } else if (!h->multi_stream && st != h->first_stream) {
-    h->multi_stream = true;
-    // (a first stream of dfx_stream_create's that dfx_stream_destroy has destroyed since must not be touched)
-    const bool gone = h->first_serial != 0 && stream_serial_of(h->first_stream) != h->first_serial;
-    hipError_t r = gone ? hipErrorContextIsDestroyed : hipEventRecord(h->ev, h->first_stream);
-    if (r == hipSuccess) r = hipStreamWaitEvent(st, h->ev, 0);
-    if (r != hipSuccess) {  // nothing to record on: wait for the device instead
-      if (!gone) (void)hipGetLastError();
-      HIP_TRY(hipDeviceSynchronize());
-    }
-  } else if (h->multi_stream && st != h->last_stream) {
-    HIP_TRY(hipStreamWaitEvent(st, h->ev, 0));
-  }
-  int rc = dfx_concat_submit(h->concat, srcs_dev, h->d_cat, s);
+  // two launches through the handle's one buffer: serialised (dfx.h; TwoLaunchOrder in dfx_internal.h)
+  std::lock_guard<std::mutex> lk(h->order.mu);
+  int rc = h->order.enter(st);
+  if (rc) return rc;
+  rc = dfx_concat_submit(h->concat, srcs_dev, h->d_cat, s);
   if (rc) return rc;
   rc = dfx_conv_submit(h->conv, h->d_cat, dst_dev, s);
   if (rc) return rc;
-  if (h->multi_stream) HIP_TRY(hipEventRecord(h->ev, st));
-  h->last_stream = st;
-  h->have_last = true;
-  return DFX_OK;
+  return h->order.leave(st);
 }
 
 int dfx_catconv_submit_host(dfx_catconv_t *h, const void *const *srcs_host, void *dst_host) {
@@ -276,20 +239,10 @@ int dfx_catconv_submit_host(dfx_catconv_t *h, const void *const *srcs_host, void
     if (!srcs_host[i]) return fail(DFX_ERR_INVALID, "catconv_submit_host: null input %d", i);
   if (!h->weights_set) return fail(DFX_ERR_STATE, "catconv_submit_host: dfx_catconv_set_weights not called");
   DeviceGuard dg(h->device);
-  std::lock_guard<std::mutex> lk(h->host_mu);
-  if (h->d_srcs.empty()) {
-    h->d_srcs.resize(h->d.n_inputs, nullptr);
-    for (int i = 0; i < h->d.n_inputs; ++i) HIP_TRY(hipMalloc(&h->d_srcs[i], (size_t)h->px * h->channels[i]));
-    HIP_TRY(hipMalloc(&h->d_dst, dst_bytes(h)));
-    HIP_TRY(hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking));
-  }
-  for (int i = 0; i < h->d.n_inputs; ++i)
-    HIP_TRY(hipMemcpyAsync(h->d_srcs[i], srcs_host[i], (size_t)h->px * h->channels[i], hipMemcpyHostToDevice, h->host_stream));
-  int rc = dfx_catconv_submit(h, (const void *const *)h->d_srcs.data(), h->d_dst, h->host_stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(dst_host, h->d_dst, dst_bytes(h), hipMemcpyDeviceToHost, h->host_stream));
-  HIP_TRY(hipStreamSynchronize(h->host_stream));
-  return DFX_OK;
+  std::vector<size_t> sb;
+  for (int c : h->channels) sb.push_back((size_t)h->px * c);
+  return h->host.run(h->d.n_inputs, srcs_host, sb.data(), dst_host, dst_bytes(h),
+                     [h](const void *const *s, void *d, dfx_stream_t st) { return dfx_catconv_submit(h, s, d, st); });
 }
 
 int dfx_catconv_query(const dfx_catconv_t *h, dfx_catconv_info *info) {

@@ -30,6 +30,7 @@
 #include "conv_mfma_roles.cuh"
 #include "dfx_device.cuh"
 #include "dfx_internal.h"
+#include "requant_host.h"
 
 namespace dfx {
 int launch_conv_generic(const ConvArgs &a, hipStream_t s, int *grid_out, int *lds_out);
@@ -179,8 +180,7 @@ struct dfx_conv {
   int *trace_host;  // DFX_TRACE builds only
   unsigned long long *d_prof;  // DFX_STAMPS builds only
   bool weights_set;
-  void *d_src, *d_dst;  // lazily allocated for dfx_conv_submit_host
-  hipStream_t host_stream;
+  HostStaging host;  // dfx_conv_submit_host
   char kernel_name[96];
 };
 
@@ -189,9 +189,7 @@ struct dfx_concat {
   dfx_concat_desc d;
   std::vector<int> channels;
   ConcatArgs args;
-  std::vector<void *> d_srcs;  // lazily allocated for submit_host
-  void *d_dst;
-  hipStream_t host_stream;
+  HostStaging host;  // dfx_concat_submit_host
 };
 
 extern "C" {
@@ -361,7 +359,6 @@ static int validate_conv(const dfx_conv_desc &d) {
   return DFX_OK;
 }
 
-static size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // Pick the unit decomposition of the MFMA variant: TH output rows x TW output
 // columns per unit, either full-width rows (linear pixel numbering) or TW a
@@ -734,9 +731,9 @@ static int mfma_dispatch(dfx_conv *h, const ConvArgs &a, const MfmaGeom &g, hipS
 static void conv_release(dfx_conv *h) {
   if (!h) return;
   DeviceGuard dg(h->device);
-  if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
+  h->host.release();
   (void)hipFree(h->d_wei); (void)hipFree(h->d_wei1); (void)hipFree(h->d_consts);
-  (void)hipFree(h->d_src); (void)hipFree(h->d_dst); (void)hipFree(h->d_queue);
+  (void)hipFree(h->d_queue);
   (void)hipFree(h->d_prof);
   for (unsigned i = 0; i < DFX_QUEUE_RING; ++i)
     if (h->slot_ev[i] && h->slot_ev[i] != h->first_ev) (void)hipEventDestroy(h->slot_ev[i]);
@@ -756,9 +753,8 @@ int dfx_conv_create(const dfx_conv_desc *desc, dfx_conv_t **out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(DFX_ERR_NO_DEVICE, "conv_create: no HIP device (this library has no CPU path)");
 
-  dfx_conv *h = new (std::nothrow) dfx_conv();
+  dfx_conv *h = new (std::nothrow) dfx_conv();  // (value-initialised: every plain field starts as zero)
   if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  memset(static_cast<void *>(h), 0, sizeof(*h));
   h->d = *desc;
   if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   const dfx_conv_desc &d = h->d;
@@ -1132,16 +1128,6 @@ int dfx_conv_create(const dfx_conv_desc *desc, dfx_conv_t **out) {
   return DFX_OK;
 }
 
-static float bias_to_f32(const void *b, int dt, int c) {
-  switch (dt) {  // vcvtdq2ps after vpmovsxbd / vpmovzxbd / vmovups, jit_conv_kernel.cc:235-255
-    case DFX_F32: return ((const float *)b)[c];
-    case DFX_S32: return (float)((const int32_t *)b)[c];
-    case DFX_S8: return (float)((const int8_t *)b)[c];
-    case DFX_U8: return (float)((const uint8_t *)b)[c];
-  }
-  return 0.0f;
-}
-
 // One channel's precondition of the fast requant path (conv_mfma.cuh store_group<FAST>):
 // amax bounds |true accumulator|; comp + bias must fold into ONE exact f32 add (bias
 // integer-valued, |comp + bias| < 2^24, |acc + bias| < 2^24) and nothing may reach +-2^31.
@@ -1152,6 +1138,57 @@ static bool fast_ok_channel(double amax, double comp, float bias, float scale) {
   const double lim = 16777216.0;  // 2^24
   if (std::fabs(comp + b) >= lim || amax + std::fabs(b) >= lim || std::fabs(comp) + amax >= lim) return false;
   return (amax + std::fabs(b)) * std::fabs((double)scale) * 1.0001 + 2.0 < 2147480000.0;
+}
+
+// The constants of conv_stream.cuh and conv_direct.cuh: comp0 (s32) bias0 scale0 [OCP each] comp1 (s32) bias1 scale1
+// [OC1P each]; padding channels are all-zero (their intermediate is 0 and meets zero 1x1 weights).  fb0 / fb1: the
+// biases as f32.  Returns whether the fast requant path is proven for every channel of both stages; the bias slots
+// then hold comp + bias.
+static bool stream_consts(const dfx_conv_desc &d, int OCP, int OC1P, const int8_t *wei, const void *bia0, const float *scales0,
+                          const int8_t *wei1, const void *bia1, const float *scales1, std::vector<int32_t> &cst,
+                          std::vector<float> &fb0, std::vector<float> &fb1) {
+  const int OC = d.oc, IC = d.ic, OC1 = d.oc1x1, ntap = d.kh * d.kw;
+  cst.assign((size_t)3 * (OCP + OC1P), 0);
+  auto put_f = [&](size_t idx, float v) { memcpy(&cst[idx], &v, 4); };
+  bool fast = d.conv0_round_mode == DFX_ROUND_NEAREST && (OC1 == 0 || d.conv1_round_mode == DFX_ROUND_NEAREST);
+  fb0.assign(OC, 0.0f);
+  fb1.assign(OC1 ? OC1 : 1, 0.0f);
+  for (int c = 0; c < OC; ++c) {
+    int32_t sum = 0, pos = 0, neg = 0;
+    for (int ic = 0; ic < IC; ++ic)
+      for (int tap = 0; tap < ntap; ++tap) {
+        const int w = wei[dfx_blocked_offset(c, ic, tap / d.kw, tap % d.kw, IC, d.kh, d.kw)];
+        sum += w;
+        (w > 0 ? pos : neg) += w;
+      }
+    cst[c] = 128 * sum;
+    fb0[c] = d.bia0_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia0, d.bia0_dt, c);
+    const float sc = scales0[d.conv0_nscales > 1 ? c : 0];
+    put_f((size_t)OCP + c, fb0[c]);
+    put_f((size_t)2 * OCP + c, sc);
+    fast = fast && fast_ok_channel(255.0 * std::max(pos, -neg), 128.0 * sum, fb0[c], sc);
+  }
+  for (int c = 0; c < OC1; ++c) {
+    int32_t sum = 0, pos = 0, neg = 0;
+    for (int oc = 0; oc < OC; ++oc) {
+      const int w = wei1[dfx_blocked_offset(c, oc, 0, 0, OC, 1, 1)];
+      sum += w;
+      (w > 0 ? pos : neg) += w;
+    }
+    cst[(size_t)3 * OCP + c] = 128 * sum;
+    fb1[c] = d.bia1_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia1, d.bia1_dt, c);
+    const float sc = scales1[d.conv1_nscales > 1 ? c : 0];
+    put_f((size_t)3 * OCP + OC1P + c, fb1[c]);
+    put_f((size_t)3 * OCP + 2 * OC1P + c, sc);
+    fast = fast && fast_ok_channel(255.0 * std::max(pos, -neg), 128.0 * sum, fb1[c], sc);
+  }
+  fast = fast && fast_allowed();
+  if (fast) {  // the fast path reads comp + bias (an exact f32) from the bias slot
+    for (int c = 0; c < OC; ++c) put_f((size_t)OCP + c, (float)((double)cst[c] + (double)fb0[c]));
+    for (int c = 0; c < OC1; ++c)
+      put_f((size_t)3 * OCP + OC1P + c, (float)((double)cst[(size_t)3 * OCP + c] + (double)fb1[c]));
+  }
+  return fast;
 }
 
 // Packs weights for conv_stream.cuh: ONE device buffer
@@ -1204,47 +1241,9 @@ static int set_weights_stream(dfx_conv_t *h, const int8_t *wei, const void *bia0
               const int oc = 32 * blk + 8 * (b >> 2) + 4 * (lane >> 5) + (b & 3);  // mid's k order
               if (oc1 < OC1 && oc < OC) pk[o] = wei1[dfx_blocked_offset(oc1, oc, 0, 0, OC, 1, 1)];
             }
-  // consts: comp0 (s32) bias0 scale0 [OCP each] comp1 (s32) bias1 scale1 [OC1P each]; padding
-  // channels are all-zero (their intermediate is 0 and meets zero 1x1 weights)
-  std::vector<int32_t> cst((size_t)3 * (OCP + OC1P), 0);
-  auto put_f = [&](size_t idx, float v) { memcpy(&cst[idx], &v, 4); };
-  bool fast = d.conv0_round_mode == DFX_ROUND_NEAREST && (!fused || d.conv1_round_mode == DFX_ROUND_NEAREST);
-  std::vector<float> fb0(OC), fb1(OC1 ? OC1 : 1);  // bias as f32
-  for (int c = 0; c < OC; ++c) {
-    int32_t sum = 0, pos = 0, neg = 0;
-    for (int ic = 0; ic < IC; ++ic)
-      for (int tap = 0; tap < ntap; ++tap) {
-        const int w = wei[dfx_blocked_offset(c, ic, tap / d.kw, tap % d.kw, IC, d.kh, d.kw)];
-        sum += w;
-        (w > 0 ? pos : neg) += w;
-      }
-    cst[c] = 128 * sum;
-    fb0[c] = d.bia0_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia0, d.bia0_dt, c);
-    const float sc = scales0[d.conv0_nscales > 1 ? c : 0];
-    put_f((size_t)OCP + c, fb0[c]);
-    put_f((size_t)2 * OCP + c, sc);
-    fast = fast && fast_ok_channel(255.0 * std::max(pos, -neg), 128.0 * sum, fb0[c], sc);
-  }
-  for (int c = 0; c < OC1; ++c) {
-    int32_t sum = 0, pos = 0, neg = 0;
-    for (int oc = 0; oc < OC; ++oc) {
-      const int w = wei1[dfx_blocked_offset(c, oc, 0, 0, OC, 1, 1)];
-      sum += w;
-      (w > 0 ? pos : neg) += w;
-    }
-    cst[(size_t)3 * OCP + c] = 128 * sum;
-    fb1[c] = d.bia1_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia1, d.bia1_dt, c);
-    const float sc = scales1[d.conv1_nscales > 1 ? c : 0];
-    put_f((size_t)3 * OCP + OC1P + c, fb1[c]);
-    put_f((size_t)3 * OCP + 2 * OC1P + c, sc);
-    fast = fast && fast_ok_channel(255.0 * std::max(pos, -neg), 128.0 * sum, fb1[c], sc);
-  }
-  if (const char *e = tune("DFX_NO_FAST")) fast = fast && atoi(e) == 0;  // testing aid: force the exact path
-  if (fast) {  // the fast path reads comp + bias (an exact f32) from the bias slot
-    for (int c = 0; c < OC; ++c) put_f((size_t)OCP + c, (float)((double)cst[c] + (double)fb0[c]));
-    for (int c = 0; c < OC1; ++c)
-      put_f((size_t)3 * OCP + OC1P + c, (float)((double)cst[(size_t)3 * OCP + c] + (double)fb1[c]));
-  }
+  std::vector<int32_t> cst;
+  std::vector<float> fb0, fb1;
+  const bool fast = stream_consts(d, OCP, OC1P, wei, bia0, scales0, wei1, bia1, scales1, cst, fb0, fb1);
   h->sgeom.fast = fast ? 1 : 0;
   if (!h->d_wei) HIP_TRY(hipMalloc(&h->d_wei, pk.size() + cst.size() * 4));
   char *base = (char *)h->d_wei;
@@ -1288,45 +1287,10 @@ static int set_weights_direct(dfx_conv_t *h, const int8_t *wei, const void *bia0
             if (oc1 < OC1 && oc < OC) pk[o] = wei1[dfx_blocked_offset(oc1, oc, 0, 0, OC, 1, 1)];
           }
   if (o != n0 + n1) return fail(DFX_ERR_HIP, "internal: direct pack size mismatch");
-  std::vector<int32_t> cst((size_t)3 * (OCP + OC1P), 0);
+  std::vector<int32_t> cst;
+  std::vector<float> fb0, fb1;
+  const bool fast = stream_consts(d, OCP, OC1P, wei, bia0, scales0, wei1, bia1, scales1, cst, fb0, fb1);
   auto put_f = [&](size_t idx, float v) { memcpy(&cst[idx], &v, 4); };
-  bool fast = d.conv0_round_mode == DFX_ROUND_NEAREST && (OC1 == 0 || d.conv1_round_mode == DFX_ROUND_NEAREST);
-  std::vector<float> fb0(OC), fb1(OC1 ? OC1 : 1);
-  for (int c = 0; c < OC; ++c) {
-    int32_t sum = 0, pos = 0, neg = 0;
-    for (int ic = 0; ic < IC; ++ic)
-      for (int tap = 0; tap < ntap; ++tap) {
-        const int w = wei[dfx_blocked_offset(c, ic, tap / d.kw, tap % d.kw, IC, d.kh, d.kw)];
-        sum += w;
-        (w > 0 ? pos : neg) += w;
-      }
-    cst[c] = 128 * sum;
-    fb0[c] = d.bia0_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia0, d.bia0_dt, c);
-    const float sc = scales0[d.conv0_nscales > 1 ? c : 0];
-    put_f((size_t)OCP + c, fb0[c]);
-    put_f((size_t)2 * OCP + c, sc);
-    fast = fast && fast_ok_channel(255.0 * std::max(pos, -neg), 128.0 * sum, fb0[c], sc);
-  }
-  for (int c = 0; c < OC1; ++c) {
-    int32_t sum = 0, pos = 0, neg = 0;
-    for (int oc = 0; oc < OC; ++oc) {
-      const int w = wei1[dfx_blocked_offset(c, oc, 0, 0, OC, 1, 1)];
-      sum += w;
-      (w > 0 ? pos : neg) += w;
-    }
-    cst[(size_t)3 * OCP + c] = 128 * sum;
-    fb1[c] = d.bia1_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia1, d.bia1_dt, c);
-    const float sc = scales1[d.conv1_nscales > 1 ? c : 0];
-    put_f((size_t)3 * OCP + OC1P + c, fb1[c]);
-    put_f((size_t)3 * OCP + 2 * OC1P + c, sc);
-    fast = fast && fast_ok_channel(255.0 * std::max(pos, -neg), 128.0 * sum, fb1[c], sc);
-  }
-  if (const char *e = tune("DFX_NO_FAST")) fast = fast && atoi(e) == 0;  // testing aid: force the exact path
-  if (fast) {  // the fast path reads comp + bias (an exact f32) from the bias slot
-    for (int c = 0; c < OC; ++c) put_f((size_t)OCP + c, (float)((double)cst[c] + (double)fb0[c]));
-    for (int c = 0; c < OC1; ++c)
-      put_f((size_t)3 * OCP + OC1P + c, (float)((double)cst[(size_t)3 * OCP + c] + (double)fb1[c]));
-  }
   h->dgeom.fast = fast ? 1 : 0;
   // Requant without int -> float conversions (conv_direct.cuh, round 3), proven per channel from the actual
   // weights like the modes of the resident kernels: with activations stored as u8 - 128 the raw accumulator lies
@@ -1738,18 +1702,8 @@ static size_t conv_dst_bytes(const dfx_conv_desc &d) {
 int dfx_conv_submit_host(dfx_conv_t *h, const void *src_host, void *dst_host) {
   if (!h || !src_host || !dst_host) return fail(DFX_ERR_INVALID, "conv_submit_host: null argument");
   DeviceGuard dg(h->device);
-  const size_t sb = conv_src_bytes(h->d), db = conv_dst_bytes(h->d);
-  if (!h->d_src) {
-    HIP_TRY(hipMalloc(&h->d_src, sb));
-    HIP_TRY(hipMalloc(&h->d_dst, db));
-    HIP_TRY(hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking));
-  }
-  HIP_TRY(hipMemcpyAsync(h->d_src, src_host, sb, hipMemcpyHostToDevice, h->host_stream));
-  int rc = dfx_conv_submit(h, h->d_src, h->d_dst, h->host_stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(dst_host, h->d_dst, db, hipMemcpyDeviceToHost, h->host_stream));
-  HIP_TRY(hipStreamSynchronize(h->host_stream));
-  return DFX_OK;
+  return h->host.run(src_host, conv_src_bytes(h->d), dst_host, conv_dst_bytes(h->d),
+                     [h](const void *s, void *d, dfx_stream_t st) { return dfx_conv_submit(h, s, d, st); });
 }
 
 int dfx_conv_query(const dfx_conv_t *h, dfx_conv_info *info) {
@@ -1878,8 +1832,6 @@ int dfx_concat_create(const dfx_concat_desc *desc, dfx_concat_t **out) {
   if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   h->channels.assign(d.channels, d.channels + d.n_inputs);
   h->d.channels = h->channels.data();
-  h->d_dst = nullptr;
-  h->host_stream = nullptr;
   ConcatArgs &a = h->args;
   memset(&a, 0, sizeof(a));
   const int per_chunk = 16 / (int)dt_size(d.dt);
@@ -1933,29 +1885,19 @@ int dfx_concat_submit_host(dfx_concat_t *h, const void *const *srcs_host, void *
   DeviceGuard dg(h->device);
   const size_t px = (size_t)h->d.bs * h->d.h * h->d.w, es = dt_size(h->d.dt);
   size_t oc = 0;
-  for (int c : h->channels) oc += c;
-  if (h->d_srcs.empty()) {
-    h->d_srcs.resize(h->d.n_inputs, nullptr);
-    for (int i = 0; i < h->d.n_inputs; ++i) HIP_TRY(hipMalloc(&h->d_srcs[i], px * h->channels[i] * es));
-    HIP_TRY(hipMalloc(&h->d_dst, px * oc * es));
-    HIP_TRY(hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking));
+  std::vector<size_t> sb;
+  for (int c : h->channels) {
+    oc += c;
+    sb.push_back(px * c * es);
   }
-  for (int i = 0; i < h->d.n_inputs; ++i)
-    HIP_TRY(hipMemcpyAsync(h->d_srcs[i], srcs_host[i], px * h->channels[i] * es, hipMemcpyHostToDevice,
-                           h->host_stream));
-  int rc = dfx_concat_submit(h, (const void *const *)h->d_srcs.data(), h->d_dst, h->host_stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(dst_host, h->d_dst, px * oc * es, hipMemcpyDeviceToHost, h->host_stream));
-  HIP_TRY(hipStreamSynchronize(h->host_stream));
-  return DFX_OK;
+  return h->host.run(h->d.n_inputs, srcs_host, sb.data(), dst_host, px * oc * es,
+                     [h](const void *const *s, void *d, dfx_stream_t st) { return dfx_concat_submit(h, s, d, st); });
 }
 
 int dfx_concat_destroy(dfx_concat_t *h) {
   if (!h) return DFX_OK;
   DeviceGuard dg(h->device);
-  for (void *p : h->d_srcs) (void)hipFree(p);
-  (void)hipFree(h->d_dst);
-  if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
+  h->host.release();
   delete h;
   return DFX_OK;
 }

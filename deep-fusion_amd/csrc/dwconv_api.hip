@@ -4,16 +4,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <new>
 #include <vector>
 
 #include "dfx_internal.h"
 #include "dwconv.cuh"
+#include "requant_host.h"
 
 namespace dfx {
 int launch_dwconv_window(const DwArgs &, int grid, int block, int lds, hipStream_t);
@@ -23,19 +22,16 @@ using namespace dfx;
 
 struct dfx_dwconv {
   dfx_dwconv_desc d;
-  int device;
-  int path;
-  int grid, block, lds;
-  DwArgs args;           // everything but src / dst; copied per launch
-  unsigned char *d_buf;  // packed weights | raw weights | comp | bias | scale
-  size_t off_wraw, off_comp, off_bias, off_scale, buf_bytes;
-  bool weights_set;
-  int route;             // 0 exact, 1 fast (dfx_debug_conv_requant's numbering)
-  // dfx_dwconv_submit_host
-  std::mutex host_mu;
-  void *d_src, *d_dst;
-  hipStream_t host_stream;
-  char kernel_name[96];
+  int device = 0;
+  int path = 0;
+  int grid = 0, block = 0, lds = 0;
+  DwArgs args = {};                // everything but src / dst; copied per launch
+  unsigned char *d_buf = nullptr;  // packed weights | raw weights | comp | bias | scale
+  size_t off_wraw = 0, off_comp = 0, off_bias = 0, off_scale = 0, buf_bytes = 0;
+  bool weights_set = false;
+  int route = 0;                   // 0 exact, 1 fast (dfx_debug_conv_requant's numbering)
+  HostStaging host;                // dfx_dwconv_submit_host
+  char kernel_name[96] = "";
 };
 
 namespace {
@@ -67,28 +63,6 @@ bool window_class(const dfx_dwconv_desc &d) {
          (long long)d.ih * d.iw * d.c < lim && (long long)d.oh * d.ow * d.c * (long long)dt_size(d.dst_dt) < lim;
 }
 
-float bias_as_f32(const void *b, int dt, int c) {  // the conv's bias_to_f32 (vcvtdq2ps after the widening move)
-  switch (dt) {
-    case DFX_F32: return ((const float *)b)[c];
-    case DFX_S32: return (float)((const int32_t *)b)[c];
-    case DFX_S8: return (float)((const int8_t *)b)[c];
-    case DFX_U8: return (float)((const uint8_t *)b)[c];
-  }
-  return 0.0f;
-}
-
-// One channel's precondition of the fast requant route (dwconv.cuh dw_store<FAST>).  The accumulator is exact on
-// both routes (integer dot products, the compensation is an integer start value) and so are the add and the
-// multiply; only the conversion differs.  amax = 255 * max(P, N) bounds |acc|.  With bias and scale finite the f32
-// result is within a relative 2^-22 of (acc + bias) * scale, so a bound of 2^30 keeps everything far from +-2^31,
-// where the hardware conversions (saturating) and vcvtps2dq (0x80000000) part ways; no NaN can arise.
-bool dw_fast_ok_channel(double amax, float bias, float scale) {
-  if (!std::isfinite(bias) || !std::isfinite(scale)) return false;
-  return (amax + std::fabs((double)bias)) * std::fabs((double)scale) <= 1073741824.0;  // 2^30
-}
-
-const char *dt_name(int dt) { return dt == DFX_F32 ? "f32" : dt == DFX_S32 ? "s32" : dt == DFX_S8 ? "s8" : "u8"; }
-
 void set_name(dfx_dwconv *h) {
   const dfx_dwconv_desc &d = h->d;
   if (h->path == DFX_DWCONV_WINDOW)
@@ -103,15 +77,12 @@ void release(dfx_dwconv *h) {
   if (!h) return;
   DeviceGuard dg(h->device);
   (void)hipFree(h->d_buf);
-  (void)hipFree(h->d_src);
-  (void)hipFree(h->d_dst);
-  if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
+  h->host.release();
   delete h;
 }
 
 size_t src_bytes(const dfx_dwconv_desc &d) { return (size_t)d.bs * d.ih * d.iw * d.c; }
 size_t dst_bytes(const dfx_dwconv_desc &d) { return (size_t)d.bs * d.oh * d.ow * d.c * dt_size(d.dst_dt); }
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -140,8 +111,6 @@ int dfx_dwconv_create(const dfx_dwconv_desc *desc, dfx_dwconv_t **out) {
   h->d = d;
   if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   h->path = (covered && d.force_path != DFX_DWCONV_GENERIC) ? DFX_DWCONV_WINDOW : DFX_DWCONV_GENERIC;
-  h->d_buf = nullptr; h->d_src = h->d_dst = nullptr; h->host_stream = nullptr;
-  h->weights_set = false; h->route = 0;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
     release(h);
@@ -149,7 +118,6 @@ int dfx_dwconv_create(const dfx_dwconv_desc *desc, dfx_dwconv_t **out) {
   }
   const int cus = std::max(1, prop.multiProcessorCount);
   DwArgs &a = h->args;
-  memset(&a, 0, sizeof(a));
   a.bs = d.bs; a.c = d.c; a.ih = d.ih; a.iw = d.iw; a.oh = d.oh; a.ow = d.ow; a.kh = d.kh; a.kw = d.kw;
   a.sh = d.sh; a.sw = d.sw; a.pt = d.pad_t; a.pl = d.pad_l;
   a.dst_dt = d.dst_dt; a.relu = (d.relu || d.dst_dt == DFX_U8) ? 1 : 0; a.rm = d.round_mode;
@@ -194,11 +162,11 @@ int dfx_dwconv_create(const dfx_dwconv_desc *desc, dfx_dwconv_t **out) {
     h->lds = 0;
     h->grid = (int)std::min((a.items + 255) / 256, (long long)cus * 8);
   }
-  h->off_wraw = align16(wpk_bytes);
-  h->off_comp = h->off_wraw + align16((size_t)d.c * taps);
-  h->off_bias = h->off_comp + align16((size_t)d.c * 4);
-  h->off_scale = h->off_bias + align16((size_t)d.c * 4);
-  h->buf_bytes = h->off_scale + align16((size_t)d.c * 4);
+  h->off_wraw = round16(wpk_bytes);
+  h->off_comp = h->off_wraw + round16((size_t)d.c * taps);
+  h->off_bias = h->off_comp + round16((size_t)d.c * 4);
+  h->off_scale = h->off_bias + round16((size_t)d.c * 4);
+  h->buf_bytes = h->off_scale + round16((size_t)d.c * 4);
   hipError_t e = hipMalloc((void **)&h->d_buf, h->buf_bytes);
   if (e != hipSuccess) {
     release(h);
@@ -223,19 +191,9 @@ int dfx_dwconv_set_weights(dfx_dwconv_t *h, const int8_t *wei, const void *bia, 
   int *comp = (int *)(img.data() + h->off_comp);
   float *fb = (float *)(img.data() + h->off_bias), *fs = (float *)(img.data() + h->off_scale);
   memcpy(img.data() + h->off_wraw, wei, (size_t)d.c * taps);
-  bool fast = h->path == DFX_DWCONV_WINDOW && d.round_mode == DFX_ROUND_NEAREST;
-  for (int k = 0; k < d.c; ++k) {
-    long long pos = 0, neg = 0;
-    for (int i = 0; i < taps; ++i) {
-      const int v = wei[(size_t)k * taps + i];
-      (v > 0 ? pos : neg) += v;
-    }
-    comp[k] = (int)(128 * (pos + neg));
-    fb[k] = d.bia_dt == DFX_UNDEF ? 0.0f : bias_as_f32(bia, d.bia_dt, k);
-    fs[k] = scales[d.nscales == 1 ? 0 : k];
-    fast = fast && dw_fast_ok_channel(255.0 * (double)std::max(pos, -neg), fb[k], fs[k]);
-  }
-  if (const char *e = tuning_value("DFX_NO_FAST")) fast = fast && atoi(e) == 0;  // testing aid: force the exact route
+  const bool proven = requant_consts(d.c, taps, [&](int k, size_t i) { return wei[(size_t)k * taps + i]; }, bia, d.bia_dt, scales,
+                                     d.nscales, comp, fb, fs);
+  const bool fast = h->path == DFX_DWCONV_WINDOW && d.round_mode == DFX_ROUND_NEAREST && proven && fast_allowed();
   if (h->path == DFX_DWCONV_WINDOW) {
     // [group][ky][dword of the row][channel of the group]: bytes = the row's taps kx = 4 * dword .. + 3, zero past K
     const int K = d.kh, ndw = K == 3 ? 1 : 2;
@@ -280,17 +238,8 @@ int dfx_dwconv_submit_host(dfx_dwconv_t *h, const void *src_host, void *dst_host
   if (!h || !src_host || !dst_host) return fail(DFX_ERR_INVALID, "dwconv_submit_host: null argument");
   if (!h->weights_set) return fail(DFX_ERR_STATE, "dwconv_submit_host: dfx_dwconv_set_weights not called");
   DeviceGuard dg(h->device);
-  std::lock_guard<std::mutex> lk(h->host_mu);
-  // each on its own: a call that failed half way leaves nothing the next one would take for complete
-  if (!h->d_src) HIP_TRY(hipMalloc(&h->d_src, src_bytes(h->d)));
-  if (!h->d_dst) HIP_TRY(hipMalloc(&h->d_dst, dst_bytes(h->d)));
-  if (!h->host_stream) HIP_TRY(hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking));
-  HIP_TRY(hipMemcpyAsync(h->d_src, src_host, src_bytes(h->d), hipMemcpyHostToDevice, h->host_stream));
-  int rc = dfx_dwconv_submit(h, h->d_src, h->d_dst, h->host_stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(dst_host, h->d_dst, dst_bytes(h->d), hipMemcpyDeviceToHost, h->host_stream));
-  HIP_TRY(hipStreamSynchronize(h->host_stream));
-  return DFX_OK;
+  return h->host.run(src_host, src_bytes(h->d), dst_host, dst_bytes(h->d),
+                     [h](const void *s, void *d, dfx_stream_t st) { return dfx_dwconv_submit(h, s, d, st); });
 }
 
 int dfx_dwconv_query(const dfx_dwconv_t *h, dfx_dwconv_info *info) {

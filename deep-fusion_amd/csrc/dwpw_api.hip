@@ -16,6 +16,7 @@
 
 #include "dfx_internal.h"
 #include "dwpw.cuh"
+#include "requant_host.h"
 
 namespace dfx {
 int launch_dwpw(const DwPwArgs &, int stride, int dst_dt, int grid, int lds, hipStream_t, int mode);
@@ -24,29 +25,22 @@ using namespace dfx;
 
 struct dfx_dwpw {
   dfx_dwpw_desc d;
-  int device;
-  int path;
-  dfx_dwconv_t *dw;      // stage 0: owns its weights, constants and proof (both paths); launched on the two-launch path
-  dfx_conv_t *conv;      // two-launch path: the unfused pointwise conv
-  bool weights_set;
-  int route0, route1;
+  int device = -1;
+  int path = 0;
+  dfx_dwconv_t *dw = nullptr;     // stage 0: owns its weights, constants and proof (both paths); launched on the two-launch path
+  dfx_conv_t *conv = nullptr;     // two-launch path: the unfused pointwise conv
+  bool weights_set = false;
+  int route0 = 0, route1 = 0;
   // fused path
-  int grid, lds;
-  DwPwArgs args;         // everything but src / dst; copied per launch
-  unsigned char *d_w1;   // [W0d | comp1 | bias1 | scale1]
-  size_t w1_bytes;
-  // two-launch path: one buffer, so its submits are SERIALISED exactly as catconv_api.hip's (see there)
-  void *d_mid;           // the u8 tensor between the stages
-  std::mutex mu;
-  hipEvent_t ev;
-  hipStream_t first_stream, last_stream;
-  unsigned long long first_serial;
-  bool have_last, multi_stream;
-  // dfx_dwpw_submit_host
-  std::mutex host_mu;
-  void *d_src, *d_dst;
-  hipStream_t host_stream;
-  char kernel_name[96];
+  int grid = 0, lds = 0;
+  DwPwArgs args = {};             // everything but src / dst; copied per launch
+  unsigned char *d_w1 = nullptr;  // [W0d | comp1 | bias1 | scale1]
+  size_t w1_bytes = 0;
+  // two-launch path
+  void *d_mid = nullptr;          // the u8 tensor between the stages: ONE buffer, so the submits are serialised
+  TwoLaunchOrder order;
+  HostStaging host;               // dfx_dwpw_submit_host
+  char kernel_name[96] = "";
 };
 
 namespace {
@@ -132,24 +126,6 @@ Plan lds_plan(const dfx_dwpw_desc &d, int th) {
   return p;
 }
 
-float bias_as_f32(const void *b, int dt, int c) {  // the conv's bias_to_f32
-  switch (dt) {
-    case DFX_F32: return ((const float *)b)[c];
-    case DFX_S32: return (float)((const int32_t *)b)[c];
-    case DFX_S8: return (float)((const int8_t *)b)[c];
-    case DFX_U8: return (float)((const uint8_t *)b)[c];
-  }
-  return 0.0f;
-}
-
-// dwconv_api.hip's clause over one output channel of the pointwise conv: the accumulator (started from the integer
-// compensation) is exact, |acc| <= 255 * max(P, N), and so are the add and the multiply on both routes
-bool fast_ok_channel(double amax, float bias, float scale) {
-  if (!std::isfinite(bias) || !std::isfinite(scale)) return false;
-  return (amax + std::fabs((double)bias)) * std::fabs((double)scale) <= 1073741824.0;  // 2^30
-}
-
-const char *dt_name(int dt) { return dt == DFX_F32 ? "f32" : dt == DFX_S32 ? "s32" : dt == DFX_S8 ? "s8" : "u8"; }
 const char *route_name(int r) { return r == 1 ? "fast" : r == 2 ? "magic" : r == 3 ? "fma" : "exact"; }
 
 void set_name(dfx_dwpw *h) {
@@ -172,10 +148,8 @@ void release(dfx_dwpw *h) {
   if (h->conv) (void)dfx_conv_destroy(h->conv);
   (void)hipFree(h->d_w1);
   (void)hipFree(h->d_mid);
-  if (h->ev) (void)hipEventDestroy(h->ev);
-  (void)hipFree(h->d_src);
-  (void)hipFree(h->d_dst);
-  if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
+  h->order.destroy();
+  h->host.release();
   delete h;
 }
 
@@ -199,15 +173,8 @@ int dfx_dwpw_create(const dfx_dwpw_desc *desc, dfx_dwpw_t **out) {
   dfx_dwpw *h = new (std::nothrow) dfx_dwpw();
   if (!h) return fail(DFX_ERR_HIP, "out of host memory");
   h->d = d;
-  h->device = -1;
   h->path = (covered && (d.force_path == DFX_DWPW_FUSED || (d.force_path == -1 && fused_wins(d)))) ? DFX_DWPW_FUSED
                                                                                                       : DFX_DWPW_TWO_LAUNCH;
-  h->dw = nullptr; h->conv = nullptr; h->weights_set = false; h->route0 = h->route1 = 0;
-  h->grid = h->lds = 0; h->d_w1 = nullptr; h->w1_bytes = 0;
-  h->d_mid = nullptr; h->ev = nullptr; h->first_stream = h->last_stream = nullptr; h->first_serial = 0;
-  h->have_last = h->multi_stream = false;
-  h->d_src = h->d_dst = nullptr; h->host_stream = nullptr;
-  memset(&h->args, 0, sizeof(h->args));
   // whatever dfx_conv_create rejects for the pointwise conv is rejected here (before it touches a device)
   if (h->path == DFX_DWPW_TWO_LAUNCH) {
     const dfx_conv_desc cd = stage1_desc(d);
@@ -277,7 +244,7 @@ int dfx_dwpw_create(const dfx_dwpw_desc *desc, dfx_dwpw_t **out) {
     h->grid = (int)grid;
   } else {
     hipError_t e = hipMalloc(&h->d_mid, mid_bytes(d));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = h->order.create();
     if (e != hipSuccess) {
       release(h);
       return fail(DFX_ERR_HIP, "dwpw_create: buffer of the tensor between the stages: %s", hipGetErrorString(e));
@@ -330,19 +297,10 @@ int dfx_dwpw_set_weights(dfx_dwpw_t *h, const int8_t *wei_dw, const void *bia0, 
           img[o] = (unsigned char)wei_pw[dfx_blocked_offset(32 * ob + (lane & 31), 32 * kb + 16 * (lane >> 5) + b, 0, 0, IC, 1, 1)];
   int32_t *comp = (int32_t *)(img.data() + (size_t)IC * OC);
   float *fb = (float *)(comp + OC), *fs = fb + OC;
-  bool fast1 = d.round_mode1 == DFX_ROUND_NEAREST;
-  for (int k = 0; k < OC; ++k) {
-    long long pos = 0, neg = 0;
-    for (int i = 0; i < IC; ++i) {
-      const int v = wei_pw[dfx_blocked_offset(k, i, 0, 0, IC, 1, 1)];
-      (v > 0 ? pos : neg) += v;
-    }
-    comp[k] = (int32_t)(128 * (pos + neg));
-    fb[k] = d.bia1_dt == DFX_UNDEF ? 0.0f : bias_as_f32(bia1, d.bia1_dt, k);
-    fs[k] = scales1[d.nscales1 == 1 ? 0 : k];
-    fast1 = fast1 && fast_ok_channel(255.0 * (double)std::max(pos, -neg), fb[k], fs[k]);
-  }
-  if (const char *e = tuning_value("DFX_NO_FAST")) fast1 = fast1 && atoi(e) == 0;  // testing aid: force the exact route
+  // (requant_host.h's clause over one output channel of the pointwise conv)
+  const bool proven = requant_consts(OC, (size_t)IC, [&](int k, size_t i) { return wei_pw[dfx_blocked_offset(k, (int)i, 0, 0, IC, 1, 1)]; },
+                                     bia1, d.bia1_dt, scales1, d.nscales1, comp, fb, fs);
+  const bool fast1 = d.round_mode1 == DFX_ROUND_NEAREST && proven && fast_allowed();
   DeviceGuard dg(h->device);
   HIP_TRY(hipMemcpy(h->d_w1, img.data(), h->w1_bytes, hipMemcpyHostToDevice));
   DwPwArgs &a = h->args;
@@ -372,49 +330,23 @@ int dfx_dwpw_submit(dfx_dwpw_t *h, const void *src_dev, void *dst_dev, dfx_strea
     HIP_TRY(hipGetLastError());
     return DFX_OK;
   }
-  // two launches through the handle's one buffer: serialised (dfx.h; catconv_api.hip)
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->have_last) {
-    h->first_stream = st;
-    h->first_serial = stream_serial_of(st);
-  } else if (!h->multi_stream && st != h->first_stream) {
-    h->multi_stream = true;
-    // (a first stream of dfx_stream_create's that dfx_stream_destroy has destroyed since must not be touched)
-    const bool gone = h->first_serial != 0 && stream_serial_of(h->first_stream) != h->first_serial;
-    hipError_t r = gone ? hipErrorContextIsDestroyed : hipEventRecord(h->ev, h->first_stream);
-    if (r == hipSuccess) r = hipStreamWaitEvent(st, h->ev, 0);
-    if (r != hipSuccess) {  // nothing to record on: wait for the device instead
-      if (!gone) (void)hipGetLastError();
-      HIP_TRY(hipDeviceSynchronize());
-    }
-  } else if (h->multi_stream && st != h->last_stream) {
-    HIP_TRY(hipStreamWaitEvent(st, h->ev, 0));
-  }
-  int rc = dfx_dwconv_submit(h->dw, src_dev, h->d_mid, s);
+  // two launches through the handle's one buffer: serialised (dfx.h; TwoLaunchOrder in dfx_internal.h)
+  std::lock_guard<std::mutex> lk(h->order.mu);
+  int rc = h->order.enter(st);
+  if (rc) return rc;
+  rc = dfx_dwconv_submit(h->dw, src_dev, h->d_mid, s);
   if (rc) return rc;
   rc = dfx_conv_submit(h->conv, h->d_mid, dst_dev, s);
   if (rc) return rc;
-  if (h->multi_stream) HIP_TRY(hipEventRecord(h->ev, st));
-  h->last_stream = st;
-  h->have_last = true;
-  return DFX_OK;
+  return h->order.leave(st);
 }
 
 int dfx_dwpw_submit_host(dfx_dwpw_t *h, const void *src_host, void *dst_host) {
   if (!h || !src_host || !dst_host) return fail(DFX_ERR_INVALID, "dwpw_submit_host: null argument");
   if (!h->weights_set) return fail(DFX_ERR_STATE, "dwpw_submit_host: dfx_dwpw_set_weights not called");
   DeviceGuard dg(h->device);
-  std::lock_guard<std::mutex> lk(h->host_mu);
-  // each on its own: a call that failed half way leaves nothing the next one would take for complete
-  if (!h->d_src) HIP_TRY(hipMalloc(&h->d_src, src_bytes(h->d)));
-  if (!h->d_dst) HIP_TRY(hipMalloc(&h->d_dst, dst_bytes(h->d)));
-  if (!h->host_stream) HIP_TRY(hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking));
-  HIP_TRY(hipMemcpyAsync(h->d_src, src_host, src_bytes(h->d), hipMemcpyHostToDevice, h->host_stream));
-  int rc = dfx_dwpw_submit(h, h->d_src, h->d_dst, h->host_stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(dst_host, h->d_dst, dst_bytes(h->d), hipMemcpyDeviceToHost, h->host_stream));
-  HIP_TRY(hipStreamSynchronize(h->host_stream));
-  return DFX_OK;
+  return h->host.run(src_host, src_bytes(h->d), dst_host, dst_bytes(h->d),
+                     [h](const void *s, void *d, dfx_stream_t st) { return dfx_dwpw_submit(h, s, d, st); });
 }
 
 int dfx_dwpw_query(const dfx_dwpw_t *h, dfx_dwpw_info *info) {

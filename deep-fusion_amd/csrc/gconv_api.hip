@@ -4,17 +4,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <new>
 #include <vector>
 
 #include "dfx_internal.h"
 #include "gconv.cuh"
 #include "gconv_pack.h"
+#include "requant_host.h"
 
 namespace dfx {
 int launch_gconv_mfma(const GcArgs &, int grid, int lds, hipStream_t, int mode, bool fast);
@@ -24,19 +23,16 @@ using namespace dfx;
 
 struct dfx_gconv {
   dfx_gconv_desc d;
-  int device;
-  int path;
-  int grid, block, lds;
-  GcArgs args;           // everything but src / dst; copied per launch
-  unsigned char *d_buf;  // packed weights | raw weights | comp | bias | scale
-  size_t off_wraw, off_comp, off_bias, off_scale, buf_bytes;
-  bool weights_set;
-  int route;             // 0 exact, 1 fast (dfx_debug_conv_requant's numbering)
-  // dfx_gconv_submit_host
-  std::mutex host_mu;
-  void *d_src, *d_dst;
-  hipStream_t host_stream;
-  char kernel_name[96];
+  int device = 0;
+  int path = 0;
+  int grid = 0, block = 0, lds = 0;
+  GcArgs args = {};                // everything but src / dst; copied per launch
+  unsigned char *d_buf = nullptr;  // packed weights | raw weights | comp | bias | scale
+  size_t off_wraw = 0, off_comp = 0, off_bias = 0, off_scale = 0, buf_bytes = 0;
+  bool weights_set = false;
+  int route = 0;                   // 0 exact, 1 fast (dfx_debug_conv_requant's numbering)
+  HostStaging host;                // dfx_gconv_submit_host
+  char kernel_name[96] = "";
 };
 
 namespace {
@@ -73,27 +69,6 @@ bool mfma_class(const dfx_gconv_desc &d) {
          (long long)d.oh * d.ow * d.oc * (long long)dt_size(d.dst_dt) < lim;
 }
 
-float bias_as_f32(const void *b, int dt, int c) {  // the conv's bias_to_f32 (vcvtdq2ps after the widening move)
-  switch (dt) {
-    case DFX_F32: return ((const float *)b)[c];
-    case DFX_S32: return (float)((const int32_t *)b)[c];
-    case DFX_S8: return (float)((const int8_t *)b)[c];
-    case DFX_U8: return (float)((const uint8_t *)b)[c];
-  }
-  return 0.0f;
-}
-
-// One output channel's precondition of the fast requant route (gconv.cuh gc_quarter<FAST>): the depthwise op's proof
-// (dwconv_api.hip) with P and N summed over the channel's ic / groups * kh * kw taps.  The accumulator is exact on both
-// routes, so are the add and the multiply; amax = 255 * max(P, N) bounds |acc|, and a bound of 2^30 on the product
-// keeps every value far from +-2^31, where the hardware conversions and vcvtps2dq part ways.
-bool gc_fast_ok_channel(double amax, float bias, float scale) {
-  if (!std::isfinite(bias) || !std::isfinite(scale)) return false;
-  return (amax + std::fabs((double)bias)) * std::fabs((double)scale) <= 1073741824.0;  // 2^30
-}
-
-const char *dt_name(int dt) { return dt == DFX_F32 ? "f32" : dt == DFX_S32 ? "s32" : dt == DFX_S8 ? "s8" : "u8"; }
-
 void set_name(dfx_gconv *h) {
   const dfx_gconv_desc &d = h->d;
   if (h->path == DFX_GCONV_MFMA)
@@ -108,16 +83,13 @@ void release(dfx_gconv *h) {
   if (!h) return;
   DeviceGuard dg(h->device);
   (void)hipFree(h->d_buf);
-  (void)hipFree(h->d_src);
-  (void)hipFree(h->d_dst);
-  if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
+  h->host.release();
   delete h;
 }
 
 size_t src_bytes(const dfx_gconv_desc &d) { return (size_t)d.bs * d.ih * d.iw * d.ic; }
 size_t dst_bytes(const dfx_gconv_desc &d) { return (size_t)d.bs * d.oh * d.ow * d.oc * dt_size(d.dst_dt); }
 size_t wei_count(const dfx_gconv_desc &d) { return (size_t)d.oc * (d.ic / d.groups) * d.kh * d.kw; }
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -140,8 +112,6 @@ int dfx_gconv_create(const dfx_gconv_desc *desc, dfx_gconv_t **out) {
   h->d = d;
   if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   h->path = (covered && d.force_path != DFX_GCONV_GENERIC) ? DFX_GCONV_MFMA : DFX_GCONV_GENERIC;
-  h->d_buf = nullptr; h->d_src = h->d_dst = nullptr; h->host_stream = nullptr;
-  h->weights_set = false; h->route = 0;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
     release(h);
@@ -149,7 +119,6 @@ int dfx_gconv_create(const dfx_gconv_desc *desc, dfx_gconv_t **out) {
   }
   const int cus = std::max(1, prop.multiProcessorCount);
   GcArgs &a = h->args;
-  memset(&a, 0, sizeof(a));
   a.bs = d.bs; a.ic = d.ic; a.ih = d.ih; a.iw = d.iw; a.oc = d.oc; a.oh = d.oh; a.ow = d.ow; a.groups = d.groups;
   a.kh = d.kh; a.kw = d.kw; a.sh = d.sh; a.sw = d.sw; a.pt = d.pad_t; a.pl = d.pad_l;
   a.dst_dt = d.dst_dt; a.relu = (d.relu || d.dst_dt == DFX_U8) ? 1 : 0; a.rm = d.round_mode;
@@ -209,11 +178,11 @@ int dfx_gconv_create(const dfx_gconv_desc *desc, dfx_gconv_t **out) {
     h->lds = 0;
     h->grid = (int)std::min((a.items + 255) / 256, (long long)cus * 8);
   }
-  h->off_wraw = align16(wpk_bytes);
-  h->off_comp = h->off_wraw + align16(wei_count(d));
-  h->off_bias = h->off_comp + align16((size_t)d.oc * 4);
-  h->off_scale = h->off_bias + align16((size_t)d.oc * 4);
-  h->buf_bytes = h->off_scale + align16((size_t)d.oc * 4);
+  h->off_wraw = round16(wpk_bytes);
+  h->off_comp = h->off_wraw + round16(wei_count(d));
+  h->off_bias = h->off_comp + round16((size_t)d.oc * 4);
+  h->off_scale = h->off_bias + round16((size_t)d.oc * 4);
+  h->buf_bytes = h->off_scale + round16((size_t)d.oc * 4);
   hipError_t e = hipMalloc((void **)&h->d_buf, h->buf_bytes);
   if (e != hipSuccess) {
     release(h);
@@ -238,19 +207,9 @@ int dfx_gconv_set_weights(dfx_gconv_t *h, const int8_t *wei, const void *bia, co
   int *comp = (int *)(img.data() + h->off_comp);
   float *fb = (float *)(img.data() + h->off_bias), *fs = (float *)(img.data() + h->off_scale);
   memcpy(img.data() + h->off_wraw, wei, wei_count(d));
-  bool fast = h->path == DFX_GCONV_MFMA && d.round_mode == DFX_ROUND_NEAREST;
-  for (int k = 0; k < d.oc; ++k) {
-    long long pos = 0, neg = 0;
-    for (size_t i = 0; i < taps; ++i) {
-      const int v = wei[(size_t)k * taps + i];
-      (v > 0 ? pos : neg) += v;
-    }
-    comp[k] = (int)(128 * (pos + neg));
-    fb[k] = d.bia_dt == DFX_UNDEF ? 0.0f : bias_as_f32(bia, d.bia_dt, k);
-    fs[k] = scales[d.nscales == 1 ? 0 : k];
-    fast = fast && gc_fast_ok_channel(255.0 * (double)std::max(pos, -neg), fb[k], fs[k]);
-  }
-  if (const char *e = tuning_value("DFX_NO_FAST")) fast = fast && atoi(e) == 0;  // testing aid: force the exact route
+  const bool proven = requant_consts(d.oc, taps, [&](int k, size_t i) { return wei[(size_t)k * taps + i]; }, bia, d.bia_dt, scales,
+                                     d.nscales, comp, fb, fs);
+  const bool fast = h->path == DFX_GCONV_MFMA && d.round_mode == DFX_ROUND_NEAREST && proven && fast_allowed();
   if (h->path == DFX_GCONV_MFMA) gconv_pack(wei, d.oc, d.ic / d.groups, img.data());
   DeviceGuard dg(h->device);
   HIP_TRY(hipMemcpy(h->d_buf, img.data(), h->buf_bytes, hipMemcpyHostToDevice));
@@ -281,17 +240,8 @@ int dfx_gconv_submit_host(dfx_gconv_t *h, const void *src_host, void *dst_host) 
   if (!h || !src_host || !dst_host) return fail(DFX_ERR_INVALID, "gconv_submit_host: null argument");
   if (!h->weights_set) return fail(DFX_ERR_STATE, "gconv_submit_host: dfx_gconv_set_weights not called");
   DeviceGuard dg(h->device);
-  std::lock_guard<std::mutex> lk(h->host_mu);
-  // each on its own: a call that failed half way leaves nothing the next one would take for complete
-  if (!h->d_src) HIP_TRY(hipMalloc(&h->d_src, src_bytes(h->d)));
-  if (!h->d_dst) HIP_TRY(hipMalloc(&h->d_dst, dst_bytes(h->d)));
-  if (!h->host_stream) HIP_TRY(hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking));
-  HIP_TRY(hipMemcpyAsync(h->d_src, src_host, src_bytes(h->d), hipMemcpyHostToDevice, h->host_stream));
-  int rc = dfx_gconv_submit(h, h->d_src, h->d_dst, h->host_stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(dst_host, h->d_dst, dst_bytes(h->d), hipMemcpyDeviceToHost, h->host_stream));
-  HIP_TRY(hipStreamSynchronize(h->host_stream));
-  return DFX_OK;
+  return h->host.run(src_host, src_bytes(h->d), dst_host, dst_bytes(h->d),
+                     [h](const void *s, void *d, dfx_stream_t st) { return dfx_gconv_submit(h, s, d, st); });
 }
 
 int dfx_gconv_query(const dfx_gconv_t *h, dfx_gconv_info *info) {

@@ -10,6 +10,7 @@
 
 #include "dfx_device.cuh"
 #include "dfx_internal.h"
+#include "requant_host.h"
 
 namespace dfx {
 int launch_reorder(const ReorderArgs &a, hipStream_t s);
@@ -18,20 +19,17 @@ using namespace dfx;
 
 struct dfx_reorder {
   dfx_reorder_desc d;
-  int device;
-  ReorderArgs args;
-  float *d_scales;
-  void *d_src, *d_dst;  // lazily allocated for dfx_reorder_submit_host
-  hipStream_t host_stream;
-  char kernel_name[96];
+  int device = 0;
+  ReorderArgs args = {};
+  float *d_scales = nullptr;
+  HostStaging host;  // dfx_reorder_submit_host
+  char kernel_name[96] = "";
 };
 
 namespace {
 
 constexpr int kLdsBudget = 48 * 1024;  // whole-depth tiles: three workgroups per CU and more
 constexpr int kMaxBlocks = 256 * 8;    // grid-stride kernels: 8 workgroups per CU
-
-const char *dt_name(int dt) { return dt == DFX_F32 ? "f32" : dt == DFX_S32 ? "s32" : dt == DFX_S8 ? "s8" : "u8"; }
 
 int validate_reorder(const dfx_reorder_desc &d, const float *scales) {
   if (d.bs <= 0 || d.h <= 0 || d.w <= 0 || d.src_c <= 0 || d.dst_c <= 0)
@@ -142,9 +140,6 @@ int dfx_reorder_create(const dfx_reorder_desc *desc, const float *scales_host, d
   h->d = d;
   if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   h->args = a;
-  h->d_scales = nullptr;
-  h->d_src = h->d_dst = nullptr;
-  h->host_stream = nullptr;
   memcpy(h->kernel_name, name, sizeof(name));
   // the kernels index one scale per source channel: expand "none" (1.0f) and "one"
   std::vector<float> sc((size_t)d.src_c, 1.0f);
@@ -177,17 +172,8 @@ int dfx_reorder_submit(dfx_reorder_t *h, const void *src_dev, void *dst_dev, dfx
 int dfx_reorder_submit_host(dfx_reorder_t *h, const void *src_host, void *dst_host) {
   if (!h || !src_host || !dst_host) return fail(DFX_ERR_INVALID, "reorder_submit_host: null argument");
   DeviceGuard dg(h->device);
-  if (!h->d_src) {
-    HIP_TRY(hipMalloc(&h->d_src, src_bytes(h->d)));
-    HIP_TRY(hipMalloc(&h->d_dst, dst_bytes(h->d)));
-    HIP_TRY(hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking));
-  }
-  HIP_TRY(hipMemcpyAsync(h->d_src, src_host, src_bytes(h->d), hipMemcpyHostToDevice, h->host_stream));
-  int rc = dfx_reorder_submit(h, h->d_src, h->d_dst, h->host_stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(dst_host, h->d_dst, dst_bytes(h->d), hipMemcpyDeviceToHost, h->host_stream));
-  HIP_TRY(hipStreamSynchronize(h->host_stream));
-  return DFX_OK;
+  return h->host.run(src_host, src_bytes(h->d), dst_host, dst_bytes(h->d),
+                     [h](const void *s, void *d, dfx_stream_t st) { return dfx_reorder_submit(h, s, d, st); });
 }
 
 int dfx_reorder_query(const dfx_reorder_t *h, dfx_reorder_info *info) {
@@ -213,9 +199,7 @@ int dfx_reorder_destroy(dfx_reorder_t *h) {
   if (!h) return DFX_OK;
   DeviceGuard dg(h->device);
   (void)hipFree(h->d_scales);
-  (void)hipFree(h->d_src);
-  (void)hipFree(h->d_dst);
-  if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
+  h->host.release();
   delete h;
   return DFX_OK;
 }

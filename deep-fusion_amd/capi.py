@@ -20,6 +20,7 @@ CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH = -1, 0, 1
 DWCONV_AUTO, DWCONV_WINDOW, DWCONV_GENERIC = -1, 0, 1
 GCONV_AUTO, GCONV_MFMA, GCONV_GENERIC = -1, 0, 1
 DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH = -1, 0, 1
+FC_AUTO, FC_MFMA, FC_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -103,6 +104,17 @@ class GConvDesc(ctypes.Structure):
 
 class GConvInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
+class FcDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "ic", "ih", "iw", "oc", "dst_dt", "bia_dt", "relu", "round_mode",
+                                             "nscales", "force_path")]
+
+
+class FcInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "splitk", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
 
@@ -230,6 +242,12 @@ def lib():
         "dfx_gconv_submit_host": (i32, [vp, vp, vp]),
         "dfx_gconv_query": (i32, [vp, ctypes.POINTER(GConvInfo)]),
         "dfx_gconv_destroy": (i32, [vp]),
+        "dfx_fc_create": (i32, [ctypes.POINTER(FcDesc), ctypes.POINTER(vp)]),
+        "dfx_fc_set_weights": (i32, [vp, vp, vp, vp]),
+        "dfx_fc_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_fc_submit_host": (i32, [vp, vp, vp]),
+        "dfx_fc_query": (i32, [vp, ctypes.POINTER(FcInfo)]),
+        "dfx_fc_destroy": (i32, [vp]),
         "dfx_dwpw_create": (i32, [ctypes.POINTER(DwPwDesc), ctypes.POINTER(vp)]),
         "dfx_dwpw_set_weights": (i32, [vp] * 7),
         "dfx_dwpw_submit": (i32, [vp, vp, vp, vp]),
@@ -244,6 +262,7 @@ def lib():
         "dfx_debug_dwconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_gconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwpw_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_debug_fc_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -544,6 +563,33 @@ class GroupConv(_Handle):
         assert ws[0].size == d.oc * (d.ic // d.groups) * d.kh * d.kw, ws[0].shape
         assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
         _check(lib().dfx_gconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+
+class InnerProduct(_Handle):
+    """dfx_fc_* handle: int8 fully-connected layer over NHWC u8 {bs, ih, iw, ic} (include/dfx.h), weights plain oihw
+    {oc, ic, ih, iw} as a flattened-CHW classifier keeps them, dst {bs, oc}.  Where ic and oc are multiples of 16 the
+    result equals the unfused Conv with the full-image window bit for bit."""
+
+    _OP, _INFO, _ROUTES = "dfx_fc", FcInfo, 1
+
+    def __init__(self, src_shape_nhwc, oc, dst_dt=DFX_U8, bia_dt=DFX_UNDEF, relu=False, rm=ROUND_NEAREST, nscales=1,
+                 force_path=FC_AUTO):
+        bs, ih, iw, ic = src_shape_nhwc
+        d = FcDesc(bs, ic, ih, iw, oc, dst_dt, bia_dt, int(relu), rm, nscales, force_path)
+        self.desc = d
+        self.src_shape = (bs, ih, iw, ic)
+        self.dst_shape = (bs, oc)
+        self.dst_np_dtype = _NP.get(dst_dt)
+        self._create(d)
+
+    def set_weights(self, wei, scales, bia=None):
+        """wei: int8 {oc, ic, ih, iw}; scales: 1 or oc floats; bia: oc entries of the descriptor's bias dtype"""
+        d = self.desc
+        ws = [np.ascontiguousarray(wei, dtype=np.int8), None if bia is None else np.ascontiguousarray(bia),
+              np.ascontiguousarray(scales, dtype=np.float32)]
+        assert ws[0].size == d.oc * d.ic * d.ih * d.iw, ws[0].shape
+        assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
+        _check(lib().dfx_fc_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
 
 
 class DwPwConv(_Handle):

@@ -1,5 +1,5 @@
 // dfx_internal.h -- the few host-side helpers the translation units behind include/dfx.h share
-// (dfx_api.hip, reorder_api.hip, catconv_api.hip, dwconv_api.hip, dwpw_api.hip, gconv_api.hip).  Not installed, not
+// (dfx_api.hip, reorder_api.hip, catconv_api.hip, dwconv_api.hip, dwpw_api.hip, gconv_api.hip, fc_api.hip).  Not installed, not
 // part of the C ABI.  What needs no HIP is in requant_host.h.
 #pragma once
 
@@ -68,7 +68,7 @@ inline bool fast_allowed() {
   return !e || atoi(e) == 0;
 }
 
-// Order of the submits of a two-launch op (catconv_api.hip, dwpw_api.hip), whose two kernels meet in ONE buffer the
+// Order of the submits of a two-launch op (catconv_api.hip, dwpw_api.hip, fc_api.hip), whose two kernels meet in ONE buffer the
 // handle owns, so that its submits are SERIALISED on the device.  Submits on ONE stream are ordered by the stream and
 // cost nothing extra (an event record behind every submit measured + 3 us per submit).  When a second stream appears,
 // one event recorded on the first stream stands for everything submitted so far; from then on every submit records `ev`

@@ -274,6 +274,22 @@ std::unique_ptr<op> grouped_conv(const std::unique_ptr<memory> &src,
                                  bool relu = false, std::vector<float> scales = {1.f},
                                  round_mode rm = round_mode::nearest);
 
+// ---- extension: fully-connected (inner product) layer (dfx_fc_* in dfx.h): the classifier head of ResNet / VGG /
+// MobileNet, which conv() cannot express where oc is no multiple of 16 (the 1000-class heads).  src: nhwc u8
+// {bs, c, h, w}, exactly as the previous conv or pool op left it (h = w = 1: a plain vector); wei: plain oihw s8 of dims
+// {oc, c, h, w}, the flattened-CHW order frameworks keep (the library permutes it to src's order when it packs); bia:
+// format x, oc entries, or null; dst: nhwc u8 / s8 / s32 / f32 of dims {bs, oc, 1, 1}, any oc >= 1.  c * h * w <= 65025.
+// Arithmetic, scales, ReLU and rounding are conv()'s: where c and oc are multiples of 16, dst holds, bit for bit, what
+// conv() gives with a window of the whole image.  c * h * w a multiple of 64 runs on a split-K int8-MFMA kernel,
+// everything else on a generic one.  submit / submit_async / wait, weight hashing and DEEPFUSION_DEVICES sharding are
+// depthwise_conv()'s. ----
+std::unique_ptr<op> inner_product(const std::unique_ptr<memory> &src,
+                                  const std::unique_ptr<memory> &wei,
+                                  const std::unique_ptr<memory> &bia,
+                                  std::unique_ptr<memory> &dst,
+                                  bool relu = false, std::vector<float> scales = {1.f},
+                                  round_mode rm = round_mode::nearest);
+
 // ---- extension: depthwise conv + pointwise conv, the depthwise-separable block (dfx_dwpw_* in dfx.h).  Stage 0 is
 // depthwise_conv() with a u8 result (ReLU implied), stage 1 a 1x1 stride-1 unpadded conv() on that tensor; dst holds,
 // bit for bit, what the two ops give one after the other.  wei_dw: plain oihw s8 {c, 1, kh, kw}; wei_pw: OIhw4i16o4i

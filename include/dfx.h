@@ -294,6 +294,43 @@ typedef struct dfx_gconv_info {
 } dfx_gconv_info;
 typedef struct dfx_gconv dfx_gconv_t;
 
+/* ---- fully-connected (inner product) layer on int8: the classifier head the conv ops cannot express.  src NHWC u8
+ *      {bs,ih,iw,ic} exactly as the previous conv or pool op wrote it (ih = iw = 1: a plain vector); wei s8
+ *      {oc,ic,ih,iw} plain row-major, the flattened-CHW classifier frameworks keep (the library permutes it to src's
+ *      order when it packs); dst {bs,oc}, rows oc elements apart.  Any bs >= 1 and oc >= 1.
+ *        acc[n,o] = sum over c, y, x of src[n,y,x,c] * w[o,c,y,x]
+ *        f = float(acc);  f = f + bias[o] (if any);  f = f * scale[o or 0];  ReLU (asked for, or dst is u8):
+ *        f = (0 > f) ? 0 : f;  dst = store(f, dst_dt, round_mode)
+ *      with the grouped op's arithmetic: separately rounded add and multiply, the bias converted like the conv's,
+ *      the x86 conversion (NaN / out of range -> 0x80000000 -> u8 255, s8 -128).  Where ic and oc are multiples of 16
+ *      the result is, bit for bit, the unfused dfx_conv with kh = ih, kw = iw, stride 1, no padding (oh = ow = 1).
+ *      Parity unpinned: the reference has no inner product. ---- */
+typedef struct dfx_fc_desc {
+  int32_t bs, ic, ih, iw;      /* K = ih * iw * ic <= 65025: below it the accumulator cannot leave s32 */
+  int32_t oc;
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t bia_dt;              /* DFX_UNDEF = none */
+  int32_t relu, round_mode;
+  int32_t nscales;             /* 1 or oc */
+  int32_t force_path;          /* -1 auto, else DFX_FC_* (testing) */
+} dfx_fc_desc;
+enum {  /* dfx_fc_info.path */
+  DFX_FC_MFMA = 0,             /* the split-K int8-MFMA kernel and its epilogue (fc.cuh): two launches.  Covers
+                                  K % 64 == 0 with any bs and oc.  Auto takes it everywhere in this class. */
+  DFX_FC_GENERIC = 1           /* everything else (a 3-channel input, K = 100): one thread per output value, one
+                                  launch, exact requant only */
+};
+typedef struct dfx_fc_info {
+  int32_t path;
+  int32_t splitk;              /* K slices of the MFMA path (1 on the generic path) */
+  int32_t grid, block, lds_bytes;  /* of the MFMA kernel (the generic kernel on that path) */
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2*MAC of one submit: 2 * bs * K * oc */
+  uint64_t algorithmic_bytes;  /* src + weights + dst (the slab of partial sums is not algorithmic) */
+  char kernel_name[96];        /* path, K, dst type, splitk and requant route (valid after set_weights) */
+} dfx_fc_info;
+typedef struct dfx_fc dfx_fc_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -541,6 +578,27 @@ int dfx_gconv_submit_host(dfx_gconv_t *h, const void *src_host, void *dst_host);
 int dfx_gconv_query(const dfx_gconv_t *h, dfx_gconv_info *info);
 int dfx_gconv_destroy(dfx_gconv_t *h);
 
+/* ---- fully-connected layer (dfx_fc_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for a non-positive size, ih * iw * ic > 65025, bs * oc of 2^31 or more, a bad dtype / round
+ *      mode / nscales / force_path; DFX_ERR_UNSUPPORTED only for force_path = DFX_FC_MFMA where K is no multiple of
+ *      64.  On auto everything outside that class takes the generic path.  set_weights: host pointers, copied; wei is
+ *      s8 {oc, ic, ih, iw}; bia has oc entries of bia_dt (NULL when DFX_UNDEF); it may be called again (not while a
+ *      submit of the handle is in flight) and chooses the requant route from the actual numbers as
+ *      dfx_gconv_set_weights does, over the K taps of a channel: "fast" when, for every output channel, bias and scale
+ *      are finite and (255 * max(P, N) + |bias|) * |scale| <= 2^30, the round mode is nearest and DFX_NO_FAST is not
+ *      set; else "exact".  The generic kernel is always exact.  submit: asynchronous on `s`; src and dst must be
+ *      non-null and 16-byte aligned (DFX_ERR_INVALID otherwise, nothing is launched); DFX_ERR_STATE before
+ *      set_weights.  MFMA path: the handle owns ONE slab of s32 partial sums [splitk][bs rounded up to 32][oc rounded
+ *      up to 32] between its two launches, so its submits are SERIALISED on the device exactly as dfx_catconv's and
+ *      dfx_dwpw's two-launch path (see there); the host never blocks.  The partial sums are added as integers: every
+ *      splitk gives the same bits.  No CPU fallback. ---- */
+int dfx_fc_create(const dfx_fc_desc *desc, dfx_fc_t **out);
+int dfx_fc_set_weights(dfx_fc_t *h, const int8_t *wei, const void *bia, const float *scales);
+int dfx_fc_submit(dfx_fc_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_fc_submit_host(dfx_fc_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_fc_query(const dfx_fc_t *h, dfx_fc_info *info);
+int dfx_fc_destroy(dfx_fc_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -611,6 +669,8 @@ int dfx_debug_catconv_requant(const dfx_catconv_t *h, int32_t out[2]);
 int dfx_debug_dwconv_requant(const dfx_dwconv_t *h, int32_t out[1]);
 /* the grouped conv's one stage, same numbering (0 exact, 1 fast) */
 int dfx_debug_gconv_requant(const dfx_gconv_t *h, int32_t out[1]);
+/* the fully-connected op's one stage, same numbering (0 exact, 1 fast) */
+int dfx_debug_fc_requant(const dfx_fc_t *h, int32_t out[1]);
 /* the depthwise + pointwise op's two stages {route0, route1}, same numbering; on the two-launch path the routes of
  * the owned depthwise and conv handles */
 int dfx_debug_dwpw_requant(const dfx_dwpw_t *h, int32_t out[2]);

@@ -19,6 +19,7 @@ REORDER_FLAT, REORDER_GENERIC, REORDER_SMALLC, REORDER_TRANSPOSE = 0, 1, 2, 3
 CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH = -1, 0, 1
 DWCONV_AUTO, DWCONV_WINDOW, DWCONV_GENERIC = -1, 0, 1
 GCONV_AUTO, GCONV_MFMA, GCONV_GENERIC = -1, 0, 1
+IMGCONV_AUTO, IMGCONV_MFMA, IMGCONV_GENERIC = -1, 0, 1
 DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH = -1, 0, 1
 FC_AUTO, FC_MFMA, FC_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
@@ -103,6 +104,17 @@ class GConvDesc(ctypes.Structure):
 
 
 class GConvInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
+class ImgConvDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "ic", "ih", "iw", "oc", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t",
+                                             "pad_l", "dst_dt", "bia_dt", "relu", "round_mode", "nscales", "force_path")]
+
+
+class ImgConvInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
@@ -242,6 +254,12 @@ def lib():
         "dfx_gconv_submit_host": (i32, [vp, vp, vp]),
         "dfx_gconv_query": (i32, [vp, ctypes.POINTER(GConvInfo)]),
         "dfx_gconv_destroy": (i32, [vp]),
+        "dfx_imgconv_create": (i32, [ctypes.POINTER(ImgConvDesc), ctypes.POINTER(vp)]),
+        "dfx_imgconv_set_weights": (i32, [vp, vp, vp, vp]),
+        "dfx_imgconv_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_imgconv_submit_host": (i32, [vp, vp, vp]),
+        "dfx_imgconv_query": (i32, [vp, ctypes.POINTER(ImgConvInfo)]),
+        "dfx_imgconv_destroy": (i32, [vp]),
         "dfx_fc_create": (i32, [ctypes.POINTER(FcDesc), ctypes.POINTER(vp)]),
         "dfx_fc_set_weights": (i32, [vp, vp, vp, vp]),
         "dfx_fc_submit": (i32, [vp, vp, vp, vp]),
@@ -261,6 +279,7 @@ def lib():
         "dfx_debug_catconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_gconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_debug_imgconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwpw_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_fc_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
@@ -563,6 +582,39 @@ class GroupConv(_Handle):
         assert ws[0].size == d.oc * (d.ic // d.groups) * d.kh * d.kw, ws[0].shape
         assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
         _check(lib().dfx_gconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+
+class ImageConv(_Handle):
+    """dfx_imgconv_* handle: the first-layer int8 conv over a 1- to 4-channel NHWC u8 image (include/dfx.h), weights plain
+    oihw {oc, ic, kh, kw}.  The result equals GroupConv with groups = 1 bit for bit and, where oc is a multiple of 16 and
+    the output size is the conv's, the unfused Conv on the image zero-padded to 16 channels.  src may sit at any byte
+    address.  out_hw defaults to the conv's (in + 2 * pad - k) // stride + 1; give it for windows that hang over the
+    bottom / right edge."""
+
+    _OP, _INFO, _ROUTES = "dfx_imgconv", ImgConvInfo, 1
+
+    def __init__(self, src_shape_nhwc, oc, kernel, stride=(1, 1), pad=(1, 1), out_hw=None, dst_dt=DFX_U8, bia_dt=DFX_UNDEF,
+                 relu=False, rm=ROUND_NEAREST, nscales=1, force_path=IMGCONV_AUTO):
+        bs, ih, iw, ic = src_shape_nhwc
+        kh, kw = kernel
+        if out_hw is None:
+            out_hw = _conv_out_hw(ih, iw, kernel, stride, pad)
+        d = ImgConvDesc(bs, ic, ih, iw, oc, out_hw[0], out_hw[1], kh, kw, stride[0], stride[1], pad[0], pad[1], dst_dt,
+                        bia_dt, int(relu), rm, nscales, force_path)
+        self.desc = d
+        self.src_shape = (bs, ih, iw, ic)
+        self.dst_shape = (bs, out_hw[0], out_hw[1], oc)
+        self.dst_np_dtype = _NP.get(dst_dt)
+        self._create(d)
+
+    def set_weights(self, wei, scales, bia=None):
+        """wei: int8 {oc, ic, kh, kw}; scales: 1 or oc floats; bia: oc entries of the descriptor's bias dtype"""
+        d = self.desc
+        ws = [np.ascontiguousarray(wei, dtype=np.int8), None if bia is None else np.ascontiguousarray(bia),
+              np.ascontiguousarray(scales, dtype=np.float32)]
+        assert ws[0].size == d.oc * d.ic * d.kh * d.kw, ws[0].shape
+        assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
+        _check(lib().dfx_imgconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
 
 
 class InnerProduct(_Handle):

@@ -274,6 +274,24 @@ std::unique_ptr<op> grouped_conv(const std::unique_ptr<memory> &src,
                                  bool relu = false, std::vector<float> scales = {1.f},
                                  round_mode rm = round_mode::nearest);
 
+// ---- extension: first-layer conv over a 1- to 4-channel image (dfx_imgconv_* in dfx.h): conv1 of ResNet / VGG /
+// MobileNet / Inception, which conv() cannot take without a reorder() that pads the image to 16 channels first.  src:
+// nhwc u8 with 1 to 4 channels, as it is; wei: plain oihw s8 of dims {oc, ic, kh, kw}; bia: format x, oc entries, or
+// null; dst: nhwc u8 / s8 / s32 / f32 with src's batch and any oc -- ITS height and width are the output size, as for
+// grouped_conv(); padding is {top, left}.  Arithmetic, scales, ReLU and rounding are conv()'s: dst holds, bit for bit,
+// what grouped_conv() with groups = 1 gives and, where oc is a multiple of 16 and the output size is conv()'s, what
+// conv() gives on the image zero-padded to 16 channels.  3 or 4 channels with 7x7 / 2, 3x3 / 1 or 3x3 / 2 windows and
+// oc in {32, 64, 96, 128} run on an int8-MFMA kernel in one launch, everything else on a generic one.  submit /
+// submit_async / wait, weight hashing and DEEPFUSION_DEVICES sharding are depthwise_conv()'s. ----
+std::unique_ptr<op> image_conv(const std::unique_ptr<memory> &src,
+                               const std::unique_ptr<memory> &wei,
+                               const std::unique_ptr<memory> &bia,
+                               std::array<int, 2> sz_stride,
+                               std::array<int, 2> sz_padding,
+                               std::unique_ptr<memory> &dst,
+                               bool relu = false, std::vector<float> scales = {1.f},
+                               round_mode rm = round_mode::nearest);
+
 // ---- extension: fully-connected (inner product) layer (dfx_fc_* in dfx.h): the classifier head of ResNet / VGG /
 // MobileNet, which conv() cannot express where oc is no multiple of 16 (the 1000-class heads).  src: nhwc u8
 // {bs, c, h, w}, exactly as the previous conv or pool op left it (h = w = 1: a plain vector); wei: plain oihw s8 of dims

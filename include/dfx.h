@@ -294,6 +294,53 @@ typedef struct dfx_gconv_info {
 } dfx_gconv_info;
 typedef struct dfx_gconv dfx_gconv_t;
 
+/* ---- first-layer conv over a 1- to 4-channel image: the conv1 of ResNet / VGG / MobileNet / Inception, which dfx_conv's
+ *      ic % 16 == 0 rule cannot take without padding the image to 16 channels first.  src NHWC u8 {bs,ih,iw,ic} with
+ *      1 <= ic <= 4, at ANY byte address (the rows of a 3-channel image start at any byte offset anyway); wei s8
+ *      {oc,ic,kh,kw} plain row-major (OIhw4i16o4i cannot express ic < 16); dst NHWC {bs,oh,ow,oc}, any oc >= 1.
+ *        acc[n,oy,ox,o] = sum over i < ic, ky, kx of src[n, oy*sh - pad_t + ky, ox*sw - pad_l + kx, i] * w[o,i,ky,kx]
+ *                         (taps outside the input are skipped, which equals zero padding)
+ *        f = float(acc);  f = f + bias[o] (if any);  f = f * scale[o or 0];  ReLU (asked for, or dst is u8):
+ *        f = (0 > f) ? 0 : f;  dst = store(f, dst_dt, round_mode)
+ *      with the grouped op's arithmetic, word for word: exact s32 accumulator, separately rounded add and multiply,
+ *      the bias converted like the conv's, the x86 conversion (NaN / out of range -> 0x80000000 -> u8 255, s8 -128).
+ *      Defining properties (tests/test_gpu_imgconv.py):
+ *        1. the result equals, bit for bit, dfx_gconv with groups = 1 on the same tensors;
+ *        2. where oc % 16 == 0 and oh / ow follow the conv formula it equals, bit for bit, the unfused dfx_conv on the
+ *           image zero-padded to 16 channels, with zero weights on the channels >= ic.
+ *      oh and ow are given by the caller as in dfx_gconv_desc: windows may hang over the bottom / right edge.  Windows
+ *      are 1 .. 255 on either axis.  Parity unpinned: the reference has no such op. ---- */
+typedef struct dfx_imgconv_desc {
+  int32_t bs, ic, ih, iw;      /* 1 <= ic <= 4 */
+  int32_t oc, oh, ow;          /* (oh - 1) * sh - pad_t <= ih - 1, likewise in x */
+  int32_t kh, kw;              /* 1 .. 255; kh * kw * ic <= 65025 */
+  int32_t sh, sw;
+  int32_t pad_t, pad_l;
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t bia_dt;              /* DFX_UNDEF = none */
+  int32_t relu, round_mode;
+  int32_t nscales;             /* 1 or oc */
+  int32_t force_path;          /* -1 auto, else DFX_IMGCONV_* (testing) */
+} dfx_imgconv_desc;
+enum {  /* dfx_imgconv_info.path */
+  DFX_IMGCONV_MFMA = 0,        /* the int8-MFMA kernel (imgconv.cuh), one launch.  Covers: ic 3 or 4; (window, stride)
+                                  7x7 / (2,2), 3x3 / (1,1) or 3x3 / (2,2); pad_t, pad_l <= k - 1; oc a multiple of 32,
+                                  at most 128; one image below 2^31 bytes on either side.
+                                  AUTO RULE: auto takes it everywhere in this class (measured against the generic
+                                  kernel on every point of profiles/imgconv/). */
+  DFX_IMGCONV_GENERIC = 1      /* everything else (ic 1 or 2, 5x5, 11x11 / 4, any oc): one thread per output element,
+                                  exact requant only */
+};
+typedef struct dfx_imgconv_info {
+  int32_t path;
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2*MAC of one submit: 2 * kh * kw * ic per output value */
+  uint64_t algorithmic_bytes;  /* src + weights + dst, src at its true ic bytes per pixel */
+  char kernel_name[96];        /* path, window, stride, ic, oc, dst type and requant route (valid after set_weights) */
+} dfx_imgconv_info;
+typedef struct dfx_imgconv dfx_imgconv_t;
+
 /* ---- fully-connected (inner product) layer on int8: the classifier head the conv ops cannot express.  src NHWC u8
  *      {bs,ih,iw,ic} exactly as the previous conv or pool op wrote it (ih = iw = 1: a plain vector); wei s8
  *      {oc,ic,ih,iw} plain row-major, the flattened-CHW classifier frameworks keep (the library permutes it to src's
@@ -578,6 +625,28 @@ int dfx_gconv_submit_host(dfx_gconv_t *h, const void *src_host, void *dst_host);
 int dfx_gconv_query(const dfx_gconv_t *h, dfx_gconv_info *info);
 int dfx_gconv_destroy(dfx_gconv_t *h);
 
+/* ---- first-layer conv (dfx_imgconv_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for a non-positive size or stride, ic > 4, a window beyond 255, a negative padding,
+ *      kh * kw * ic > 65025, an output row / column whose window starts below / right of the input, a bad dtype / round
+ *      mode / nscales / force_path, a tensor of 2^31 pixels or more; DFX_ERR_UNSUPPORTED only for force_path =
+ *      DFX_IMGCONV_MFMA on a shape outside that class.  On auto everything outside it takes the generic path: the op is
+ *      total and delegates to no other op.  set_weights: host pointers, copied; wei is s8 {oc, ic, kh, kw}; bia has oc
+ *      entries of bia_dt (NULL when DFX_UNDEF); it may be called again (not while a submit of the handle is in flight)
+ *      and chooses the requant route from the actual numbers exactly as dfx_gconv_set_weights does (one proof,
+ *      requant_host.h): "fast" when, for every output channel, bias and scale are finite and
+ *      (255 * max(P, N) + |bias|) * |scale| <= 2^30 over its ic * kh * kw taps, the round mode is nearest and
+ *      DFX_NO_FAST is not set; else "exact".  The generic kernel is always exact.  submit: asynchronous on `s`; src and
+ *      dst must be non-null, dst 16-byte aligned (DFX_ERR_INVALID otherwise, nothing is launched), src at any byte
+ *      address: no thread reads outside [src, src + bs*ih*iw*ic); DFX_ERR_STATE before set_weights.  Every launch has
+ *      its own copy of the arguments and submit never writes to the handle: one handle serves several streams and host
+ *      threads at once.  No CPU fallback. ---- */
+int dfx_imgconv_create(const dfx_imgconv_desc *desc, dfx_imgconv_t **out);
+int dfx_imgconv_set_weights(dfx_imgconv_t *h, const int8_t *wei, const void *bia, const float *scales);
+int dfx_imgconv_submit(dfx_imgconv_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_imgconv_submit_host(dfx_imgconv_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_imgconv_query(const dfx_imgconv_t *h, dfx_imgconv_info *info);
+int dfx_imgconv_destroy(dfx_imgconv_t *h);
+
 /* ---- fully-connected layer (dfx_fc_desc above).  The descriptor is validated before anything touches a device:
  *      DFX_ERR_INVALID for a non-positive size, ih * iw * ic > 65025, bs * oc of 2^31 or more, a bad dtype / round
  *      mode / nscales / force_path; DFX_ERR_UNSUPPORTED only for force_path = DFX_FC_MFMA where K is no multiple of
@@ -669,6 +738,8 @@ int dfx_debug_catconv_requant(const dfx_catconv_t *h, int32_t out[2]);
 int dfx_debug_dwconv_requant(const dfx_dwconv_t *h, int32_t out[1]);
 /* the grouped conv's one stage, same numbering (0 exact, 1 fast) */
 int dfx_debug_gconv_requant(const dfx_gconv_t *h, int32_t out[1]);
+/* the first-layer conv's one stage, same numbering (0 exact, 1 fast) */
+int dfx_debug_imgconv_requant(const dfx_imgconv_t *h, int32_t out[1]);
 /* the fully-connected op's one stage, same numbering (0 exact, 1 fast) */
 int dfx_debug_fc_requant(const dfx_fc_t *h, int32_t out[1]);
 /* the depthwise + pointwise op's two stages {route0, route1}, same numbering; on the two-launch path the routes of

@@ -20,6 +20,7 @@ CATCONV_AUTO, CATCONV_FUSED, CATCONV_TWO_LAUNCH = -1, 0, 1
 DWCONV_AUTO, DWCONV_WINDOW, DWCONV_GENERIC = -1, 0, 1
 GCONV_AUTO, GCONV_MFMA, GCONV_GENERIC = -1, 0, 1
 IMGCONV_AUTO, IMGCONV_MFMA, IMGCONV_GENERIC = -1, 0, 1
+DECONV_AUTO, DECONV_MFMA, DECONV_GENERIC = -1, 0, 1
 DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH = -1, 0, 1
 FC_AUTO, FC_MFMA, FC_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
@@ -115,6 +116,17 @@ class ImgConvDesc(ctypes.Structure):
 
 
 class ImgConvInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
+class DeconvDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "ic", "ih", "iw", "oc", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t",
+                                             "pad_l", "dst_dt", "bia_dt", "relu", "round_mode", "nscales", "force_path")]
+
+
+class DeconvInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
@@ -260,6 +272,12 @@ def lib():
         "dfx_imgconv_submit_host": (i32, [vp, vp, vp]),
         "dfx_imgconv_query": (i32, [vp, ctypes.POINTER(ImgConvInfo)]),
         "dfx_imgconv_destroy": (i32, [vp]),
+        "dfx_deconv_create": (i32, [ctypes.POINTER(DeconvDesc), ctypes.POINTER(vp)]),
+        "dfx_deconv_set_weights": (i32, [vp, vp, vp, vp]),
+        "dfx_deconv_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_deconv_submit_host": (i32, [vp, vp, vp]),
+        "dfx_deconv_query": (i32, [vp, ctypes.POINTER(DeconvInfo)]),
+        "dfx_deconv_destroy": (i32, [vp]),
         "dfx_fc_create": (i32, [ctypes.POINTER(FcDesc), ctypes.POINTER(vp)]),
         "dfx_fc_set_weights": (i32, [vp, vp, vp, vp]),
         "dfx_fc_submit": (i32, [vp, vp, vp, vp]),
@@ -280,6 +298,7 @@ def lib():
         "dfx_debug_dwconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_gconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_imgconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_debug_deconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwpw_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_fc_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
@@ -615,6 +634,44 @@ class ImageConv(_Handle):
         assert ws[0].size == d.oc * d.ic * d.kh * d.kw, ws[0].shape
         assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
         _check(lib().dfx_imgconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+
+def deconv_out_hw(ih, iw, kernel, stride, pad, output_padding=(0, 0)):
+    """the output size of a transposed conv with symmetric padding: (in - 1) * stride - 2 * pad + k + output_padding"""
+    return ((ih - 1) * stride[0] - 2 * pad[0] + kernel[0] + output_padding[0],
+            (iw - 1) * stride[1] - 2 * pad[1] + kernel[1] + output_padding[1])
+
+
+class Deconv(_Handle):
+    """dfx_deconv_* handle: int8 transposed conv over NHWC u8 (include/dfx.h), weights plain {oc, ic, kh, kw} (PyTorch's
+    ConvTranspose2d.weight is {ic, oc, kh, kw}: swap the first two axes).  The result equals GroupConv with groups = 1,
+    stride 1 and padding (kh-1-pad_t, kw-1-pad_l) on the zero-stuffed tensor with the spatially flipped weights, bit for
+    bit.  pad is {top, left}; out_hw defaults to (in - 1) * stride - 2 * pad + k; give it for output_padding or a crop."""
+
+    _OP, _INFO, _ROUTES = "dfx_deconv", DeconvInfo, 1
+
+    def __init__(self, src_shape_nhwc, oc, kernel, stride=(2, 2), pad=(0, 0), out_hw=None, dst_dt=DFX_U8, bia_dt=DFX_UNDEF,
+                 relu=False, rm=ROUND_NEAREST, nscales=1, force_path=DECONV_AUTO):
+        bs, ih, iw, ic = src_shape_nhwc
+        kh, kw = kernel
+        if out_hw is None:
+            out_hw = deconv_out_hw(ih, iw, kernel, stride, pad)
+        d = DeconvDesc(bs, ic, ih, iw, oc, out_hw[0], out_hw[1], kh, kw, stride[0], stride[1], pad[0], pad[1], dst_dt,
+                       bia_dt, int(relu), rm, nscales, force_path)
+        self.desc = d
+        self.src_shape = (bs, ih, iw, ic)
+        self.dst_shape = (bs, out_hw[0], out_hw[1], oc)
+        self.dst_np_dtype = _NP.get(dst_dt)
+        self._create(d)
+
+    def set_weights(self, wei, scales, bia=None):
+        """wei: int8 {oc, ic, kh, kw}; scales: 1 or oc floats; bia: oc entries of the descriptor's bias dtype"""
+        d = self.desc
+        ws = [np.ascontiguousarray(wei, dtype=np.int8), None if bia is None else np.ascontiguousarray(bia),
+              np.ascontiguousarray(scales, dtype=np.float32)]
+        assert ws[0].size == d.oc * d.ic * d.kh * d.kw, ws[0].shape
+        assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
+        _check(lib().dfx_deconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
 
 
 class InnerProduct(_Handle):

@@ -292,6 +292,24 @@ std::unique_ptr<op> image_conv(const std::unique_ptr<memory> &src,
                                bool relu = false, std::vector<float> scales = {1.f},
                                round_mode rm = round_mode::nearest);
 
+// ---- extension: int8 transposed conv ("deconvolution", dfx_deconv_* in dfx.h): the up-conv of U-Net / FPN decoders, pose
+// and CenterNet heads, DCGAN generators and the Mask R-CNN mask head.  src: nhwc u8; wei: plain oihw s8 of dims
+// {oc, ic, kh, kw} (oneDNN's logical order; PyTorch's ConvTranspose2d.weight is {ic, oc, kh, kw}); bia: format x, oc
+// entries, or null; dst: nhwc u8 / s8 / s32 / f32 with src's batch -- ITS height and width are the output size, at most
+// (in - 1) * stride + k - pad (this covers output_padding and cropping), as for image_conv(); padding is {top, left}, at
+// most k - 1.  Arithmetic, scales, ReLU and rounding are conv()'s: dst holds, bit for bit, what grouped_conv() with
+// groups = 1, stride 1 and padding k - 1 - pad gives on the zero-stuffed tensor with the spatially flipped weights.
+// Which shapes run on the sub-pixel int8-MFMA kernel and which on the generic one: DFX_DECONV_MFMA in dfx.h.  submit /
+// submit_async / wait, weight hashing and DEEPFUSION_DEVICES sharding are depthwise_conv()'s. ----
+std::unique_ptr<op> deconvolution(const std::unique_ptr<memory> &src,
+                                  const std::unique_ptr<memory> &wei,
+                                  const std::unique_ptr<memory> &bia,
+                                  std::array<int, 2> sz_stride,
+                                  std::array<int, 2> sz_padding,
+                                  std::unique_ptr<memory> &dst,
+                                  bool relu = false, std::vector<float> scales = {1.f},
+                                  round_mode rm = round_mode::nearest);
+
 // ---- extension: fully-connected (inner product) layer (dfx_fc_* in dfx.h): the classifier head of ResNet / VGG /
 // MobileNet, which conv() cannot express where oc is no multiple of 16 (the 1000-class heads).  src: nhwc u8
 // {bs, c, h, w}, exactly as the previous conv or pool op left it (h = w = 1: a plain vector); wei: plain oihw s8 of dims

@@ -341,6 +341,65 @@ typedef struct dfx_imgconv_info {
 } dfx_imgconv_info;
 typedef struct dfx_imgconv dfx_imgconv_t;
 
+/* ---- transposed conv ("deconvolution") on int8: the layer that makes feature maps larger (U-Net / FPN up-convs, pose
+ *      and CenterNet heads, DCGAN generators, the Mask R-CNN mask head).  src NHWC u8 {bs,ih,iw,ic}; wei s8
+ *      {oc,ic,kh,kw} plain row-major, the order of every other op here (PyTorch's ConvTranspose2d.weight is
+ *      {ic,oc,kh,kw}: swap the first two axes); dst NHWC {bs,oh,ow,oc}.
+ *        acc[n,oy,ox,o] = sum over i < ic, ky < kh, kx < kw
+ *                         with (oy + pad_t - ky) % sh == 0, iy = (oy + pad_t - ky) / sh in [0, ih)
+ *                         and  (ox + pad_l - kx) % sw == 0, ix = (ox + pad_l - kx) / sw in [0, iw)
+ *                         of   src[n,iy,ix,i] * w[o,i,ky,kx]
+ *        f = float(acc);  f = f + bias[o] (if any);  f = f * scale[o or 0];  ReLU (asked for, or dst is u8):
+ *        f = (0 > f) ? 0 : f;  dst = store(f, dst_dt, round_mode)
+ *      with the grouped op's arithmetic, word for word: exact s32 accumulator, separately rounded add and multiply,
+ *      the bias converted like the conv's, the x86 conversion (NaN / out of range -> 0x80000000 -> u8 255, s8 -128).
+ *      An output element that no tap reaches is requant(0).
+ *      Defining properties (tests/test_gpu_deconv.py):
+ *        1. the result equals, bit for bit, dfx_gconv with groups = 1, stride 1, padding (kh-1-pad_t, kw-1-pad_l), the
+ *           same oh / ow, on the zero-stuffed tensor {bs, (ih-1)*sh+1, (iw-1)*sw+1, ic} (src at the multiples of the
+ *           stride, 0 elsewhere) with the spatially flipped weights w[o,i,kh-1-ky,kw-1-kx];
+ *        2. where ic and oc are multiples of 16, kh-1-pad_t == kw-1-pad_l and oh / ow are the conv formula's, it equals
+ *           the unfused dfx_conv on the same stuffed tensor and flipped weights.
+ *      oh and ow are given by the caller as in dfx_gconv_desc (this covers output_padding and cropping):
+ *      1 <= oh <= (ih-1)*sh + kh - pad_t, likewise in x.  Parity unpinned: the reference has no such op. ---- */
+typedef struct dfx_deconv_desc {
+  int32_t bs, ic, ih, iw;
+  int32_t oc, oh, ow;          /* 1 <= oh <= (ih - 1) * sh + kh - pad_t, likewise in x */
+  int32_t kh, kw;              /* 1 .. 255; kh * kw * ic <= 65025 */
+  int32_t sh, sw;              /* 1 .. 255 */
+  int32_t pad_t, pad_l;        /* 0 .. kh - 1, 0 .. kw - 1 */
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t bia_dt;              /* DFX_UNDEF = none */
+  int32_t relu, round_mode;
+  int32_t nscales;             /* 1 or oc */
+  int32_t force_path;          /* -1 auto, else DFX_DECONV_* */
+} dfx_deconv_desc;
+enum {  /* dfx_deconv_info.path */
+  DFX_DECONV_MFMA = 0,         /* the sub-pixel int8-MFMA kernel (deconv.cuh), one launch: every output parity
+                                  ((oy + pad_t) % 2, (ox + pad_l) % 2) is a dense conv of the un-stuffed input with its
+                                  own sub-kernel.  Covers: stride (2,2); window 2x2 with pad 0, 4x4 with pad <= 3, or 3x3
+                                  with pad <= 2 (packed as a 4x4 window whose last row and column are zero: 16/9 of the
+                                  MACs); ic and oc multiples of 32; one output block's fragments in LDS:
+                                  128 * (kh > 2 ? 4 : 1) * ic + 21504 <= 163840 bytes (ic <= 1088 for 2x2, ic <= 256
+                                  for 3x3 / 4x4); one image below 2^31 bytes on either side.
+                                  AUTO RULE: auto takes it everywhere in this class: on the eight layers of
+                                  profiles/deconv/ inside the class it is 260 to 1350 times faster than the generic kernel
+                                  and 1.2 to 1.9 times faster than dfx_conv on a tensor stuffed in advance (DESIGN.md
+                                  section 4.12).  A 4x4 / 3x3 window with ic > 256 (DCGAN's 512 -> 256) is outside the
+                                  class and runs on the generic kernel, far slower than dfx_conv on a stuffed tensor. */
+  DFX_DECONV_GENERIC = 1       /* everything else: one thread per output element, the gather formula above, any window
+                                  / stride / padding / ic / oc, exact requant only */
+};
+typedef struct dfx_deconv_info {
+  int32_t path;
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2*MAC of one submit over the taps that exist (not those of the stuffed conv) */
+  uint64_t algorithmic_bytes;  /* src + weights + dst, src un-stuffed */
+  char kernel_name[96];        /* path, window, stride, ic, oc, dst type and requant route (valid after set_weights) */
+} dfx_deconv_info;
+typedef struct dfx_deconv dfx_deconv_t;
+
 /* ---- fully-connected (inner product) layer on int8: the classifier head the conv ops cannot express.  src NHWC u8
  *      {bs,ih,iw,ic} exactly as the previous conv or pool op wrote it (ih = iw = 1: a plain vector); wei s8
  *      {oc,ic,ih,iw} plain row-major, the flattened-CHW classifier frameworks keep (the library permutes it to src's
@@ -647,6 +706,28 @@ int dfx_imgconv_submit_host(dfx_imgconv_t *h, const void *src_host, void *dst_ho
 int dfx_imgconv_query(const dfx_imgconv_t *h, dfx_imgconv_info *info);
 int dfx_imgconv_destroy(dfx_imgconv_t *h);
 
+/* ---- transposed conv (dfx_deconv_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for a non-positive size, a window or stride outside 1 .. 255, a padding outside 0 .. k - 1,
+ *      kh * kw * ic > 65025, an output size outside 1 .. (in - 1) * stride + k - pad, a bad dtype / round mode /
+ *      nscales / force_path, a tensor of 2^31 pixels or more; DFX_ERR_UNSUPPORTED only for force_path =
+ *      DFX_DECONV_MFMA on a shape outside that class.  The op is total and delegates to no other op.  set_weights:
+ *      host pointers, copied; wei is s8 {oc, ic, kh, kw}; bia has oc entries of bia_dt (NULL when DFX_UNDEF); it may be
+ *      called again (not while a submit of the handle is in flight) and chooses the requant route exactly as
+ *      dfx_gconv_set_weights does (one proof, requant_host.h), from the channel's positive and negative weight sums over
+ *      ALL its ic * kh * kw taps -- every output sums a subset of them, so the bound holds for each: "fast" when, for
+ *      every output channel, bias and scale are finite and (255 * max(P, N) + |bias|) * |scale| <= 2^30, the round mode
+ *      is nearest and DFX_NO_FAST is not set; else "exact".  The generic kernel is always exact.  submit: asynchronous
+ *      on `s`; src and dst must be non-null and 16-byte aligned on the MFMA path, aligned to the element on the generic
+ *      path (DFX_ERR_INVALID otherwise, nothing is launched); DFX_ERR_STATE before set_weights.  Every launch has its
+ *      own copy of the arguments and submit never writes to the handle: one handle serves several streams and host
+ *      threads at once.  DFX_DECONV_GRID=n (tuning switch) caps the MFMA kernel's grid.  No CPU fallback. ---- */
+int dfx_deconv_create(const dfx_deconv_desc *desc, dfx_deconv_t **out);
+int dfx_deconv_set_weights(dfx_deconv_t *h, const int8_t *wei, const void *bia, const float *scales);
+int dfx_deconv_submit(dfx_deconv_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_deconv_submit_host(dfx_deconv_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_deconv_query(const dfx_deconv_t *h, dfx_deconv_info *info);
+int dfx_deconv_destroy(dfx_deconv_t *h);
+
 /* ---- fully-connected layer (dfx_fc_desc above).  The descriptor is validated before anything touches a device:
  *      DFX_ERR_INVALID for a non-positive size, ih * iw * ic > 65025, bs * oc of 2^31 or more, a bad dtype / round
  *      mode / nscales / force_path; DFX_ERR_UNSUPPORTED only for force_path = DFX_FC_MFMA where K is no multiple of
@@ -740,6 +821,8 @@ int dfx_debug_dwconv_requant(const dfx_dwconv_t *h, int32_t out[1]);
 int dfx_debug_gconv_requant(const dfx_gconv_t *h, int32_t out[1]);
 /* the first-layer conv's one stage, same numbering (0 exact, 1 fast) */
 int dfx_debug_imgconv_requant(const dfx_imgconv_t *h, int32_t out[1]);
+/* the transposed conv's one stage, same numbering (0 exact, 1 fast) */
+int dfx_debug_deconv_requant(const dfx_deconv_t *h, int32_t out[1]);
 /* the fully-connected op's one stage, same numbering (0 exact, 1 fast) */
 int dfx_debug_fc_requant(const dfx_fc_t *h, int32_t out[1]);
 /* the depthwise + pointwise op's two stages {route0, route1}, same numbering; on the two-launch path the routes of

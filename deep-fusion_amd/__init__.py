@@ -20,6 +20,7 @@ from .capi import (  # noqa: F401
     GCONV_AUTO, GCONV_MFMA, GCONV_GENERIC, GConvDesc, GConvInfo, GroupConv,
     IMGCONV_AUTO, IMGCONV_MFMA, IMGCONV_GENERIC, ImgConvDesc, ImgConvInfo, ImageConv,
     DECONV_AUTO, DECONV_MFMA, DECONV_GENERIC, DeconvDesc, DeconvInfo, Deconv, deconv_out_hw,
+    DILCONV_AUTO, DILCONV_MFMA, DILCONV_GENERIC, DilConvDesc, DilConvInfo, DilatedConv, dilconv_out_hw,
     FC_AUTO, FC_MFMA, FC_GENERIC, FcDesc, FcInfo, InnerProduct,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,

@@ -21,6 +21,7 @@ DWCONV_AUTO, DWCONV_WINDOW, DWCONV_GENERIC = -1, 0, 1
 GCONV_AUTO, GCONV_MFMA, GCONV_GENERIC = -1, 0, 1
 IMGCONV_AUTO, IMGCONV_MFMA, IMGCONV_GENERIC = -1, 0, 1
 DECONV_AUTO, DECONV_MFMA, DECONV_GENERIC = -1, 0, 1
+DILCONV_AUTO, DILCONV_MFMA, DILCONV_GENERIC = -1, 0, 1
 DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH = -1, 0, 1
 FC_AUTO, FC_MFMA, FC_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
@@ -127,6 +128,18 @@ class DeconvDesc(ctypes.Structure):
 
 
 class DeconvInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
+class DilConvDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "ic", "ih", "iw", "oc", "oh", "ow", "kh", "kw", "sh", "sw", "dh", "dw",
+                                             "pad_t", "pad_l", "dst_dt", "bia_dt", "relu", "round_mode", "nscales",
+                                             "force_path")]
+
+
+class DilConvInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
@@ -278,6 +291,12 @@ def lib():
         "dfx_deconv_submit_host": (i32, [vp, vp, vp]),
         "dfx_deconv_query": (i32, [vp, ctypes.POINTER(DeconvInfo)]),
         "dfx_deconv_destroy": (i32, [vp]),
+        "dfx_dilconv_create": (i32, [ctypes.POINTER(DilConvDesc), ctypes.POINTER(vp)]),
+        "dfx_dilconv_set_weights": (i32, [vp, vp, vp, vp]),
+        "dfx_dilconv_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_dilconv_submit_host": (i32, [vp, vp, vp]),
+        "dfx_dilconv_query": (i32, [vp, ctypes.POINTER(DilConvInfo)]),
+        "dfx_dilconv_destroy": (i32, [vp]),
         "dfx_fc_create": (i32, [ctypes.POINTER(FcDesc), ctypes.POINTER(vp)]),
         "dfx_fc_set_weights": (i32, [vp, vp, vp, vp]),
         "dfx_fc_submit": (i32, [vp, vp, vp, vp]),
@@ -299,6 +318,7 @@ def lib():
         "dfx_debug_gconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_imgconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_deconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_debug_dilconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwpw_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_fc_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
@@ -672,6 +692,44 @@ class Deconv(_Handle):
         assert ws[0].size == d.oc * d.ic * d.kh * d.kw, ws[0].shape
         assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
         _check(lib().dfx_deconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+
+def dilconv_out_hw(ih, iw, kernel, stride, dilation, pad):
+    """the output size of a dilated conv with symmetric padding: (in + 2 * pad - ((k - 1) * d + 1)) // stride + 1"""
+    return ((ih + 2 * pad[0] - ((kernel[0] - 1) * dilation[0] + 1)) // stride[0] + 1,
+            (iw + 2 * pad[1] - ((kernel[1] - 1) * dilation[1] + 1)) // stride[1] + 1)
+
+
+class DilatedConv(_Handle):
+    """dfx_dilconv_* handle: int8 dilated conv over NHWC u8 (include/dfx.h), weights plain oihw {oc, ic, kh, kw}.  The
+    result equals GroupConv with groups = 1 on the zero-stuffed ((k-1)*d+1)^2 window bit for bit, wherever that window can
+    be expressed.  pad is {top, left}; out_hw defaults to the conv formula's with the dilated extent; give it for windows
+    that hang over the bottom / right edge or a cropped output."""
+
+    _OP, _INFO, _ROUTES = "dfx_dilconv", DilConvInfo, 1
+
+    def __init__(self, src_shape_nhwc, oc, kernel, dilation=(1, 1), stride=(1, 1), pad=(0, 0), out_hw=None, dst_dt=DFX_U8,
+                 bia_dt=DFX_UNDEF, relu=False, rm=ROUND_NEAREST, nscales=1, force_path=DILCONV_AUTO):
+        bs, ih, iw, ic = src_shape_nhwc
+        kh, kw = kernel
+        if out_hw is None:
+            out_hw = dilconv_out_hw(ih, iw, kernel, stride, dilation, pad)
+        d = DilConvDesc(bs, ic, ih, iw, oc, out_hw[0], out_hw[1], kh, kw, stride[0], stride[1], dilation[0], dilation[1],
+                        pad[0], pad[1], dst_dt, bia_dt, int(relu), rm, nscales, force_path)
+        self.desc = d
+        self.src_shape = (bs, ih, iw, ic)
+        self.dst_shape = (bs, out_hw[0], out_hw[1], oc)
+        self.dst_np_dtype = _NP.get(dst_dt)
+        self._create(d)
+
+    def set_weights(self, wei, scales, bia=None):
+        """wei: int8 {oc, ic, kh, kw}; scales: 1 or oc floats; bia: oc entries of the descriptor's bias dtype"""
+        d = self.desc
+        ws = [np.ascontiguousarray(wei, dtype=np.int8), None if bia is None else np.ascontiguousarray(bia),
+              np.ascontiguousarray(scales, dtype=np.float32)]
+        assert ws[0].size == d.oc * d.ic * d.kh * d.kw, ws[0].shape
+        assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
+        _check(lib().dfx_dilconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
 
 
 class InnerProduct(_Handle):

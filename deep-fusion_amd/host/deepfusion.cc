@@ -1802,6 +1802,167 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- dilated conv (dfx_dilconv_*).  Checks are op_grouped_conv's; the weights are a plain oihw {oc, ic, kh, kw} tensor and
+// dst's dims give the output size.  Weight hashing and batch sharding are op_depthwise_conv's. ----
+class op_dilated_conv : public op {
+public:
+  op_dilated_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
+                std::array<int, 2> stride, std::array<int, 2> dilation, std::array<int, 2> padding, std::unique_ptr<memory> &dst, bool relu,
+                const std::vector<float> &scales, round_mode rm)
+      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0),
+        packed_versions_(0) {
+    using fmt = memory::format;
+    if (!src_ || !wei_ || !dst_) error_and_exit("Init DilatedConv op failed! (null tensor)");
+    if (src_->data_type() != memory::dtype::u8 || wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc ||
+        dst_->dim_format() != fmt::nhwc || wei_->dim_format() != fmt::oihw || (bia_ && bia_->dim_format() != fmt::x))
+      error_and_exit("Init DilatedConv op failed! (data type / format)");
+    auto i = src_->std_dims(), w = wei_->std_dims(), o = dst_->std_dims();
+    if (i[0] != o[0]) error_and_exit("Init DilatedConv op failed! (Batch size do not equal)");
+    if (w[0] != o[1] || w[1] != i[1]) error_and_exit("Init DilatedConv op failed! (weights must be {oc, ic, kh, kw})");
+    if (bia_ && (int)bia_->size() != o[1]) error_and_exit("Init DilatedConv op failed! (Bias channel do not match)");
+    dfx_dilconv_desc d;
+    memset(&d, 0, sizeof(d));
+    d.bs = i[0]; d.ic = i[1]; d.ih = i[2]; d.iw = i[3]; d.oc = o[1]; d.oh = o[2]; d.ow = o[3];
+    d.kh = w[2]; d.kw = w[3]; d.sh = stride[0]; d.sw = stride[1]; d.dh = dilation[0]; d.dw = dilation[1]; d.pad_t = padding[0]; d.pad_l = padding[1];
+    d.dst_dt = to_dfx_dtype(dst_->data_type());
+    d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
+    d.relu = relu;
+    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.nscales = (int)scales_.size();
+    d.force_path = -1;
+    src_img_ = (size_t)d.ih * d.iw * d.ic;
+    dst_img_ = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
+    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
+      shard sh;
+      sh.r = r;
+      dfx_dilconv_desc ds = d;
+      ds.bs = r.n;
+      check_dfx(dfx_set_device(r.device), "set device");
+      if (dfx_dilconv_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init DilatedConv op failed! (%s)", dfx_last_error());
+      check_dfx(dfx_stream_create(&sh.stream), "stream create");
+      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
+      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
+      shards_.push_back(sh);
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    if (dfx_dilconv_create(&d, &h_) != DFX_OK) error_and_exit("Init DilatedConv op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_dilated_conv() override {
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      dfx_dilconv_destroy(sh.h);
+      dfx_stream_destroy(sh.stream);
+      dfx_mem_free_device(sh.src);
+      dfx_mem_free_device(sh.dst);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire(*dst_);
+    dfx_dilconv_destroy(h_);
+  }
+
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  void submit_async() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(false);
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled(*dst_);
+    }
+  }
+
+protected:
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  unsigned long long weights_hash() {
+    using detail::hash_bytes;
+    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
+    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
+    return v | 1ull;
+  }
+  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
+  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
+    const unsigned long long v = weights_hash();
+    const char *hs = static_cast<const char *>(src_->host_data());
+    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      if (v != sh.wei_seen) {
+        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+        check_dfx(dfx_dilconv_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
+                  "dilated_conv set_weights");
+        sh.wei_seen = v;
+      }
+      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
+      check_dfx(dfx_dilconv_submit(sh.h, sh.src, sh.dst, sh.stream), "dilated_conv submit");
+      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    detail::op_state::host_is_current(*dst_);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
+    const unsigned long long vers = weights_versions();
+    if (sync_host || vers != packed_versions_) {
+      const unsigned long long hash = weights_hash();
+      if (hash != packed_hash_) {
+        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
+        check_dfx(dfx_dilconv_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
+                  "dilated_conv set_weights");
+        packed_hash_ = hash;
+      }
+      packed_versions_ = vers;
+    }
+    const void *in = st_.sync_in(*src_, sync_host);
+    void *o = st_.device_out(*dst_);
+    st_.profile_begin();
+    check_dfx(dfx_dilconv_submit(h_, in, o, st_.stream), "dilated_conv submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "dilated_conv"; }
+
+private:
+  struct shard {
+    detail::shard_range r;
+    dfx_dilconv_t *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    void *src = nullptr, *dst = nullptr;
+    unsigned long long wei_seen = 0;
+  };
+  memory *src_, *wei_, *bia_, *dst_;
+  std::vector<float> scales_;
+  dfx_dilconv_t *h_;
+  unsigned long long packed_hash_, packed_versions_;
+  size_t src_img_, dst_img_;  // bytes per image
+  detail::op_state st_;
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
+};
+
 // ---- fully-connected layer (dfx_fc_*): dst[n][o] = requant(sum over c, y, x of src[n][y][x][c] * wei[o][c][y][x]).  Checks
 // are op_grouped_conv's; the weights are a plain oihw {oc, c, h, w} tensor over the whole source image (a flattened-CHW
 // classifier), dst is {bs, oc, 1, 1}.  Weight hashing and batch sharding are op_depthwise_conv's. ----
@@ -2169,6 +2330,13 @@ std::unique_ptr<op> deconvolution(const std::unique_ptr<memory> &src, const std:
                                std::array<int, 2> sz_padding, std::unique_ptr<memory> &dst, bool relu,
                                std::vector<float> scales, round_mode rm) {
   return std::unique_ptr<op>(new op_deconvolution(src, wei, bia, sz_stride, sz_padding, dst, relu, scales, rm));
+}
+
+std::unique_ptr<op> dilated_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei,
+                                 const std::unique_ptr<memory> &bia, std::array<int, 2> sz_stride,
+                                 std::array<int, 2> sz_dilation, std::array<int, 2> sz_padding,
+                                 std::unique_ptr<memory> &dst, bool relu, std::vector<float> scales, round_mode rm) {
+  return std::unique_ptr<op>(new op_dilated_conv(src, wei, bia, sz_stride, sz_dilation, sz_padding, dst, relu, scales, rm));
 }
 
 std::unique_ptr<op> inner_product(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei,

@@ -310,6 +310,25 @@ std::unique_ptr<op> deconvolution(const std::unique_ptr<memory> &src,
                                   bool relu = false, std::vector<float> scales = {1.f},
                                   round_mode rm = round_mode::nearest);
 
+// ---- extension: int8 dilated ("atrous") conv (dfx_dilconv_* in dfx.h): the 3x3 of a DeepLab ASPP branch, of a dilated
+// ResNet's res4 / res5, of PSPNet / RFBNet context modules.  src: nhwc u8; wei: plain oihw s8 of dims {oc, ic, kh, kw};
+// bia: format x, oc entries, or null; dst: nhwc u8 / s8 / s32 / f32 with src's batch -- ITS height and width are the
+// output size, as for grouped_conv(); dilation is {dh, dw}, 1 = none; padding is {top, left}, at most (k - 1) * dilation.
+// Arithmetic, scales, ReLU and rounding are conv()'s: dst holds, bit for bit, what grouped_conv() with groups = 1 gives
+// on the zero-stuffed ((k - 1) * d + 1)^2 window -- where that window can be expressed at all (window * ic <= 65025) --
+// at 1 / ((k - 1) d + 1)^2 * k^2 of its MACs and weight bytes.  Which shapes run on the K-slabbed int8-MFMA kernel and
+// which on the generic one: DFX_DILCONV_MFMA in dfx.h.  submit / submit_async / wait, weight hashing and
+// DEEPFUSION_DEVICES sharding are depthwise_conv()'s. ----
+std::unique_ptr<op> dilated_conv(const std::unique_ptr<memory> &src,
+                                 const std::unique_ptr<memory> &wei,
+                                 const std::unique_ptr<memory> &bia,
+                                 std::array<int, 2> sz_stride,
+                                 std::array<int, 2> sz_dilation,
+                                 std::array<int, 2> sz_padding,
+                                 std::unique_ptr<memory> &dst,
+                                 bool relu = false, std::vector<float> scales = {1.f},
+                                 round_mode rm = round_mode::nearest);
+
 // ---- extension: fully-connected (inner product) layer (dfx_fc_* in dfx.h): the classifier head of ResNet / VGG /
 // MobileNet, which conv() cannot express where oc is no multiple of 16 (the 1000-class heads).  src: nhwc u8
 // {bs, c, h, w}, exactly as the previous conv or pool op left it (h = w = 1: a plain vector); wei: plain oihw s8 of dims

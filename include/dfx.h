@@ -400,6 +400,63 @@ typedef struct dfx_deconv_info {
 } dfx_deconv_info;
 typedef struct dfx_deconv dfx_deconv_t;
 
+/* ---- dilated ("atrous") conv on int8: the 3x3 of a DeepLab ASPP branch, of a dilated ResNet's res4 / res5, of the
+ *      context modules of PSPNet / RFBNet / SSD's fc6.  src NHWC u8 {bs,ih,iw,ic}; wei s8 {oc,ic,kh,kw} plain
+ *      row-major; dst NHWC {bs,oh,ow,oc}; any ic, oc >= 1.
+ *        acc[n,oy,ox,o] = sum over i < ic, ky < kh, kx < kw of
+ *                         src[n, oy*sh - pad_t + ky*dh, ox*sw - pad_l + kx*dw, i] * w[o,i,ky,kx]
+ *                         (taps outside the input are skipped)
+ *        f = float(acc);  f = f + bias[o] (if any);  f = f * scale[o or 0];  ReLU (asked for, or dst is u8):
+ *        f = (0 > f) ? 0 : f;  dst = store(f, dst_dt, round_mode)
+ *      with the grouped op's arithmetic, word for word: exact s32 accumulator, separately rounded add and multiply,
+ *      the bias converted like the conv's, the x86 conversion (NaN / out of range -> 0x80000000 -> u8 255, s8 -128).
+ *      Defining properties (tests/test_gpu_dilconv.py), with the zero-stuffed weights wz[o,i,ky*dh,kx*dw] = w[o,i,ky,kx],
+ *      0 elsewhere, a ((kh-1)*dh+1) x ((kw-1)*dw+1) window:
+ *        1. the result equals, bit for bit, dfx_gconv with groups = 1 on wz, same stride, padding and oh / ow, wherever
+ *           that descriptor is valid (its window * ic <= 65025);
+ *        2. where additionally ic and oc are multiples of 16 and oh / ow follow the conv formula it equals the unfused
+ *           dfx_conv on wz;
+ *        3. with dh = dw = 1 it equals dfx_gconv (groups = 1) on the same tensors.
+ *      oh and ow are given by the caller as in dfx_gconv_desc, with the dilated extent.  Parity unpinned: the
+ *      reference has no such op. ---- */
+typedef struct dfx_dilconv_desc {
+  int32_t bs, ic, ih, iw;
+  int32_t oc, oh, ow;          /* (oh - 1) * sh - pad_t <= ih - 1, likewise in x */
+  int32_t kh, kw;              /* 1 .. 255; kh * kw * ic <= 65025 (the taps that exist, not the stuffed window) */
+  int32_t sh, sw;              /* 1 .. 255 */
+  int32_t dh, dw;              /* 1 .. 255; 1 = no dilation */
+  int32_t pad_t, pad_l;        /* 0 .. (kh - 1) * dh, 0 .. (kw - 1) * dw */
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t bia_dt;              /* DFX_UNDEF = none */
+  int32_t relu, round_mode;
+  int32_t nscales;             /* 1 or oc */
+  int32_t force_path;          /* -1 auto, else DFX_DILCONV_* */
+} dfx_dilconv_desc;
+enum {  /* dfx_dilconv_info.path */
+  DFX_DILCONV_MFMA = 0,        /* the int8-MFMA kernel (dilconv.cuh), one launch: dilation is an address offset of the
+                                  activation loads, the weights stream through LDS in K-slabs.  Covers: 3x3 window;
+                                  stride (1,1); any dh, dw; any padding the descriptor admits; ic and oc multiples of 32
+                                  with NO further cap on ic (9 * ic <= 65025 is the descriptor's own); one image below
+                                  2^31 bytes on either side.
+                                  AUTO RULE: auto takes it everywhere in this class: on the 16 points of
+                                  profiles/dilconv/ (ASPP on ResNet-50 and MobileNetV2 at d 6 / 12 / 18, dilated ResNet res4
+                                  / res5, N = 1 and 16) it is 23 to 1094 times faster than the generic kernel.  Against
+                                  dfx_conv on zero-stuffed weights, where that can be expressed at all (6 of the 16), it
+                                  is 1.3 to 12 times faster on five and 16 % slower on one (res4, d 2, N = 1).  640 to
+                                  1036 TOP/s at N = 16, 4.9 to 7.9 times the matrix floor. */
+  DFX_DILCONV_GENERIC = 1      /* everything else: one thread per output element, the formula above, any window / stride
+                                  / dilation / padding / ic / oc, exact requant only */
+};
+typedef struct dfx_dilconv_info {
+  int32_t path;
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2*MAC of one submit: 2 * kh * kw * ic per output value (not the stuffed window's) */
+  uint64_t algorithmic_bytes;  /* src + weights + dst, weights un-stuffed */
+  char kernel_name[96];        /* path, window, dilation, ic, oc, dst type and requant route (valid after set_weights) */
+} dfx_dilconv_info;
+typedef struct dfx_dilconv dfx_dilconv_t;
+
 /* ---- fully-connected (inner product) layer on int8: the classifier head the conv ops cannot express.  src NHWC u8
  *      {bs,ih,iw,ic} exactly as the previous conv or pool op wrote it (ih = iw = 1: a plain vector); wei s8
  *      {oc,ic,ih,iw} plain row-major, the flattened-CHW classifier frameworks keep (the library permutes it to src's
@@ -728,6 +785,28 @@ int dfx_deconv_submit_host(dfx_deconv_t *h, const void *src_host, void *dst_host
 int dfx_deconv_query(const dfx_deconv_t *h, dfx_deconv_info *info);
 int dfx_deconv_destroy(dfx_deconv_t *h);
 
+/* ---- dilated conv (dfx_dilconv_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for a non-positive size, a window, stride or dilation outside 1 .. 255, a padding outside
+ *      0 .. (k - 1) * d, kh * kw * ic > 65025, an output row / column whose window starts below / right of the input, a
+ *      bad dtype / round mode / nscales / force_path, a tensor of 2^31 pixels or more; DFX_ERR_UNSUPPORTED only for
+ *      force_path = DFX_DILCONV_MFMA on a shape outside that class.  The op is total and delegates to no other op.
+ *      set_weights: host pointers, copied; wei is s8 {oc, ic, kh, kw}; bia has oc entries of bia_dt (NULL when
+ *      DFX_UNDEF); it may be called again (not while a submit of the handle is in flight) and chooses the requant route
+ *      exactly as dfx_gconv_set_weights does (one proof, requant_host.h) over the channel's ic * kh * kw taps: "fast"
+ *      when, for every output channel, bias and scale are finite and (255 * max(P, N) + |bias|) * |scale| <= 2^30, the
+ *      round mode is nearest and DFX_NO_FAST is not set; else "exact".  The generic kernel is always exact.  submit:
+ *      asynchronous on `s`; src and dst must be non-null and 16-byte aligned on the MFMA path, dst aligned to its
+ *      element on the generic path (DFX_ERR_INVALID otherwise, nothing is launched); DFX_ERR_STATE before set_weights.
+ *      Every launch has its own copy of the arguments and submit never writes to the handle: one handle serves several
+ *      streams and host threads at once.  Tuning switches: DFX_DILCONV_GRID=n caps the MFMA kernel's grid,
+ *      DFX_DILCONV_SLAB=n sets the K-steps per weight slab (clamped to what LDS holds).  No CPU fallback. ---- */
+int dfx_dilconv_create(const dfx_dilconv_desc *desc, dfx_dilconv_t **out);
+int dfx_dilconv_set_weights(dfx_dilconv_t *h, const int8_t *wei, const void *bia, const float *scales);
+int dfx_dilconv_submit(dfx_dilconv_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_dilconv_submit_host(dfx_dilconv_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_dilconv_query(const dfx_dilconv_t *h, dfx_dilconv_info *info);
+int dfx_dilconv_destroy(dfx_dilconv_t *h);
+
 /* ---- fully-connected layer (dfx_fc_desc above).  The descriptor is validated before anything touches a device:
  *      DFX_ERR_INVALID for a non-positive size, ih * iw * ic > 65025, bs * oc of 2^31 or more, a bad dtype / round
  *      mode / nscales / force_path; DFX_ERR_UNSUPPORTED only for force_path = DFX_FC_MFMA where K is no multiple of
@@ -823,6 +902,8 @@ int dfx_debug_gconv_requant(const dfx_gconv_t *h, int32_t out[1]);
 int dfx_debug_imgconv_requant(const dfx_imgconv_t *h, int32_t out[1]);
 /* the transposed conv's one stage, same numbering (0 exact, 1 fast) */
 int dfx_debug_deconv_requant(const dfx_deconv_t *h, int32_t out[1]);
+/* the dilated conv's one stage, same numbering (0 exact, 1 fast) */
+int dfx_debug_dilconv_requant(const dfx_dilconv_t *h, int32_t out[1]);
 /* the fully-connected op's one stage, same numbering (0 exact, 1 fast) */
 int dfx_debug_fc_requant(const dfx_fc_t *h, int32_t out[1]);
 /* the depthwise + pointwise op's two stages {route0, route1}, same numbering; on the two-launch path the routes of

@@ -21,6 +21,8 @@ from .capi import (  # noqa: F401
     IMGCONV_AUTO, IMGCONV_MFMA, IMGCONV_GENERIC, ImgConvDesc, ImgConvInfo, ImageConv,
     DECONV_AUTO, DECONV_MFMA, DECONV_GENERIC, DeconvDesc, DeconvInfo, Deconv, deconv_out_hw,
     DILCONV_AUTO, DILCONV_MFMA, DILCONV_GENERIC, DilConvDesc, DilConvInfo, DilatedConv, dilconv_out_hw,
+    RESIZE_AUTO, RESIZE_BAND, RESIZE_GENERIC, RESIZE_NEAREST, RESIZE_BILINEAR, COORD_HALF_PIXEL, COORD_ALIGN_CORNERS,
+    COORD_ASYMMETRIC, ResizeDesc, ResizeInfo, Resize,
     FC_AUTO, FC_MFMA, FC_GENERIC, FcDesc, FcInfo, InnerProduct,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,

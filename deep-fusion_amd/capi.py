@@ -23,6 +23,9 @@ IMGCONV_AUTO, IMGCONV_MFMA, IMGCONV_GENERIC = -1, 0, 1
 DECONV_AUTO, DECONV_MFMA, DECONV_GENERIC = -1, 0, 1
 DILCONV_AUTO, DILCONV_MFMA, DILCONV_GENERIC = -1, 0, 1
 DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH = -1, 0, 1
+RESIZE_AUTO, RESIZE_BAND, RESIZE_GENERIC = -1, 0, 1
+RESIZE_NEAREST, RESIZE_BILINEAR = 0, 1
+COORD_HALF_PIXEL, COORD_ALIGN_CORNERS, COORD_ASYMMETRIC = 0, 1, 2
 FC_AUTO, FC_MFMA, FC_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
@@ -143,6 +146,16 @@ class DilConvInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
+
+
+class ResizeDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "dt", "algo", "coord", "add", "post_relu",
+                                             "force_path")]
+
+
+class ResizeInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device", "rows_per_lane")] + \
+               [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
 
 
 class FcDesc(ctypes.Structure):
@@ -297,6 +310,11 @@ def lib():
         "dfx_dilconv_submit_host": (i32, [vp, vp, vp]),
         "dfx_dilconv_query": (i32, [vp, ctypes.POINTER(DilConvInfo)]),
         "dfx_dilconv_destroy": (i32, [vp]),
+        "dfx_resize_create": (i32, [ctypes.POINTER(ResizeDesc), ctypes.POINTER(vp)]),
+        "dfx_resize_submit": (i32, [vp, vp, vp, vp, vp]),
+        "dfx_resize_submit_host": (i32, [vp, vp, vp, vp]),
+        "dfx_resize_query": (i32, [vp, ctypes.POINTER(ResizeInfo)]),
+        "dfx_resize_destroy": (i32, [vp]),
         "dfx_fc_create": (i32, [ctypes.POINTER(FcDesc), ctypes.POINTER(vp)]),
         "dfx_fc_set_weights": (i32, [vp, vp, vp, vp]),
         "dfx_fc_submit": (i32, [vp, vp, vp, vp]),
@@ -321,6 +339,7 @@ def lib():
         "dfx_debug_dilconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwpw_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_fc_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_debug_resize_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -337,6 +356,13 @@ def lib():
 def set_tuning(key, value):
     """testing / tuning switch of the library; value None clears it."""
     _check(lib().dfx_debug_set_tuning(key.encode(), None if value is None else str(value).encode()))
+
+
+def resize_launches():
+    """(band, generic): dfx_resize_submit calls of this process that launched each kernel (dfx_debug_resize_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_resize_launches(v))
+    return v[RESIZE_BAND], v[RESIZE_GENERIC]
 
 
 def _check(rc):
@@ -730,6 +756,38 @@ class DilatedConv(_Handle):
         assert ws[0].size == d.oc * d.ic * d.kh * d.kw, ws[0].shape
         assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
         _check(lib().dfx_dilconv_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+
+class Resize(_Handle):
+    """dfx_resize_* handle: nearest / bilinear resize of an NHWC tensor to (oh, ow), optionally with a tensor of dst's
+    shape added in the same launch (include/dfx.h).  The index and weight tables are the library's (csrc/resize_plan.h)."""
+
+    _OP, _INFO = "dfx_resize", ResizeInfo
+
+    def __init__(self, src_shape_nhwc, out_hw, np_dtype, algo=RESIZE_BILINEAR, coord=COORD_HALF_PIXEL, add=False,
+                 post_relu=False, force_path=RESIZE_AUTO):
+        bs, ih, iw, c = src_shape_nhwc
+        dt = np_dtype if isinstance(np_dtype, int) else _DT[np.dtype(np_dtype)]
+        d = ResizeDesc(bs, c, ih, iw, out_hw[0], out_hw[1], dt, algo, coord, int(add), int(post_relu), force_path)
+        self.desc = d
+        self.src_shape = (bs, ih, iw, c)
+        self.dst_shape = (bs, out_hw[0], out_hw[1], c)
+        self.src_np_dtype = self.dst_np_dtype = _NP[dt]
+        self._create(d)
+
+    def submit(self, src_dev, dst_dev, add_dev=None, stream=None):
+        """asynchronous; add_dev is given exactly when the handle was made with add=True and may be dst_dev"""
+        _check(lib().dfx_resize_submit(self._h, _dev_ptr(src_dev), None if add_dev is None else _dev_ptr(add_dev),
+                                       _dev_ptr(dst_dev), _stream_ptr(stream)))
+
+    def submit_host(self, src_np, add_np=None):
+        src = np.ascontiguousarray(src_np, dtype=self.src_np_dtype)
+        assert src.shape == self.src_shape, (src.shape, self.src_shape)
+        add = None if add_np is None else np.ascontiguousarray(add_np, dtype=self.dst_np_dtype)
+        assert add is None or add.shape == self.dst_shape, (add.shape, self.dst_shape)
+        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
+        _check(lib().dfx_resize_submit_host(self._h, _p(src), _p(add), _p(dst)))
+        return dst
 
 
 class InnerProduct(_Handle):

@@ -128,6 +128,26 @@ struct EltwiseArgs {
   long long elems;
 };
 
+// eltwise sum: accumulator type and the saturating finish (+ ReLU).  Shared by pool_eltwise.hip and the fused add of
+// resize.cuh, which is dfx_eltwise's arithmetic word for word.
+template <typename T> struct EltAcc { typedef int type; };                 // 1-byte types: <= 8 x 255 fits an int
+template <> struct EltAcc<int> { typedef long long type; };
+template <> struct EltAcc<float> { typedef float type; };
+
+template <typename T>
+__device__ __forceinline__ T elt_finish(typename EltAcc<T>::type v, bool relu);
+template <> __device__ __forceinline__ float elt_finish<float>(float v, bool relu) { return relu ? relu_x86(v) : v; }
+template <> __device__ __forceinline__ int elt_finish<int>(long long v, bool relu) {
+  if (relu && v < 0) v = 0;
+  return (int)(v < -2147483648LL ? -2147483648LL : (v > 2147483647LL ? 2147483647LL : v));
+}
+template <> __device__ __forceinline__ signed char elt_finish<signed char>(int v, bool relu) {
+  return (signed char)min(127, max(relu ? 0 : -128, v));
+}
+template <> __device__ __forceinline__ unsigned char elt_finish<unsigned char>(int v, bool) {
+  return (unsigned char)min(255, v);  // (sums of u8 are never negative: relu is the identity)
+}
+
 // kernel arguments of reorder.hip (filled by reorder_api.hip)
 constexpr int SMALLC_PX = 1024;  // pixels per workgroup of the smallc kernel
 enum { REORDER_FLAT = 0, REORDER_GENERIC = 1, REORDER_SMALLC = 2, REORDER_TRANSPOSE = 3 };

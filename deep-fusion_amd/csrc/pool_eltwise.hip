@@ -137,24 +137,7 @@ int launch_pool(const PoolArgs &a, hipStream_t s) {
 }
 
 // ---- eltwise sum ----
-template <typename T> struct EltAcc { typedef int type; };                 // 1-byte types: <= 8 x 255 fits an int
-template <> struct EltAcc<int> { typedef long long type; };
-template <> struct EltAcc<float> { typedef float type; };
-
-template <typename T>
-__device__ __forceinline__ T elt_finish(typename EltAcc<T>::type v, bool relu);
-template <> __device__ __forceinline__ float elt_finish<float>(float v, bool relu) { return relu ? relu_x86(v) : v; }
-template <> __device__ __forceinline__ int elt_finish<int>(long long v, bool relu) {
-  if (relu && v < 0) v = 0;
-  return (int)(v < -2147483648LL ? -2147483648LL : (v > 2147483647LL ? 2147483647LL : v));
-}
-template <> __device__ __forceinline__ signed char elt_finish<signed char>(int v, bool relu) {
-  return (signed char)min(127, max(relu ? 0 : -128, v));
-}
-template <> __device__ __forceinline__ unsigned char elt_finish<unsigned char>(int v, bool) {
-  return (unsigned char)min(255, v);  // (sums of u8 are never negative: relu is the identity)
-}
-
+// (EltAcc / elt_finish, the sum's accumulator and its saturating finish, are in dfx_device.cuh: resize.cuh adds with them too)
 template <typename T, int N>  // N elements starting at e0: 16 bytes (N = 16 / sizeof(T)) or one element
 __device__ __forceinline__ void eltwise_item(const EltwiseArgs &a, long long e0) {
   typename EltAcc<T>::type acc[N];

@@ -2124,6 +2124,143 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- activation resize (dfx_resize_*), optionally with a lateral tensor added in the same launch.  No weights: nothing to
+// hash or pack.  Batch sharding is op_depthwise_conv's; the lateral is sharded like dst, whose dims it has. ----
+class op_resize : public op {
+public:
+  op_resize(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> *lateral, std::unique_ptr<memory> &dst, resize_algo algo,
+            resize_coord coord, bool post_relu)
+      : src_(src.get()), lat_(lateral ? lateral->get() : nullptr), dst_(dst.get()), h_(nullptr) {
+    using fmt = memory::format;
+    if (!src_ || !dst_ || (lateral && !lat_)) error_and_exit("Init Resize op failed! (null tensor)");
+    if (src_->dim_format() != fmt::nhwc || dst_->dim_format() != fmt::nhwc || src_->data_type() != dst_->data_type())
+      error_and_exit("Init Resize op failed! (data type / format)");
+    auto i = src_->std_dims(), o = dst_->std_dims();
+    if (i[0] != o[0]) error_and_exit("Init Resize op failed! (Batch size do not equal)");
+    if (i[1] != o[1]) error_and_exit("Init Resize op failed! (Channel do not match)");
+    if (lat_ && (lat_->dim_format() != fmt::nhwc || lat_->data_type() != dst_->data_type() || lat_->std_dims() != o))
+      error_and_exit("Init Resize op failed! (the lateral must have dst's dims, format and data type)");
+    if (src_ == dst_) error_and_exit("Init Resize op failed! (dst must not be src)");
+    dfx_resize_desc d;
+    memset(&d, 0, sizeof(d));
+    d.bs = i[0]; d.c = i[1]; d.ih = i[2]; d.iw = i[3]; d.oh = o[2]; d.ow = o[3];
+    d.dt = to_dfx_dtype(dst_->data_type());
+    d.algo = algo == resize_algo::nearest ? DFX_RESIZE_NEAREST : DFX_RESIZE_BILINEAR;
+    d.coord = coord == resize_coord::half_pixel ? DFX_COORD_HALF_PIXEL
+              : coord == resize_coord::align_corners ? DFX_COORD_ALIGN_CORNERS : DFX_COORD_ASYMMETRIC;
+    d.add = lat_ ? 1 : 0;
+    d.post_relu = post_relu ? 1 : 0;
+    d.force_path = -1;
+    src_img_ = (size_t)d.ih * d.iw * d.c * dtype_size(src_->data_type());
+    dst_img_ = (size_t)d.oh * d.ow * d.c * dtype_size(dst_->data_type());
+    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
+      shard sh;
+      sh.r = r;
+      dfx_resize_desc ds = d;
+      ds.bs = r.n;
+      check_dfx(dfx_set_device(r.device), "set device");
+      if (dfx_resize_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init Resize op failed! (%s)", dfx_last_error());
+      check_dfx(dfx_stream_create(&sh.stream), "stream create");
+      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
+      if (lat_) check_dfx(dfx_mem_alloc_device(&sh.lat, (size_t)r.n * dst_img_), "device alloc");
+      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
+      shards_.push_back(sh);
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    if (dfx_resize_create(&d, &h_) != DFX_OK) error_and_exit("Init Resize op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_resize() override {
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      dfx_resize_destroy(sh.h);
+      dfx_stream_destroy(sh.stream);
+      dfx_mem_free_device(sh.src);
+      dfx_mem_free_device(sh.lat);
+      dfx_mem_free_device(sh.dst);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire(*dst_);
+    dfx_resize_destroy(h_);
+  }
+
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  void submit_async() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(false);
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled(*dst_);
+    }
+  }
+
+protected:
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
+    const char *hs = static_cast<const char *>(src_->host_data());
+    const char *hl = lat_ ? static_cast<const char *>(lat_->host_data()) : nullptr;
+    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
+      if (lat_) check_dfx(dfx_memcpy_h2d(sh.lat, hl + sh.r.n0 * dst_img_, sh.r.n * dst_img_, sh.stream), "H2D copy");
+      check_dfx(dfx_resize_submit(sh.h, sh.src, sh.lat, sh.dst, sh.stream), "resize submit");
+      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    detail::op_state::host_is_current(*dst_);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  void run(bool sync_host) {
+    const void *in = st_.sync_in(*src_, sync_host);
+    const void *lat = lat_ ? st_.sync_in(*lat_, sync_host) : nullptr;  // (the lateral may be dst: uploaded, then overwritten)
+    void *o = st_.device_out(*dst_);
+    st_.profile_begin();
+    check_dfx(dfx_resize_submit(h_, in, lat, o, st_.stream), "resize submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return lat_ ? "resize_add" : "resize"; }
+
+private:
+  struct shard {
+    detail::shard_range r;
+    dfx_resize_t *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    void *src = nullptr, *lat = nullptr, *dst = nullptr;
+  };
+  memory *src_, *lat_, *dst_;
+  dfx_resize_t *h_;
+  size_t src_img_, dst_img_;  // bytes per image
+  detail::op_state st_;
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
+};
+
 // ---- depthwise + pointwise conv (dfx_dwpw_*): depthwise_conv() with a u8 result followed by a 1x1 conv(), behind one
 // handle.  force_path stays -1 (auto), so the path is the library's choice (dfx.h, AUTO RULE at DFX_DWPW_FUSED).  The depthwise weights are a plain oihw
 // {c, 1, kh, kw} tensor, the pointwise weights OIhw4i16o4i {oc, c, 1, 1}; dst's dims give the output size. ----
@@ -2337,6 +2474,15 @@ std::unique_ptr<op> dilated_conv(const std::unique_ptr<memory> &src, const std::
                                  std::array<int, 2> sz_dilation, std::array<int, 2> sz_padding,
                                  std::unique_ptr<memory> &dst, bool relu, std::vector<float> scales, round_mode rm) {
   return std::unique_ptr<op>(new op_dilated_conv(src, wei, bia, sz_stride, sz_dilation, sz_padding, dst, relu, scales, rm));
+}
+
+std::unique_ptr<op> resize(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst, resize_algo algo, resize_coord coord) {
+  return std::unique_ptr<op>(new op_resize(src, nullptr, dst, algo, coord, false));
+}
+
+std::unique_ptr<op> resize_add(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &lateral,
+                               std::unique_ptr<memory> &dst, resize_algo algo, resize_coord coord, bool post_relu) {
+  return std::unique_ptr<op>(new op_resize(src, &lateral, dst, algo, coord, post_relu));
 }
 
 std::unique_ptr<op> inner_product(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei,

@@ -329,6 +329,25 @@ std::unique_ptr<op> dilated_conv(const std::unique_ptr<memory> &src,
                                  bool relu = false, std::vector<float> scales = {1.f},
                                  round_mode rm = round_mode::nearest);
 
+// ---- extension: activation resize (dfx_resize_* in dfx.h): nearest or bilinear interpolation of an nhwc feature map to
+// dst's height and width -- FPN's nearest x2, DeepLab's and PSPNet's bilinear upsampling, bilinear U-Net decoders.  src
+// and dst: nhwc of one dtype (u8 / s8 / f32; s32 with nearest only) with the same batch and channels.  The index and
+// weight arithmetic is dfx.h's, exact integers per axis and separately rounded f32 operations; u8 / s8 results are
+// rounded to nearest even.  resize_add() adds `lateral` (dst's dims and dtype; it may BE dst) in the same launch with
+// eltwise_sum()'s arithmetic: dst holds, bit for bit, what resize() followed by eltwise_sum({resized, lateral}) gives.
+// submit / submit_async / wait and DEEPFUSION_DEVICES sharding over the batch are depthwise_conv()'s. ----
+enum class resize_algo { nearest = 0, bilinear };
+enum class resize_coord {
+  half_pixel = 0,  // PyTorch align_corners=False / 'nearest-exact'
+  align_corners,
+  asymmetric,      // PyTorch's legacy 'nearest', Caffe / TF1
+};
+std::unique_ptr<op> resize(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst,
+                           resize_algo algo = resize_algo::bilinear, resize_coord coord = resize_coord::half_pixel);
+std::unique_ptr<op> resize_add(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &lateral,
+                               std::unique_ptr<memory> &dst, resize_algo algo = resize_algo::nearest,
+                               resize_coord coord = resize_coord::asymmetric, bool post_relu = false);
+
 // ---- extension: fully-connected (inner product) layer (dfx_fc_* in dfx.h): the classifier head of ResNet / VGG /
 // MobileNet, which conv() cannot express where oc is no multiple of 16 (the 1000-class heads).  src: nhwc u8
 // {bs, c, h, w}, exactly as the previous conv or pool op left it (h = w = 1: a plain vector); wei: plain oihw s8 of dims

@@ -457,6 +457,71 @@ typedef struct dfx_dilconv_info {
 } dfx_dilconv_info;
 typedef struct dfx_dilconv dfx_dilconv_t;
 
+/* ---- activation resize: nearest / bilinear interpolation of an NHWC feature map, optionally with a lateral tensor added
+ *      in the same launch: FPN's "nearest x2, add the lateral", DeepLab's / PSPNet's bilinear upsampling, bilinear U-Net
+ *      decoders.  src NHWC {bs,ih,iw,c}; dst NHWC {bs,oh,ow,c} of the same dtype; oh and ow are given by the caller.  All
+ *      four sizes lie in 1 .. 65535, so that every remainder and denominator below is < 2^24 and float(.) of it exact.
+ *      c >= 1.  dtype: u8 / s8 / f32; nearest also takes s32 (it is a copy).
+ *      PER-AXIS PLAN, the same for y and x (in, out: the axis's sizes; o: output index).  Exact integer arithmetic, done
+ *      once on the host at create time (csrc/resize_plan.h) and uploaded as tables; the kernels only read tables.
+ *                                                                              num(o)            den
+ *        DFX_COORD_HALF_PIXEL     (PyTorch align_corners=False, nearest-exact) (2o+1)*in - out   2*out
+ *        DFX_COORD_ALIGN_CORNERS                                               o*(in-1)          out-1  (out == 1: 0, 1)
+ *        DFX_COORD_ASYMMETRIC     (PyTorch legacy 'nearest', Caffe / TF1)      o*in              out
+ *        bilinear: num = max(num, 0); i0 = min(num / den, in-1); i1 = min(i0+1, in-1);
+ *                  w1 = float(num % den) / float(den) (ONE IEEE f32 division); w0 = 1.0f - w1
+ *        nearest:  i0 = i1 = min(idx, in-1), w0 = 1, w1 = 0, with idx = ((2o+1)*in) / (2*out) (HALF_PIXEL),
+ *                  (o*in) / out (ASYMMETRIC), (2*num + den) / (2*den) (ALIGN_CORNERS: round half up)
+ *      VALUE.  Bilinear, with v = float(src) (exact for u8 / s8), every multiply and add rounded separately (never an FMA):
+ *        top = v[y0,x0]*wx0 + v[y0,x1]*wx1;  bot = v[y1,x0]*wx0 + v[y1,x1]*wx1;  out = top*wy0 + bot*wy1
+ *      f32 dst stores out; u8 / s8 dst stores rint(out) (ties to even) clamped to the dtype's range (the reorder's
+ *      conversion).  f32 specials follow the formula: Inf * 0 is NaN, denormals are kept, and -0*1 + x*0 is +0, so an
+ *      identity-size bilinear resize of f32 is NOT a bit copy.  Nearest copies src[y0,x0] bit for bit, NaN payloads
+ *      included.
+ *      FUSED ADD (add != 0): dst = eltwise_sum(resized, add_tensor) with dfx_eltwise's arithmetic, word for word: the
+ *      resized value is first converted to the dtype as above, then an exact integer sum saturated to the dtype, or the
+ *      f32 sum resized + add in that operand order, then ReLU if post_relu.  add_tensor has dst's shape and dtype and may
+ *      BE dst (in place); an add range that overlaps dst's in any other way is refused.  dst must not overlap src.
+ *      Defining properties (tests/test_gpu_resize.py): nearest at an integer factor s equals dfx_deconv with identity
+ *      weights (stride s, window s x s); bilinear HALF_PIXEL at oh = ih/2, ow = iw/2 equals dfx_pool's 2x2 / 2 average;
+ *      resize + add equals dfx_resize followed by dfx_eltwise.  Parity unpinned: the reference has no such op. ---- */
+enum { DFX_RESIZE_NEAREST = 0, DFX_RESIZE_BILINEAR = 1 };                             /* dfx_resize_desc.algo */
+enum { DFX_COORD_HALF_PIXEL = 0, DFX_COORD_ALIGN_CORNERS = 1, DFX_COORD_ASYMMETRIC = 2 }; /* dfx_resize_desc.coord */
+typedef struct dfx_resize_desc {
+  int32_t bs, c, ih, iw;
+  int32_t oh, ow;              /* 1 .. 65535, like ih and iw */
+  int32_t dt;                  /* DFX_F32 | DFX_S8 | DFX_U8; DFX_S32 with DFX_RESIZE_NEAREST only */
+  int32_t algo;                /* DFX_RESIZE_* */
+  int32_t coord;               /* DFX_COORD_* */
+  int32_t add;                 /* 1: submit takes the tensor to add */
+  int32_t post_relu;           /* with add only (DFX_ERR_INVALID otherwise) */
+  int32_t force_path;          /* -1 auto, else DFX_RESIZE_BAND | DFX_RESIZE_GENERIC */
+} dfx_resize_desc;
+enum {  /* dfx_resize_info.path */
+  DFX_RESIZE_BAND = 0,         /* resize_band_kernel (resize.cuh): a lane owns 16 bytes of channels of one output column
+                                  and a band of consecutive output rows; it keeps the two horizontal interpolations of the
+                                  rows y0 and y1 in f32 registers and rebuilds only what the next output row changes.
+                                  Class: c * sizeof(element) a multiple of 16; src, dst and add 16-byte aligned (checked
+                                  per submit: other pointers take the generic kernel for that submit); one image below
+                                  2^31 bytes on either side.  Bit-identical to the generic kernel.
+                                  AUTO RULE: see DFX_RESIZE_AUTO_NOTE below. */
+  DFX_RESIZE_GENERIC = 1       /* everything else: one thread per output element, grid-stride */
+};
+/* DFX_RESIZE_AUTO_NOTE: auto takes DFX_RESIZE_BAND everywhere in its class.  On the 16 in-class points of
+ * profiles/resize/bench_resize.txt (FPN nearest x2 + add at 16 / 32 / 64 -> x2 on 256 channels, DeepLab 33 -> 129 and its
+ * logits at c = 32, PSPNet 6 -> 60, U-Net x2 on u8 and f32; N = 1 and 16; buffers in rotation beyond the Infinity Cache) it
+ * is 1.2 to 9.5 times faster than the generic kernel on every one; with warm caches the smallest point (FPN 16 -> 32,
+ * N = 1) sits on the launch floor (3 us) and the band kernel is 1 to 4 % slower there.  1.5 to 5.0 TB/s of algorithmic bytes at N = 16. */
+typedef struct dfx_resize_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  int32_t rows_per_lane;       /* band length of the band kernel (1 on the generic path) */
+  uint64_t algorithmic_bytes;  /* src + dst + add tensor, one submit */
+  char kernel_name[96];
+} dfx_resize_info;
+typedef struct dfx_resize dfx_resize_t;
+
 /* ---- fully-connected (inner product) layer on int8: the classifier head the conv ops cannot express.  src NHWC u8
  *      {bs,ih,iw,ic} exactly as the previous conv or pool op wrote it (ih = iw = 1: a plain vector); wei s8
  *      {oc,ic,ih,iw} plain row-major, the flattened-CHW classifier frameworks keep (the library permutes it to src's
@@ -807,6 +872,26 @@ int dfx_dilconv_submit_host(dfx_dilconv_t *h, const void *src_host, void *dst_ho
 int dfx_dilconv_query(const dfx_dilconv_t *h, dfx_dilconv_info *info);
 int dfx_dilconv_destroy(dfx_dilconv_t *h);
 
+/* ---- activation resize (dfx_resize_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for a size outside 1 .. 65535, bs or c below 1, a bad dtype / algo / coord / force_path, add or
+ *      post_relu other than 0 / 1, post_relu without add, src or dst of more than 2^40 elements (so that no size product
+ *      leaves 64 bits); DFX_ERR_UNSUPPORTED for bilinear on s32 and for force_path =
+ *      DFX_RESIZE_BAND on a shape outside that class.  "No HIP device" is reported only for a valid descriptor.
+ *      submit: asynchronous on `s`; it never writes to the handle and every launch has its own copy of the arguments:
+ *      one handle serves several streams and host threads at once.  src and dst must be non-null; add_dev must be
+ *      non-null exactly when the descriptor has add = 1 (DFX_ERR_INVALID otherwise, nothing is launched).  Pointers
+ *      aligned to the element but not to 16 bytes take the generic kernel for that submit, as pooling does; a pointer
+ *      not aligned to the element, a dst range that overlaps src's, or an add range that overlaps dst's without being
+ *      dst, is DFX_ERR_INVALID.  add_dev may be dst_dev.
+ *      Tuning switches: DFX_RESIZE_ROWS=n sets the band length (default: 8 rows for bilinear, 2 for nearest, halved
+ *      while the launch would have fewer than 512 workgroups), DFX_RESIZE_MAX_GRID=n caps the grid of either kernel.
+ *      No CPU fallback. ---- */
+int dfx_resize_create(const dfx_resize_desc *desc, dfx_resize_t **out);
+int dfx_resize_submit(dfx_resize_t *h, const void *src_dev, const void *add_dev, void *dst_dev, dfx_stream_t s);
+int dfx_resize_submit_host(dfx_resize_t *h, const void *src_host, const void *add_host, void *dst_host); /* synchronous */
+int dfx_resize_query(const dfx_resize_t *h, dfx_resize_info *info);
+int dfx_resize_destroy(dfx_resize_t *h);
+
 /* ---- fully-connected layer (dfx_fc_desc above).  The descriptor is validated before anything touches a device:
  *      DFX_ERR_INVALID for a non-positive size, ih * iw * ic > 65025, bs * oc of 2^31 or more, a bad dtype / round
  *      mode / nscales / force_path; DFX_ERR_UNSUPPORTED only for force_path = DFX_FC_MFMA where K is no multiple of
@@ -909,6 +994,10 @@ int dfx_debug_fc_requant(const dfx_fc_t *h, int32_t out[1]);
 /* the depthwise + pointwise op's two stages {route0, route1}, same numbering; on the two-launch path the routes of
  * the owned depthwise and conv handles */
 int dfx_debug_dwpw_requant(const dfx_dwpw_t *h, int32_t out[2]);
+/* Read-only: how many dfx_resize_submit calls of this process have launched the band kernel (out[DFX_RESIZE_BAND]) and
+ * the generic kernel (out[DFX_RESIZE_GENERIC]) so far.  Process-wide, since submit does not write to the handle; it is
+ * how a test sees the per-submit fallback of 16-byte-misaligned pointers, which dfx_resize_query does not report. */
+int dfx_debug_resize_launches(int64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -73,6 +73,9 @@ struct memory_state {
   unsigned long long uploaded_version = 0;  // host_version the device copy reflects
   dfx_stream_t producer = nullptr;          // stream of the op whose launch, possibly still in flight, last wrote the
                                             // device copy; cleared once that stream has been synchronised
+  std::vector<dfx_stream_t> readers;        // streams of the ops whose launches, possibly still in flight, have read the
+                                            // device copy since that write (the producer's own stream is not listed: a
+                                            // stream is in order); a stream leaves when it is synchronised or destroyed
   bool device_ahead = false;                // the device copy is NEWER than the host bytes (written by an op and
                                             // not downloaded yet): an upload would destroy it
 };
@@ -146,6 +149,27 @@ struct op_state {
   void ensure_stream() {
     if (!stream) check_dfx(dfx_stream_create(&stream), "stream create");
   }
+  // The tensors in which this op's stream is registered as producer or reader.  Tensors outlive the ops built from them
+  // (deepfusion.h), so the pointers stay valid for the op's life.
+  std::vector<memory_state *> touched;
+  void touch(memory_state *s) {
+    for (memory_state *t : touched)
+      if (t == s) return;
+    touched.push_back(s);
+  }
+  // This op's stream is about to WRITE the device copy of s (a kernel's output or an upload): order it behind every launch
+  // on another stream that still reads the copy (write after read) or wrote it last (write after write), then own it.
+  void before_write(memory_state *s) {
+    bool was_reader = false;  // then sync_in() has waited for this producer already (every write clears the list)
+    for (dfx_stream_t r : s->readers) {
+      if (r != stream) check_dfx(dfx_stream_wait_stream(stream, r), "stream wait");
+      else was_reader = true;
+    }
+    s->readers.clear();
+    if (s->producer && s->producer != stream && !was_reader) check_dfx(dfx_stream_wait_stream(stream, s->producer), "stream wait");
+    s->producer = stream;
+    touch(s);
+  }
   // Make the device copy of input `m` current; returns the device pointer.
   // always == true is the reference-compatible submit(): the caller may have refilled the host
   // buffer through a pointer it fetched once (the reference reads host memory on every submit),
@@ -154,37 +178,53 @@ struct op_state {
   // stale, uploading them would overwrite the producer's result).  The asynchronous extension path
   // (submit_async / upload / device_data) skips the copy while no data() call has bumped the
   // version, and orders itself behind the op that produced the device copy on another stream.
+  // An upload is a write of the device copy like any other (before_write); a plain read registers
+  // this stream in `readers`, so that the next writer on another stream waits for it.
   void *sync_in(memory &m, bool always) {
     memory_state *s = m.st_;
     if (!s->device) check_dfx(dfx_mem_alloc_device(&s->device, s->bytes), "device alloc");
-    if (s->producer && s->producer != stream) check_dfx(dfx_stream_wait_stream(stream, s->producer), "stream wait");
     const bool host_touched = s->uploaded_version != s->host_version;
     if (host_touched || (always && !s->device_ahead)) {
+      before_write(s);
       check_dfx(dfx_memcpy_h2d(s->device, s->host, s->bytes, stream), "H2D copy");
       s->uploaded_version = s->host_version;
       s->device_ahead = false;
+    } else if (s->producer != stream) {
+      if (s->producer) check_dfx(dfx_stream_wait_stream(stream, s->producer), "stream wait");
+      bool listed = false;
+      for (dfx_stream_t r : s->readers) listed = listed || r == stream;
+      if (!listed) s->readers.push_back(stream);
+      touch(s);
     }
     return s->device;
   }
   void *device_out(memory &m) {
     memory_state *s = m.st_;
     if (!s->device) check_dfx(dfx_mem_alloc_device(&s->device, s->bytes), "device alloc");
-    s->producer = stream;
+    before_write(s);  // (an op whose input is also its output, resize_add(lateral = dst), does not wait on itself)
     s->uploaded_version = s->host_version;  // the device copy is about to become the newer one
     s->device_ahead = true;
     return s->device;
   }
-  // this op's stream has just been synchronised: nothing it launched is still writing m, consumers on
-  // other streams need not (and, once this op is gone, could not) wait on it
-  void settled(memory &m) {
-    if (m.st_->producer == stream) m.st_->producer = nullptr;
+  // forget this op's stream in every tensor it is registered in
+  void unregister() {
+    for (memory_state *s : touched) {
+      if (s->producer == stream) s->producer = nullptr;
+      for (size_t i = 0; i < s->readers.size();)
+        if (s->readers[i] == stream) s->readers.erase(s->readers.begin() + i);
+        else ++i;
+    }
+    touched.clear();
   }
-  // the op is being destroyed while a launch of it may still be writing m (the reference only asks that
-  // tensors outlive ops): finish that work, then forget the stream -- it is about to be destroyed
-  void retire(memory &m) {
-    if (stream && m.st_->producer == stream) {
+  // this op's stream has just been synchronised: nothing it launched is still writing its output or reading its inputs;
+  // ops on other streams need not (and, once this op is gone, could not) wait on it
+  void settled(memory &) { unregister(); }
+  // the op is being destroyed while a launch of it may still be writing its output or reading an input (the reference
+  // only asks that tensors outlive ops): finish that work, then forget the stream -- it is about to be destroyed
+  void retire(memory &) {
+    if (stream && !touched.empty()) {
       dfx_stream_sync(stream);
-      m.st_->producer = nullptr;
+      unregister();
     }
   }
   // device-side duration of what infer() enqueued, printed like the reference's profiling wrapper
@@ -275,6 +315,13 @@ void *memory::device_data() {
   return st_->device;
 }
 void memory::upload() {
+  // the copy overwrites the device buffer: launches that still read or write it finish first
+  for (dfx_stream_t r : st_->readers) check_dfx(dfx_stream_sync(r), "stream sync");
+  st_->readers.clear();
+  if (st_->producer) {
+    check_dfx(dfx_stream_sync(st_->producer), "stream sync");
+    st_->producer = nullptr;
+  }
   check_dfx(dfx_memcpy_h2d(device_data(), st_->host, st_->bytes, nullptr), "H2D copy");
   check_dfx(dfx_stream_sync(nullptr), "sync");
   st_->uploaded_version = st_->host_version;
@@ -731,7 +778,12 @@ public:
     check_dfx(dfx_stream_sync(st_.stream), "stream sync");
     st_.settled(*dst_);
   }
-  void submit_async() override { run(false); }
+  // (this op is not sharded.  Under DEEPFUSION_DEVICES > 1 its neighbours are, and they work host to host: the result
+  // is sent to the host as well, where a sharded consumer finds it after wait())
+  void submit_async() override {
+    run(false);
+    if (detail::requested_shards() > 1) st_.fetch_out(*dst_);
+  }
   void wait() override {
     check_dfx(dfx_stream_sync(st_.stream), "stream sync");
     st_.settled(*dst_);
@@ -807,7 +859,10 @@ public:
     check_dfx(dfx_stream_sync(st_.stream), "stream sync");
     st_.settled(*dst_);
   }
-  void submit_async() override { run(false); }
+  void submit_async() override {  // (not sharded: see op_conv_pool::submit_async)
+    run(false);
+    if (detail::requested_shards() > 1) st_.fetch_out(*dst_);
+  }
   void wait() override {
     check_dfx(dfx_stream_sync(st_.stream), "stream sync");
     st_.settled(*dst_);

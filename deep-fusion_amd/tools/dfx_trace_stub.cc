@@ -1,0 +1,424 @@
+// dfx_trace_stub.cc -- a recording fake of the C ABI (include/dfx.h): every entry point host/deepfusion.cc calls, with
+// no GPU, no HIP and no arithmetic behind it.  "Device" buffers are malloc'ed, streams are small records, and every call
+// that touches memory or orders streams is appended to an in-process trace (dfx_trace.h) that coherence_check.cc walks
+// with vector clocks.  A *_submit records its src / lateral / dst ranges with the byte sizes of the descriptor given at
+// create time; copies record both sides and do copy (so that a sanitizer build sees a wrong range); set_weights is a
+// host-thread read of the borrowed tensors and a write of the handle's packed copy, which every submit reads.
+//   DFX_TRACE_DEVICES=<n>   what dfx_device_count reports (default 1), so that DEEPFUSION_DEVICES shards can be traced
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "dfx.h"
+#include "dfx_trace.h"
+
+namespace {
+
+struct allocation {
+  char *base;
+  size_t bytes;
+  bool host, live;
+};
+struct stream_rec {  // never freed or reused: a stale handle cannot alias a newer stream
+  int id, device;
+  bool live;
+};
+struct handle {  // behind every dfx_*_t
+  const char *op;
+  std::vector<size_t> src;  // bytes of each source tensor
+  size_t lat, dst;          // bytes of the tensor to add (resize) and of dst
+  std::vector<size_t> wei;  // bytes of the borrowed host tensors, in set_weights' argument order (scales left out)
+  int packed;               // allocation id standing for the handle's own copy of the weights
+};
+
+std::vector<allocation> g_allocs;  // index = allocation id
+std::deque<stream_rec> g_streams;  // (a deque: addresses stay put)
+std::vector<dfx_trace::record> g_trace;
+std::vector<std::string> g_errors;
+std::string g_last_error;
+int g_device = 0;
+
+int fail(int rc, const std::string &msg) {
+  g_last_error = msg;
+  return rc;
+}
+void stub_error(const std::string &msg) {
+  g_errors.push_back(msg);
+  g_last_error = msg;
+}
+
+size_t dt_size(int dt) { return dt == DFX_F32 || dt == DFX_S32 ? 4 : 1; }
+
+int new_alloc(void **p, size_t bytes, bool host) {
+  char *b = static_cast<char *>(malloc(bytes ? bytes : 1));
+  if (!b) return fail(DFX_ERR_HIP, "out of memory");
+  g_allocs.push_back({b, bytes, host, true});
+  *p = b;
+  return DFX_OK;
+}
+int free_alloc(void *p, bool host) {
+  if (!p) return DFX_OK;
+  for (allocation &a : g_allocs)
+    if (a.live && a.base == p && a.host == host) {
+      a.live = false;
+      free(a.base);
+      return DFX_OK;
+    }
+  stub_error("free of a pointer that is no live allocation");
+  return DFX_ERR_INVALID;
+}
+// [p, p + len) -> range of the live allocation that holds it
+bool resolve(const void *p, size_t len, bool write, dfx_trace::range *out) {
+  const char *c = static_cast<const char *>(p);
+  for (size_t i = 0; i < g_allocs.size(); ++i) {
+    const allocation &a = g_allocs[i];
+    if (a.live && c >= a.base && c + len <= a.base + a.bytes) {
+      *out = {static_cast<int>(i), static_cast<size_t>(c - a.base), len, write};
+      return true;
+    }
+  }
+  return false;
+}
+void add_range(dfx_trace::record &r, const void *p, size_t len, bool write) {
+  dfx_trace::range g;
+  if (!p || !len) return;
+  if (resolve(p, len, write, &g)) r.ranges.push_back(g);
+  else stub_error(r.name + ": " + std::to_string(len) + " bytes outside every live allocation");
+}
+// a stream handle the caller passes in: NULL is the default stream
+bool stream_ok(dfx_stream_t s, const char *what) {
+  if (!s) return true;
+  for (stream_rec &t : g_streams)
+    if (&t == s) {
+      if (t.live) return true;
+      stub_error(std::string(what) + ": stream " + std::to_string(t.id) + " was destroyed");
+      return false;
+    }
+  stub_error(std::string(what) + ": not a stream");
+  return false;
+}
+
+handle *new_handle(const char *op) {
+  handle *h = new handle();
+  h->op = op;
+  h->lat = h->dst = 0;
+  void *p = nullptr;
+  new_alloc(&p, 1, false);
+  h->packed = static_cast<int>(g_allocs.size()) - 1;
+  return h;
+}
+int destroy_handle(void *hv) {
+  handle *h = static_cast<handle *>(hv);
+  if (!h) return DFX_OK;
+  free_alloc(g_allocs[h->packed].base, false);
+  delete h;
+  return DFX_OK;
+}
+// host-thread read of the borrowed weight / bias tensors, host-thread write of the packed copy
+int set_weights(void *hv, const char *name, std::initializer_list<const void *> tensors) {
+  handle *h = static_cast<handle *>(hv);
+  if (!h) return fail(DFX_ERR_INVALID, "null handle");
+  dfx_trace::record r{dfx_trace::HOST, nullptr, nullptr, name, {}};
+  size_t i = 0;
+  for (const void *t : tensors) {
+    if (i < h->wei.size()) add_range(r, t, h->wei[i], false);
+    ++i;
+  }
+  r.ranges.push_back({h->packed, 0, 1, true});
+  g_trace.push_back(r);
+  return DFX_OK;
+}
+int submit(void *hv, const char *name, const void *const *srcs, const void *lat, void *dst, dfx_stream_t s) {
+  handle *h = static_cast<handle *>(hv);
+  if (!h) return fail(DFX_ERR_INVALID, "null handle");
+  if (!stream_ok(s, name)) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, name, {}};
+  for (size_t i = 0; i < h->src.size(); ++i) add_range(r, srcs[i], h->src[i], false);
+  if (lat) add_range(r, lat, h->lat, false);
+  add_range(r, dst, h->dst, true);
+  r.ranges.push_back({h->packed, 0, 1, false});
+  g_trace.push_back(r);
+  return DFX_OK;
+}
+int submit1(void *hv, const char *name, const void *src, void *dst, dfx_stream_t s) {
+  return submit(hv, name, &src, nullptr, dst, s);
+}
+
+}  // namespace
+
+namespace dfx_trace {
+const std::vector<record> &records() { return g_trace; }
+void host_access(const char *name, const void *p, size_t len, bool write) {
+  record r{HOST, nullptr, nullptr, name, {}};
+  add_range(r, p, len, write);
+  g_trace.push_back(r);
+}
+const std::vector<std::string> &stub_errors() { return g_errors; }
+std::string describe(const range &r) {
+  return std::string(g_allocs[r.buf].host ? "host#" : "device#") + std::to_string(r.buf) + "+" + std::to_string(r.off);
+}
+int buffer_of(const void *p) {
+  range g;
+  return resolve(p, 1, false, &g) ? g.buf : -1;
+}
+}  // namespace dfx_trace
+
+extern "C" {
+
+int dfx_version(void) { return DFX_VERSION; }
+const char *dfx_last_error(void) { return g_last_error.c_str(); }
+int dfx_device_count(int *count) {
+  const char *e = getenv("DFX_TRACE_DEVICES");
+  const int n = e ? atoi(e) : 1;
+  *count = n < 1 ? 1 : n;
+  return DFX_OK;
+}
+int dfx_set_device(int ordinal) {
+  int n = 1;
+  dfx_device_count(&n);
+  if (ordinal < 0 || ordinal >= n) return fail(DFX_ERR_NO_DEVICE, "no such device");
+  g_device = ordinal;
+  return DFX_OK;
+}
+
+int dfx_mem_alloc_host(void **p, size_t bytes) { return new_alloc(p, bytes, true); }
+int dfx_mem_free_host(void *p) { return free_alloc(p, true); }
+int dfx_mem_alloc_device(void **p, size_t bytes) { return new_alloc(p, bytes, false); }
+int dfx_mem_free_device(void *p) { return free_alloc(p, false); }
+int dfx_memcpy_h2d(void *dst_dev, const void *src_host, size_t bytes, dfx_stream_t s) {
+  if (!stream_ok(s, "dfx_memcpy_h2d")) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_memcpy_h2d", {}};
+  add_range(r, src_host, bytes, false);
+  add_range(r, dst_dev, bytes, true);
+  g_trace.push_back(r);
+  if (r.ranges.size() == 2) memcpy(dst_dev, src_host, bytes);
+  return DFX_OK;
+}
+int dfx_memcpy_d2h(void *dst_host, const void *src_dev, size_t bytes, dfx_stream_t s) {
+  if (!stream_ok(s, "dfx_memcpy_d2h")) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_memcpy_d2h", {}};
+  add_range(r, src_dev, bytes, false);
+  add_range(r, dst_host, bytes, true);
+  g_trace.push_back(r);
+  if (r.ranges.size() == 2) memcpy(dst_host, src_dev, bytes);
+  return DFX_OK;
+}
+int dfx_stream_create(dfx_stream_t *s) {
+  g_streams.push_back({static_cast<int>(g_streams.size()) + 1, g_device, true});
+  *s = &g_streams.back();
+  return DFX_OK;
+}
+int dfx_stream_destroy(dfx_stream_t s) {
+  if (!s) return DFX_OK;
+  if (!stream_ok(s, "dfx_stream_destroy")) return DFX_ERR_INVALID;
+  static_cast<stream_rec *>(s)->live = false;
+  g_trace.push_back({dfx_trace::STREAM_DESTROY, s, nullptr, "dfx_stream_destroy", {}});
+  return DFX_OK;
+}
+int dfx_stream_sync(dfx_stream_t s) {
+  if (!stream_ok(s, "dfx_stream_sync")) return DFX_ERR_INVALID;
+  g_trace.push_back({dfx_trace::SYNC, s, nullptr, "dfx_stream_sync", {}});
+  return DFX_OK;
+}
+int dfx_stream_wait_stream(dfx_stream_t waiter, dfx_stream_t producer) {
+  if (!stream_ok(waiter, "dfx_stream_wait_stream (waiter)") || !stream_ok(producer, "dfx_stream_wait_stream (producer)"))
+    return DFX_ERR_INVALID;
+  g_trace.push_back({dfx_trace::WAIT, waiter, producer, "dfx_stream_wait_stream", {}});
+  return DFX_OK;
+}
+int dfx_event_create(dfx_event_t *e) {
+  *e = new int(0);
+  return DFX_OK;
+}
+int dfx_event_record(dfx_event_t, dfx_stream_t s) { return stream_ok(s, "dfx_event_record") ? DFX_OK : DFX_ERR_INVALID; }
+int dfx_event_elapsed_ms(dfx_event_t, dfx_event_t, float *ms) {
+  *ms = 0.f;
+  return DFX_OK;
+}
+int dfx_event_destroy(dfx_event_t e) {
+  delete static_cast<int *>(e);
+  return DFX_OK;
+}
+
+// the layout of include/deepfusion.h: [O/16][I/16][kh][kw][(i%16)/4][o%16][i%4]
+int dfx_reorder_oihw_to_blocked(const int8_t *oihw, int8_t *blocked, int O, int I, int KH, int KW) {
+  if (!oihw || !blocked || O < 1 || I < 1 || O % 16 || I % 16 || KH < 1 || KW < 1) return fail(DFX_ERR_INVALID, "bad reorder");
+  for (int o = 0; o < O; ++o)
+    for (int i = 0; i < I; ++i)
+      for (int y = 0; y < KH; ++y)
+        for (int x = 0; x < KW; ++x) {
+          const size_t blk = (((size_t)(o / 16) * (I / 16) + i / 16) * KH + y) * KW + x;
+          blocked[blk * 256 + ((i % 16) / 4) * 64 + (o % 16) * 4 + i % 4] = oihw[(((size_t)o * I + i) * KH + y) * KW + x];
+        }
+  return DFX_OK;
+}
+
+// ---- conv (+ the pooling fused into it) ----
+int dfx_conv_create(const dfx_conv_desc *d, dfx_conv_t **out) {
+  if (!d || !out || d->bs < 1) return fail(DFX_ERR_INVALID, "bad conv descriptor");
+  handle *h = new_handle("conv");
+  const int oc = d->oc1x1 ? d->oc1x1 : d->oc, div = d->fuse_pool == 2 ? 2 : 1;
+  h->src = {(size_t)d->bs * d->ih * d->iw * d->ic};
+  h->dst = (size_t)d->bs * (d->oh / div) * (d->ow / div) * oc * dt_size(d->dst_dt);
+  h->wei = {(size_t)d->oc * d->ic * d->kh * d->kw, d->bia0_dt ? d->oc * dt_size(d->bia0_dt) : 0, (size_t)d->oc1x1 * d->oc,
+            d->bia1_dt ? d->oc1x1 * dt_size(d->bia1_dt) : 0};
+  *out = reinterpret_cast<dfx_conv_t *>(h);
+  return DFX_OK;
+}
+int dfx_conv_set_weights(dfx_conv_t *h, const int8_t *w0, const void *b0, const float *, const int8_t *w1, const void *b1,
+                         const float *) {
+  return set_weights(h, "dfx_conv_set_weights", {w0, b0, w1, b1});
+}
+int dfx_conv_submit(dfx_conv_t *h, const void *src, void *dst, dfx_stream_t s) { return submit1(h, "dfx_conv_submit", src, dst, s); }
+int dfx_conv_destroy(dfx_conv_t *h) { return destroy_handle(h); }
+
+int dfx_pool_create(const dfx_pool_desc *d, dfx_pool_t **out) {
+  if (!d || !out) return fail(DFX_ERR_INVALID, "bad pool descriptor");
+  handle *h = new_handle("pool");
+  h->src = {(size_t)d->bs * d->ih * d->iw * d->c * dt_size(d->dt)};
+  h->dst = (size_t)d->bs * d->oh * d->ow * d->c * dt_size(d->dt);
+  *out = reinterpret_cast<dfx_pool_t *>(h);
+  return DFX_OK;
+}
+int dfx_pool_submit(dfx_pool_t *h, const void *src, void *dst, dfx_stream_t s) { return submit1(h, "dfx_pool_submit", src, dst, s); }
+int dfx_pool_destroy(dfx_pool_t *h) { return destroy_handle(h); }
+
+// ---- concat, eltwise sum ----
+int dfx_concat_create(const dfx_concat_desc *d, dfx_concat_t **out) {
+  if (!d || !out || d->n_inputs < 1) return fail(DFX_ERR_INVALID, "bad concat descriptor");
+  handle *h = new_handle("concat");
+  const size_t px = (size_t)d->bs * d->h * d->w * dt_size(d->dt);
+  for (int i = 0; i < d->n_inputs; ++i) {
+    h->src.push_back(px * d->channels[i]);
+    h->dst += px * d->channels[i];
+  }
+  *out = reinterpret_cast<dfx_concat_t *>(h);
+  return DFX_OK;
+}
+int dfx_concat_submit(dfx_concat_t *h, const void *const *srcs, void *dst, dfx_stream_t s) {
+  return submit(h, "dfx_concat_submit", srcs, nullptr, dst, s);
+}
+int dfx_concat_destroy(dfx_concat_t *h) { return destroy_handle(h); }
+
+int dfx_eltwise_create(const dfx_eltwise_desc *d, dfx_eltwise_t **out) {
+  if (!d || !out || d->n_inputs < 2) return fail(DFX_ERR_INVALID, "bad eltwise descriptor");
+  handle *h = new_handle("eltwise");
+  h->src.assign(d->n_inputs, (size_t)d->elems * dt_size(d->dt));
+  h->dst = (size_t)d->elems * dt_size(d->dt);
+  *out = reinterpret_cast<dfx_eltwise_t *>(h);
+  return DFX_OK;
+}
+int dfx_eltwise_submit(dfx_eltwise_t *h, const void *const *srcs, void *dst, dfx_stream_t s) {
+  return submit(h, "dfx_eltwise_submit", srcs, nullptr, dst, s);
+}
+int dfx_eltwise_destroy(dfx_eltwise_t *h) { return destroy_handle(h); }
+
+// ---- reorder ----
+int dfx_reorder_create(const dfx_reorder_desc *d, const float *, dfx_reorder_t **out) {
+  if (!d || !out) return fail(DFX_ERR_INVALID, "bad reorder descriptor");
+  handle *h = new_handle("reorder");
+  const size_t px = (size_t)d->bs * d->h * d->w;
+  h->src = {px * d->src_c * dt_size(d->src_dt)};
+  h->dst = px * d->dst_c * dt_size(d->dst_dt);
+  *out = reinterpret_cast<dfx_reorder_t *>(h);
+  return DFX_OK;
+}
+int dfx_reorder_submit(dfx_reorder_t *h, const void *src, void *dst, dfx_stream_t s) {
+  return submit1(h, "dfx_reorder_submit", src, dst, s);
+}
+int dfx_reorder_destroy(dfx_reorder_t *h) { return destroy_handle(h); }
+
+// ---- concat + pointwise conv ----
+int dfx_catconv_create(const dfx_catconv_desc *d, dfx_catconv_t **out) {
+  if (!d || !out || d->n_inputs < 2) return fail(DFX_ERR_INVALID, "bad catconv descriptor");
+  handle *h = new_handle("catconv");
+  const size_t px = (size_t)d->bs * d->h * d->w;
+  size_t ic = 0;
+  for (int i = 0; i < d->n_inputs; ++i) {
+    h->src.push_back(px * d->channels[i]);
+    ic += d->channels[i];
+  }
+  h->dst = px * d->oc * dt_size(d->dst_dt);
+  h->wei = {(size_t)d->oc * ic, d->bia_dt ? d->oc * dt_size(d->bia_dt) : 0};
+  *out = reinterpret_cast<dfx_catconv_t *>(h);
+  return DFX_OK;
+}
+int dfx_catconv_set_weights(dfx_catconv_t *h, const int8_t *w, const void *b, const float *) {
+  return set_weights(h, "dfx_catconv_set_weights", {w, b});
+}
+int dfx_catconv_submit(dfx_catconv_t *h, const void *const *srcs, void *dst, dfx_stream_t s) {
+  return submit(h, "dfx_catconv_submit", srcs, nullptr, dst, s);
+}
+int dfx_catconv_destroy(dfx_catconv_t *h) { return destroy_handle(h); }
+
+// ---- the single-source conv family: depthwise, grouped, first-layer, transposed, dilated, fully-connected ----
+#define DFX_STUB_CONV_FAMILY(NAME, DESC, SRC_BYTES, DST_ELEMS, WEI_BYTES, BIA_N)                                              \
+  int dfx_##NAME##_create(const DESC *d, dfx_##NAME##_t **out) {                                                            \
+    if (!d || !out || d->bs < 1) return fail(DFX_ERR_INVALID, "bad " #NAME " descriptor");                                  \
+    handle *h = new_handle(#NAME);                                                                                           \
+    h->src = {(size_t)(SRC_BYTES)};                                                                                          \
+    h->dst = (size_t)(DST_ELEMS)*dt_size(d->dst_dt);                                                                         \
+    h->wei = {(size_t)(WEI_BYTES), d->bia_dt ? (size_t)(BIA_N)*dt_size(d->bia_dt) : 0};                                      \
+    *out = reinterpret_cast<dfx_##NAME##_t *>(h);                                                                            \
+    return DFX_OK;                                                                                                           \
+  }                                                                                                                          \
+  int dfx_##NAME##_set_weights(dfx_##NAME##_t *h, const int8_t *w, const void *b, const float *) {                          \
+    return set_weights(h, "dfx_" #NAME "_set_weights", {w, b});                                                              \
+  }                                                                                                                          \
+  int dfx_##NAME##_submit(dfx_##NAME##_t *h, const void *src, void *dst, dfx_stream_t s) {                                  \
+    return submit1(h, "dfx_" #NAME "_submit", src, dst, s);                                                                  \
+  }                                                                                                                          \
+  int dfx_##NAME##_destroy(dfx_##NAME##_t *h) { return destroy_handle(h); }
+
+DFX_STUB_CONV_FAMILY(dwconv, dfx_dwconv_desc, (size_t)d->bs * d->ih * d->iw * d->c, (size_t)d->bs * d->oh * d->ow * d->c,
+                     (size_t)d->c * d->kh * d->kw, d->c)
+DFX_STUB_CONV_FAMILY(gconv, dfx_gconv_desc, (size_t)d->bs * d->ih * d->iw * d->ic, (size_t)d->bs * d->oh * d->ow * d->oc,
+                     (size_t)d->oc * (d->ic / (d->groups > 0 ? d->groups : 1)) * d->kh * d->kw, d->oc)
+DFX_STUB_CONV_FAMILY(imgconv, dfx_imgconv_desc, (size_t)d->bs * d->ih * d->iw * d->ic, (size_t)d->bs * d->oh * d->ow * d->oc,
+                     (size_t)d->oc * d->ic * d->kh * d->kw, d->oc)
+DFX_STUB_CONV_FAMILY(deconv, dfx_deconv_desc, (size_t)d->bs * d->ih * d->iw * d->ic, (size_t)d->bs * d->oh * d->ow * d->oc,
+                     (size_t)d->oc * d->ic * d->kh * d->kw, d->oc)
+DFX_STUB_CONV_FAMILY(dilconv, dfx_dilconv_desc, (size_t)d->bs * d->ih * d->iw * d->ic, (size_t)d->bs * d->oh * d->ow * d->oc,
+                     (size_t)d->oc * d->ic * d->kh * d->kw, d->oc)
+DFX_STUB_CONV_FAMILY(fc, dfx_fc_desc, (size_t)d->bs * d->ih * d->iw * d->ic, (size_t)d->bs * d->oc,
+                     (size_t)d->oc * d->ic * d->ih * d->iw, d->oc)
+#undef DFX_STUB_CONV_FAMILY
+
+// ---- depthwise + pointwise conv ----
+int dfx_dwpw_create(const dfx_dwpw_desc *d, dfx_dwpw_t **out) {
+  if (!d || !out || d->bs < 1) return fail(DFX_ERR_INVALID, "bad dwpw descriptor");
+  handle *h = new_handle("dwpw");
+  h->src = {(size_t)d->bs * d->ih * d->iw * d->c};
+  h->dst = (size_t)d->bs * d->oh * d->ow * d->oc * dt_size(d->dst_dt);
+  h->wei = {(size_t)d->c * d->kh * d->kw, d->bia0_dt ? d->c * dt_size(d->bia0_dt) : 0, (size_t)d->oc * d->c,
+            d->bia1_dt ? d->oc * dt_size(d->bia1_dt) : 0};
+  *out = reinterpret_cast<dfx_dwpw_t *>(h);
+  return DFX_OK;
+}
+int dfx_dwpw_set_weights(dfx_dwpw_t *h, const int8_t *w0, const void *b0, const float *, const int8_t *w1, const void *b1,
+                         const float *) {
+  return set_weights(h, "dfx_dwpw_set_weights", {w0, b0, w1, b1});
+}
+int dfx_dwpw_submit(dfx_dwpw_t *h, const void *src, void *dst, dfx_stream_t s) { return submit1(h, "dfx_dwpw_submit", src, dst, s); }
+int dfx_dwpw_destroy(dfx_dwpw_t *h) { return destroy_handle(h); }
+
+// ---- resize (+ add) ----
+int dfx_resize_create(const dfx_resize_desc *d, dfx_resize_t **out) {
+  if (!d || !out || d->bs < 1) return fail(DFX_ERR_INVALID, "bad resize descriptor");
+  handle *h = new_handle("resize");
+  h->src = {(size_t)d->bs * d->ih * d->iw * d->c * dt_size(d->dt)};
+  h->dst = (size_t)d->bs * d->oh * d->ow * d->c * dt_size(d->dt);
+  h->lat = d->add ? h->dst : 0;
+  *out = reinterpret_cast<dfx_resize_t *>(h);
+  return DFX_OK;
+}
+int dfx_resize_submit(dfx_resize_t *h, const void *src, const void *add, void *dst, dfx_stream_t s) {
+  return submit(h, "dfx_resize_submit", &src, add, dst, s);
+}
+int dfx_resize_destroy(dfx_resize_t *h) { return destroy_handle(h); }
+
+}  // extern "C"

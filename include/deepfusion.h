@@ -28,6 +28,16 @@
 //     submit_async()); memory::device_data() exposes the device buffer; memory::download() /
 //     op::wait() complete a transfer explicitly.  With DEEPFUSION_PROFILE=1 every submit,
 //     submit_async() included, waits for its launch (it prints the launch's duration).
+//     Every op runs on a stream of its own, and the library orders the streams on the device:
+//     an op waits for the op that wrote its input, and for every op that still reads, or last
+//     wrote, the tensor it is about to overwrite.  So ops may be chained, tensors may have
+//     several consumers, an op may update a tensor in place, and several frames may be in flight
+//     (for frame: a->submit_async(); b->submit_async();) without a wait() in between; ops may be
+//     destroyed while their launch is in flight.  Two rules are the caller's:
+//       - wait() (on the op that consumed the tensor) before rewriting host bytes which an
+//         earlier submit_async() uploaded: the upload reads the host buffer asynchronously;
+//       - under DEEPFUSION_DEVICES > 1 (batch shards: host in, host out on per-shard streams,
+//         no ordering between ops) a consumer needs the producer's wait() first.
 //
 // Lifetime rule kept from the reference (op_conv.h:81-95, op_concat.h:53-56):
 // an op borrows the tensors it was built from; they must outlive it.

@@ -24,6 +24,7 @@ from .capi import (  # noqa: F401
     RESIZE_AUTO, RESIZE_BAND, RESIZE_GENERIC, RESIZE_NEAREST, RESIZE_BILINEAR, COORD_HALF_PIXEL, COORD_ALIGN_CORNERS,
     COORD_ASYMMETRIC, ResizeDesc, ResizeInfo, Resize,
     FC_AUTO, FC_MFMA, FC_GENERIC, FcDesc, FcInfo, InnerProduct,
+    SE_AUTO, SE_BAND, SE_GENERIC, SE_SCALE, SE_GATE, SE_SQUEEZE, SeDesc, SeInfo, SqueezeExcite,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

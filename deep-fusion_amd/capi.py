@@ -27,6 +27,8 @@ RESIZE_AUTO, RESIZE_BAND, RESIZE_GENERIC = -1, 0, 1
 RESIZE_NEAREST, RESIZE_BILINEAR = 0, 1
 COORD_HALF_PIXEL, COORD_ALIGN_CORNERS, COORD_ASYMMETRIC = 0, 1, 2
 FC_AUTO, FC_MFMA, FC_GENERIC = -1, 0, 1
+SE_AUTO, SE_BAND, SE_GENERIC = -1, 0, 1
+SE_SCALE, SE_GATE, SE_SQUEEZE = 0, 1, 2
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -167,6 +169,16 @@ class FcInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "splitk", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
+
+
+class SeDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "cr", "mode", "bia1_dt", "bia2_dt", "round_mode",
+                                             "nscales1", "nscales2", "nscales_out", "force_path")]
+
+
+class SeInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "slices", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
 
 
 class DwPwDesc(ctypes.Structure):
@@ -321,6 +333,12 @@ def lib():
         "dfx_fc_submit_host": (i32, [vp, vp, vp]),
         "dfx_fc_query": (i32, [vp, ctypes.POINTER(FcInfo)]),
         "dfx_fc_destroy": (i32, [vp]),
+        "dfx_se_create": (i32, [ctypes.POINTER(SeDesc), ctypes.POINTER(vp)]),
+        "dfx_se_set_weights": (i32, [vp] * 9),
+        "dfx_se_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_se_submit_host": (i32, [vp, vp, vp]),
+        "dfx_se_query": (i32, [vp, ctypes.POINTER(SeInfo)]),
+        "dfx_se_destroy": (i32, [vp]),
         "dfx_dwpw_create": (i32, [ctypes.POINTER(DwPwDesc), ctypes.POINTER(vp)]),
         "dfx_dwpw_set_weights": (i32, [vp] * 7),
         "dfx_dwpw_submit": (i32, [vp, vp, vp, vp]),
@@ -815,6 +833,38 @@ class InnerProduct(_Handle):
         assert ws[0].size == d.oc * d.ic * d.ih * d.iw, ws[0].shape
         assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
         _check(lib().dfx_fc_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+
+class SqueezeExcite(_Handle):
+    """dfx_se_* handle: squeeze-and-excitation over NHWC u8 {bs, ih, iw, c} (include/dfx.h): global average, FC1 {cr, c}
+    (relu, u8), FC2 {c, cr} (s8), a 256-entry gate table and the per-(image, channel) rescale.  SE_SCALE writes the
+    rescaled tensor (dst may be src), SE_GATE the {bs, c} gate, SE_SQUEEZE the {bs, c} average (no weights)."""
+
+    _OP, _INFO = "dfx_se", SeInfo
+
+    def __init__(self, src_shape_nhwc, cr, mode=SE_SCALE, bia1_dt=DFX_UNDEF, bia2_dt=DFX_UNDEF, nscales1=1, nscales2=1,
+                 nscales_out=1, rm=ROUND_NEAREST, force_path=SE_AUTO):
+        bs, ih, iw, c = src_shape_nhwc
+        d = SeDesc(bs, c, ih, iw, cr, mode, bia1_dt, bia2_dt, rm, nscales1, nscales2, nscales_out, force_path)
+        self.desc = d
+        self.src_shape = (bs, ih, iw, c)
+        self.dst_shape = (bs, ih, iw, c) if mode == SE_SCALE else (bs, c)
+        self.dst_np_dtype = np.uint8
+        self._create(d)
+
+    def set_weights(self, w1, scales1, w2, scales2, lut, out_scales, bia1=None, bia2=None):
+        """w1: int8 {cr, c}; w2: int8 {c, cr}; scales1: 1 or cr floats; scales2 and out_scales: 1 or c floats; lut: 256
+        uint8; biases: cr / c entries of the descriptor's bias dtypes"""
+        d = self.desc
+        w1, w2 = np.ascontiguousarray(w1, dtype=np.int8), np.ascontiguousarray(w2, dtype=np.int8)
+        s1, s2, so = [np.ascontiguousarray(v, dtype=np.float32) for v in (scales1, scales2, out_scales)]
+        lut = np.ascontiguousarray(lut, dtype=np.uint8)
+        b1 = None if bia1 is None else np.ascontiguousarray(bia1)
+        b2 = None if bia2 is None else np.ascontiguousarray(bia2)
+        assert w1.size == d.cr * d.c and w2.size == d.c * d.cr and lut.size == 256, (w1.shape, w2.shape, lut.shape)
+        assert s1.size == d.nscales1 and s2.size == d.nscales2 and so.size == d.nscales_out
+        assert (b1 is None or b1.size == d.cr) and (b2 is None or b2.size == d.c)
+        _check(lib().dfx_se_set_weights(self._h, _p(w1), _p(b1), _p(s1), _p(w2), _p(b2), _p(s2), _p(lut), _p(so)))
 
 
 class DwPwConv(_Handle):

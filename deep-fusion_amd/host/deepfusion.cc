@@ -2316,6 +2316,201 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- squeeze-and-excitation (dfx_se_*) and, with no weights, the global average pooling it starts with.  The two weight
+// tensors are plain oihw {cr, c, 1, 1} and {c, cr, 1, 1}; dst may be src.  Weight hashing and batch sharding are
+// op_depthwise_conv's: the op is per image, so shards are independent. ----
+class op_squeeze_excite : public op {
+public:
+  op_squeeze_excite(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> *wei1, const std::unique_ptr<memory> *bia1,
+                    const std::unique_ptr<memory> *wei2, const std::unique_ptr<memory> *bia2, const std::array<u8, 256> *table,
+                    std::unique_ptr<memory> &dst, const std::vector<float> &scales1, const std::vector<float> &scales2,
+                    const std::vector<float> &out_scales, round_mode rm)
+      : src_(src.get()), wei1_(wei1 ? wei1->get() : nullptr), bia1_(bia1 ? bia1->get() : nullptr), wei2_(wei2 ? wei2->get() : nullptr),
+        bia2_(bia2 ? bia2->get() : nullptr), dst_(dst.get()), pool_only_(!wei1), scales1_(scales1), scales2_(scales2), out_scales_(out_scales),
+        h_(nullptr), packed_hash_(0), packed_versions_(0) {
+    using fmt = memory::format;
+    const char *what = pool_only_ ? "GlobalAvgPool" : "SqueezeExcite";
+    if (!src_ || !dst_ || (!pool_only_ && (!wei1_ || !wei2_))) error_and_exit("Init %s op failed! (null tensor)", what);
+    if (src_->data_type() != memory::dtype::u8 || dst_->data_type() != memory::dtype::u8 || src_->dim_format() != fmt::nhwc ||
+        dst_->dim_format() != fmt::nhwc)
+      error_and_exit("Init %s op failed! (data type / format)", what);
+    auto i = src_->std_dims(), o = dst_->std_dims();
+    if (i[0] != o[0]) error_and_exit("Init %s op failed! (Batch size do not equal)", what);
+    if (i[1] != o[1]) error_and_exit("Init %s op failed! (Channel do not match)", what);
+    dfx_se_desc d;
+    memset(&d, 0, sizeof(d));
+    d.bs = i[0]; d.c = i[1]; d.ih = i[2]; d.iw = i[3];
+    d.cr = 1;
+    d.nscales1 = d.nscales2 = d.nscales_out = 1;
+    d.bia1_dt = d.bia2_dt = DFX_UNDEF;
+    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.force_path = -1;
+    if (pool_only_) {
+      if (o[2] != 1 || o[3] != 1) error_and_exit("Init GlobalAvgPool op failed! (dst must be {bs, c, 1, 1})");
+      if (src_ == dst_) error_and_exit("Init GlobalAvgPool op failed! (dst must not be src)");
+      d.mode = DFX_SE_SQUEEZE;
+    } else {
+      if (wei1_->data_type() != memory::dtype::s8 || wei2_->data_type() != memory::dtype::s8 || wei1_->dim_format() != fmt::oihw ||
+          wei2_->dim_format() != fmt::oihw || (bia1_ && bia1_->dim_format() != fmt::x) || (bia2_ && bia2_->dim_format() != fmt::x))
+        error_and_exit("Init SqueezeExcite op failed! (data type / format)");
+      if (o != i) error_and_exit("Init SqueezeExcite op failed! (dst must have src's dims)");
+      auto w1 = wei1_->std_dims(), w2 = wei2_->std_dims();
+      if (w1[1] != i[1] || w1[2] != 1 || w1[3] != 1 || w2[0] != i[1] || w2[1] != w1[0] || w2[2] != 1 || w2[3] != 1)
+        error_and_exit("Init SqueezeExcite op failed! (weights must be {cr, c, 1, 1} and {c, cr, 1, 1})");
+      if ((bia1_ && (int)bia1_->size() != w1[0]) || (bia2_ && (int)bia2_->size() != i[1]))
+        error_and_exit("Init SqueezeExcite op failed! (Bias channel do not match)");
+      table_ = *table;
+      d.mode = DFX_SE_SCALE;
+      d.cr = w1[0];
+      d.bia1_dt = bia1_ ? to_dfx_dtype(bia1_->data_type()) : DFX_UNDEF;
+      d.bia2_dt = bia2_ ? to_dfx_dtype(bia2_->data_type()) : DFX_UNDEF;
+      d.nscales1 = (int)scales1_.size();
+      d.nscales2 = (int)scales2_.size();
+      d.nscales_out = (int)out_scales_.size();
+    }
+    src_img_ = (size_t)d.ih * d.iw * d.c;
+    dst_img_ = pool_only_ ? (size_t)d.c : src_img_;
+    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
+      shard sh;
+      sh.r = r;
+      dfx_se_desc ds = d;
+      ds.bs = r.n;
+      check_dfx(dfx_set_device(r.device), "set device");
+      if (dfx_se_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init %s op failed! (%s)", what, dfx_last_error());
+      check_dfx(dfx_stream_create(&sh.stream), "stream create");
+      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
+      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
+      shards_.push_back(sh);
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    if (dfx_se_create(&d, &h_) != DFX_OK) error_and_exit("Init %s op failed! (%s)", what, dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_squeeze_excite() override {
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      dfx_se_destroy(sh.h);
+      dfx_stream_destroy(sh.stream);
+      dfx_mem_free_device(sh.src);
+      dfx_mem_free_device(sh.dst);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire(*dst_);
+    dfx_se_destroy(h_);
+  }
+
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  void submit_async() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(false);
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled(*dst_);
+    }
+  }
+
+protected:
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  unsigned long long weights_hash() {
+    using detail::hash_bytes;
+    unsigned long long v = hash_bytes(wei1_->host_data(), wei1_->buffer_size(), 1469598103934665603ull);
+    v = hash_bytes(wei2_->host_data(), wei2_->buffer_size(), v);
+    if (bia1_) v = hash_bytes(bia1_->host_data(), bia1_->buffer_size(), v);
+    if (bia2_) v = hash_bytes(bia2_->host_data(), bia2_->buffer_size(), v);
+    return v | 1ull;
+  }
+  unsigned long long weights_versions() const {
+    return wei1_->host_version() + wei2_->host_version() + (bia1_ ? bia1_->host_version() : 0) + (bia2_ ? bia2_->host_version() : 0);
+  }
+  void set_weights(dfx_se_t *h) {
+    check_dfx(dfx_se_set_weights(h, (const int8_t *)wei1_->host_data(), bia1_ ? bia1_->host_data() : nullptr, scales1_.data(),
+                                 (const int8_t *)wei2_->host_data(), bia2_ ? bia2_->host_data() : nullptr, scales2_.data(),
+                                 table_.data(), out_scales_.data()),
+              "squeeze_excite set_weights");
+  }
+  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
+    const unsigned long long v = pool_only_ ? 0 : weights_hash();
+    const char *hs = static_cast<const char *>(src_->host_data());
+    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      if (!pool_only_ && v != sh.wei_seen) {
+        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+        set_weights(sh.h);
+        sh.wei_seen = v;
+      }
+      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
+      check_dfx(dfx_se_submit(sh.h, sh.src, sh.dst, sh.stream), "squeeze_excite submit");
+      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    detail::op_state::host_is_current(*dst_);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
+    const unsigned long long vers = pool_only_ ? 0 : weights_versions();
+    if (!pool_only_ && (sync_host || vers != packed_versions_)) {
+      const unsigned long long hash = weights_hash();
+      if (hash != packed_hash_) {
+        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
+        set_weights(h_);
+        packed_hash_ = hash;
+      }
+      packed_versions_ = vers;
+    }
+    const void *in = st_.sync_in(*src_, sync_host);
+    void *o = st_.device_out(*dst_);  // (dst may be src: uploaded, then overwritten in place)
+    st_.profile_begin();
+    check_dfx(dfx_se_submit(h_, in, o, st_.stream), "squeeze_excite submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return pool_only_ ? "global_avg_pool" : "squeeze_excite"; }
+
+private:
+  struct shard {
+    detail::shard_range r;
+    dfx_se_t *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    void *src = nullptr, *dst = nullptr;
+    unsigned long long wei_seen = 0;
+  };
+  memory *src_, *wei1_, *bia1_, *wei2_, *bia2_, *dst_;
+  bool pool_only_;  // no weights: global_avg_pool()
+  std::array<u8, 256> table_;
+  std::vector<float> scales1_, scales2_, out_scales_;
+  dfx_se_t *h_;
+  unsigned long long packed_hash_, packed_versions_;
+  size_t src_img_, dst_img_;  // bytes per image
+  detail::op_state st_;
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
+};
+
 // ---- depthwise + pointwise conv (dfx_dwpw_*): depthwise_conv() with a u8 result followed by a 1x1 conv(), behind one
 // handle.  force_path stays -1 (auto), so the path is the library's choice (dfx.h, AUTO RULE at DFX_DWPW_FUSED).  The depthwise weights are a plain oihw
 // {c, 1, kh, kw} tensor, the pointwise weights OIhw4i16o4i {oc, c, 1, 1}; dst's dims give the output size. ----
@@ -2544,6 +2739,19 @@ std::unique_ptr<op> inner_product(const std::unique_ptr<memory> &src, const std:
                                   const std::unique_ptr<memory> &bia, std::unique_ptr<memory> &dst, bool relu,
                                   std::vector<float> scales, round_mode rm) {
   return std::unique_ptr<op>(new op_inner_product(src, wei, bia, dst, relu, scales, rm));
+}
+
+std::unique_ptr<op> squeeze_excite(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei1,
+                                   const std::unique_ptr<memory> &bia1, const std::unique_ptr<memory> &wei2,
+                                   const std::unique_ptr<memory> &bia2, const std::array<u8, 256> &gate_table,
+                                   std::unique_ptr<memory> &dst, std::vector<float> scales1, std::vector<float> scales2,
+                                   std::vector<float> out_scales, round_mode rm) {
+  return std::unique_ptr<op>(new op_squeeze_excite(src, &wei1, &bia1, &wei2, &bia2, &gate_table, dst, scales1, scales2, out_scales, rm));
+}
+
+std::unique_ptr<op> global_avg_pool(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst) {
+  return std::unique_ptr<op>(new op_squeeze_excite(src, nullptr, nullptr, nullptr, nullptr, nullptr, dst, {1.f}, {1.f}, {1.f},
+                                                   round_mode::nearest));
 }
 
 std::unique_ptr<op> depthwise_separable_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei_dw,

@@ -421,4 +421,22 @@ int dfx_resize_submit(dfx_resize_t *h, const void *src, const void *add, void *d
 }
 int dfx_resize_destroy(dfx_resize_t *h) { return destroy_handle(h); }
 
+// ---- squeeze-and-excitation (dst may be src) ----
+int dfx_se_create(const dfx_se_desc *d, dfx_se_t **out) {
+  if (!d || !out || d->bs < 1) return fail(DFX_ERR_INVALID, "bad se descriptor");
+  handle *h = new_handle("se");
+  h->src = {(size_t)d->bs * d->ih * d->iw * d->c};
+  h->dst = d->mode == DFX_SE_SCALE ? h->src[0] : (size_t)d->bs * d->c;
+  h->wei = {(size_t)d->cr * d->c, d->bia1_dt ? d->cr * dt_size(d->bia1_dt) : 0, (size_t)d->c * d->cr,
+            d->bia2_dt ? d->c * dt_size(d->bia2_dt) : 0};
+  *out = reinterpret_cast<dfx_se_t *>(h);
+  return DFX_OK;
+}
+int dfx_se_set_weights(dfx_se_t *h, const int8_t *w1, const void *b1, const float *, const int8_t *w2, const void *b2, const float *,
+                       const uint8_t *, const float *) {
+  return set_weights(h, "dfx_se_set_weights", {w1, b1, w2, b2});
+}
+int dfx_se_submit(dfx_se_t *h, const void *src, void *dst, dfx_stream_t s) { return submit1(h, "dfx_se_submit", src, dst, s); }
+int dfx_se_destroy(dfx_se_t *h) { return destroy_handle(h); }
+
 }  // extern "C"

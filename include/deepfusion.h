@@ -374,6 +374,29 @@ std::unique_ptr<op> inner_product(const std::unique_ptr<memory> &src,
                                   bool relu = false, std::vector<float> scales = {1.f},
                                   round_mode rm = round_mode::nearest);
 
+// ---- extension: squeeze-and-excitation (dfx_se_* in dfx.h), the gate between the depthwise (or grouped) conv and the
+// projecting 1x1 conv of an EfficientNet / MobileNetV3 / SENet / RegNetY block: global average over the image, FC1
+// (ReLU, u8), FC2 (s8), a 256-entry table that turns the requantised logit t into the gate (gate_table[t + 128]: the
+// caller's sigmoid, hard-sigmoid, ...), and dst = src * gate * out_scale per (image, channel).  src and dst: nhwc u8 of
+// the same dims; dst may BE src.  wei1: plain oihw s8 {cr, c, 1, 1}; wei2: plain oihw s8 {c, cr, 1, 1}; biases: format x
+// with cr / c entries, or null.  scales1: 1 or cr, scales2 and out_scales: 1 or c entries.  The arithmetic is dfx.h's:
+// the average is avg pooling's, the two layers are inner_product()'s, every f32 step is rounded separately.  c a multiple
+// of 16 runs on 16-byte kernels, everything else on generic ones.  global_avg_pool() is the op's first stage alone: dst
+// {bs, c, 1, 1} u8 holds what avg pooling with the window of the image gives, at any image size -- the layer in front of
+// a classifier's inner_product().  submit / submit_async / wait, weight hashing and DEEPFUSION_DEVICES sharding are
+// depthwise_conv()'s. ----
+std::unique_ptr<op> squeeze_excite(const std::unique_ptr<memory> &src,
+                                   const std::unique_ptr<memory> &wei1,
+                                   const std::unique_ptr<memory> &bia1,
+                                   const std::unique_ptr<memory> &wei2,
+                                   const std::unique_ptr<memory> &bia2,
+                                   const std::array<u8, 256> &gate_table,
+                                   std::unique_ptr<memory> &dst,
+                                   std::vector<float> scales1 = {1.f}, std::vector<float> scales2 = {1.f},
+                                   std::vector<float> out_scales = {1.f / 255.f},
+                                   round_mode rm = round_mode::nearest);
+std::unique_ptr<op> global_avg_pool(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst);
+
 // ---- extension: depthwise conv + pointwise conv, the depthwise-separable block (dfx_dwpw_* in dfx.h).  Stage 0 is
 // depthwise_conv() with a u8 result (ReLU implied), stage 1 a 1x1 stride-1 unpadded conv() on that tensor; dst holds,
 // bit for bit, what the two ops give one after the other.  wei_dw: plain oihw s8 {c, 1, kh, kw}; wei_pw: OIhw4i16o4i

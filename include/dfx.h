@@ -559,6 +559,70 @@ typedef struct dfx_fc_info {
 } dfx_fc_info;
 typedef struct dfx_fc dfx_fc_t;
 
+/* ---- squeeze-and-excitation gate: the piece between the depthwise (or grouped) conv and the projecting 1x1 conv of every
+ *      EfficientNet block, most MobileNetV3 blocks and every SENet / SE-ResNeXt / RegNetY block: global average, two tiny
+ *      fully-connected layers, a gate function, a per-(image, channel) rescale of the activation.
+ *        src   NHWC u8 {bs,ih,iw,c};  dst NHWC u8 of the same shape, it may BE src (in place), any other overlap is refused
+ *        w1    s8 {cr,c} row-major;   w2 s8 {c,cr} row-major;  biases bia1_dt / bia2_dt as in dfx_fc_desc (DFX_UNDEF = none)
+ *        scales1: 1 or cr floats;  scales2: 1 or c floats;  out_scales: 1 or c floats
+ *        lut   256 u8 entries given by the caller: lut[i] is the gate for t = i - 128
+ *      ARITHMETIC (one round_mode rm for all stages; requant, cvt_x86_rt, sat_u8_bits and sat_s8 are csrc/dfx_device.cuh's:
+ *      separately rounded f32 add and multiply, never an FMA; the biases are converted on the host as dfx_fc's are):
+ *        sum[n,c] = sum over y, x of src[n,y,x,c]                        exact s32 (ih*iw <= 2^23, so 255*ih*iw < 2^31)
+ *        z[n,c]   = rint(float(sum) / float(ih*iw)) clamped to 0 .. 255   dfx_pool's average (avg_finish<u8>)
+ *        a1[n,j]  = sum over c of z[n,c] * w1[j,c]                        exact s32
+ *        h[n,j]   = sat_u8_bits(cvt_x86_rt(requant(a1, b1[j], s1[j], relu = true), rm))       dfx_fc with dst u8
+ *        a2[n,c]  = sum over j of h[n,j] * w2[c,j]
+ *        t[n,c]   = sat_s8(cvt_x86_rt(requant(a2, b2[c], s2[c], relu = false), rm))            dfx_fc with dst s8
+ *        g[n,c]   = lut[t[n,c] + 128]
+ *        dst[n,y,x,c] = sat_u8_bits(cvt_x86_rt(requant(src[n,y,x,c] * g[n,c], +0.0f, out_scale[c], true), rm))
+ *      The table turns the requantised logit into the gate: the caller builds it for sigmoid, hard-sigmoid (MobileNetV3) or
+ *      anything else; with out_scale = 1/255 and lut = rint(255 * sigmoid(t * s)) the op is the float SE gate to within
+ *      quantisation.  No transcendental is evaluated on the device: every stage is exact integer or single-rounded f32.
+ *      Defining properties (tests/test_gpu_se.py): DFX_SE_SQUEEZE equals dfx_pool (DFX_POOL_AVG_EXCLUDE_PADDING, window =
+ *      image, no padding) bit for bit; DFX_SE_GATE equals that pool -> dfx_fc (relu, u8) -> dfx_fc (s8) -> table lookup;
+ *      DFX_SE_SCALE equals the formula above.  Parity unpinned: the reference has no such op. ---- */
+enum {  /* dfx_se_desc.mode */
+  DFX_SE_SCALE = 0,            /* the whole op: dst as above */
+  DFX_SE_GATE = 1,             /* dst is g, u8 {bs,c}, rows c bytes apart: the caller applies the gate elsewhere */
+  DFX_SE_SQUEEZE = 2           /* dst is z, u8 {bs,c}: global average pooling at any image size; needs no weights */
+};
+typedef struct dfx_se_desc {
+  int32_t bs, c, ih, iw;       /* ih * iw <= 2^23, c <= 16384 */
+  int32_t cr;                  /* the squeezed width, 1 .. 16384 (ignored by the kernels in DFX_SE_SQUEEZE) */
+  int32_t mode;                /* DFX_SE_* */
+  int32_t bia1_dt, bia2_dt;    /* DFX_UNDEF = none */
+  int32_t round_mode;          /* of every stage */
+  int32_t nscales1;            /* 1 or cr */
+  int32_t nscales2;            /* 1 or c */
+  int32_t nscales_out;         /* 1 or c */
+  int32_t force_path;          /* -1 auto, else DFX_SE_BAND | DFX_SE_GENERIC */
+} dfx_se_desc;
+enum {  /* dfx_se_info.path */
+  DFX_SE_BAND = 0,             /* se_squeeze_kernel + se_excite_kernel + se_scale_kernel (se.cuh): a lane owns 16 bytes of
+                                  channels.  The squeeze sums bytes as packed 16-bit halves, flushed to s32 every 257 pixels
+                                  at the latest, one workgroup per (image, slice of pixels), partial sums into the handle's
+                                  slab [bs][slices][c]; the scale kernel keeps a lane's 16 gate bytes and scales in
+                                  registers and walks down pixels.  Class: c % 16 == 0, src and dst 16-byte aligned (checked
+                                  per submit: other pointers take the generic kernels for that submit), one image below
+                                  2^31 bytes.  Bit-identical to the generic kernels.  AUTO RULE: DFX_SE_AUTO_NOTE below. */
+  DFX_SE_GENERIC = 1           /* everything else (c = 72, 120): se_squeeze_generic, one thread per (image, channel), and
+                                  se_scale_generic, one thread per byte, grid-stride; se_excite_kernel serves both paths */
+};
+/* DFX_SE_AUTO_NOTE: auto takes DFX_SE_BAND everywhere in its class.  On the 18 points of profiles/se/bench_se.txt (the SE
+ * blocks of EfficientNet-B0 and SE-ResNeXt-50 at N = 1 and 32, buffers in rotation beyond the Infinity Cache) the generic
+ * kernels are 1.4 to 1.8 times slower on the 7x7 maps, 5 times on 14x14 and 16 to 125 times from 28x28 up; no point has
+ * them faster.  14 to 35 us per op, about 13 us of it the three dependent launch boundaries. */
+typedef struct dfx_se_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t slices;              /* pixel slices per image of the squeeze kernel (1 on the generic path) */
+  int32_t grid, block, lds_bytes;  /* of the squeeze kernel */
+  int32_t device;
+  uint64_t algorithmic_bytes;  /* DFX_SE_SCALE: src twice + dst; the other modes: src + the {bs,c} result */
+  char kernel_name[96];
+} dfx_se_info;
+typedef struct dfx_se dfx_se_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -912,6 +976,31 @@ int dfx_fc_submit(dfx_fc_t *h, const void *src_dev, void *dst_dev, dfx_stream_t 
 int dfx_fc_submit_host(dfx_fc_t *h, const void *src_host, void *dst_host); /* synchronous */
 int dfx_fc_query(const dfx_fc_t *h, dfx_fc_info *info);
 int dfx_fc_destroy(dfx_fc_t *h);
+
+/* ---- squeeze-and-excitation (dfx_se_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for a size below 1, ih * iw > 2^23, c or cr > 16384 (the accumulators stay in s32), bs * ih * iw * c
+ *      of 2^40 or more, a bad mode / bias dtype / round mode / nscales1 / nscales2 / nscales_out / force_path;
+ *      DFX_ERR_UNSUPPORTED only for force_path = DFX_SE_BAND outside that class.  "No HIP device" is reported only for a
+ *      valid descriptor.  set_weights: host pointers, copied; w1 s8 {cr,c}, w2 s8 {c,cr}, bia1 cr entries of bia1_dt, bia2
+ *      c entries of bia2_dt (NULL when DFX_UNDEF), lut 256 bytes; it may be called again (not while a submit of the handle
+ *      is in flight).  submit: asynchronous on `s`; src and dst must be non-null (DFX_ERR_INVALID, nothing is launched);
+ *      DFX_ERR_STATE before set_weights in DFX_SE_SCALE and DFX_SE_GATE, never in DFX_SE_SQUEEZE, which takes no weights.
+ *      DFX_SE_SCALE: dst may BE src, a dst range that overlaps src's in any other way is DFX_ERR_INVALID; in the other two
+ *      modes the {bs,c} result must not overlap src at all.  Pointers that are not 16-byte aligned take the generic kernels
+ *      for that submit, as pooling and resize do.  The handle owns the scratch between its launches (two in DFX_SE_GATE
+ *      and DFX_SE_SQUEEZE, three in DFX_SE_SCALE): the s32 slab of partial sums [bs][slices][c] and the {bs,c} gate, so its
+ *      submits are SERIALISED on the device exactly as dfx_fc's MFMA path and dfx_catconv's two-launch path (see there);
+ *      the host never blocks.  The partial sums are integers: every slice count gives the same bits.
+ *      Tuning switches: DFX_SE_SLICES=n forces the slice count (clamped to 1 .. ih*iw; default: at least two workgroups per
+ *      CU where the tensor allows it and at least 64 pixels per slice), DFX_SE_GRID=n caps the grid of every SE kernel.
+ *      No CPU fallback. ---- */
+int dfx_se_create(const dfx_se_desc *desc, dfx_se_t **out);
+int dfx_se_set_weights(dfx_se_t *h, const int8_t *w1, const void *bia1, const float *scales1, const int8_t *w2, const void *bia2,
+                       const float *scales2, const uint8_t *lut, const float *out_scales);
+int dfx_se_submit(dfx_se_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_se_submit_host(dfx_se_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_se_query(const dfx_se_t *h, dfx_se_info *info);
+int dfx_se_destroy(dfx_se_t *h);
 
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,

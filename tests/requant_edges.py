@@ -170,14 +170,10 @@ def exact_acc(case, data):
     return acc0, mid @ data["w1"].reshape(case.oc1x1, case.oc).astype(np.int64).T
 
 
-def count_ties(case, acc, bias, k, stage):
-    """ties of (acc + bias) * 2^-k among the values that stay inside the unsaturated output range: dict with
-    total / below (the even neighbour is the one below: nearest-even rounds down) / above / negative"""
-    fused = bool(case.oc1x1)
-    final = stage == 1 or not fused
-    relu = (case.relu1 if stage == 1 else case.relu0) or (not final) or case.dst_dt == C.U8
-    dt = case.dst_dt if final else C.U8
-    t = acc + (0 if bias is None else bias.astype(np.int64))
+def count_ties_of(t, k, dt, relu):
+    """ties of t * 2^-k (t: exact int64 accumulator + bias) among the values that stay inside the unsaturated range of
+    the output type dt after the ReLU (if any): dict with total / below (the even neighbour is the one below:
+    nearest-even rounds down) / above / negative / need_negative.  Shared with op_ties.py."""
     half = 1 << (k - 1)
     tie = (t & ((1 << k) - 1)) == half
     fl = t >> k                                                   # floor(t / 2^k); the tie sits at fl + 1/2
@@ -188,6 +184,21 @@ def count_ties(case, acc, bias, k, stage):
     return dict(total=int(inside.sum()), below=int((inside & (fl % 2 == 0)).sum()),
                 above=int((inside & (fl % 2 != 0)).sum()), negative=int((inside & (fl < 0)).sum()),
                 need_negative=(not relu) and dt in (C.S8, C.S32, C.F32))
+
+
+def count_ties(case, acc, bias, k, stage):
+    """count_ties_of for one stage of a conv case: the intermediate of a fused op is u8 behind a ReLU"""
+    fused = bool(case.oc1x1)
+    final = stage == 1 or not fused
+    relu = (case.relu1 if stage == 1 else case.relu0) or (not final) or case.dst_dt == C.U8
+    dt = case.dst_dt if final else C.U8
+    return count_ties_of(acc + (0 if bias is None else bias.astype(np.int64)), k, dt, relu)
+
+
+def assert_enough_ties(n, what):
+    """at least 50 ties, 15 with the even neighbour below, 15 above and, where negative results survive, 15 negative"""
+    assert n["total"] >= 50 and n["below"] >= 15 and n["above"] >= 15, (what, n)
+    assert not n["need_negative"] or n["negative"] >= 15, (what, n)
 
 
 def tie_data(case, stage, k):
@@ -205,8 +216,7 @@ def tie_data(case, stage, k):
     bias = data["bia0"] if stage == 0 else data["bia1"]
     assert bias is None or bias.dtype != np.float32, "tie data needs integer biases"
     n = count_ties(case, acc0 if stage == 0 else acc1, bias, k, stage)
-    assert n["total"] >= 50 and n["below"] >= 15 and n["above"] >= 15, (case.ident(), stage, k, n)
-    assert not n["need_negative"] or n["negative"] >= 15, (case.ident(), stage, k, n)
+    assert_enough_ties(n, (case.ident(), stage, k))
     return data, n
 
 

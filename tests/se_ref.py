@@ -7,11 +7,12 @@ matrix products, refmath's _requant / _store unchanged -- which tests/test_se_cp
 average pooling and fc_ref, and tests/test_gpu_se.py compares the GPU against, bit for bit.
 """
 import functools
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import numpy as np
 
 import cases as C
+import requant_edges as E
 from refmath import _requant, _store
 
 F32, S32, S8, U8, UNDEF = C.F32, C.S32, C.S8, C.U8, C.UNDEF
@@ -231,3 +232,23 @@ SLICE_VALUES = (1, 2, 3, 7, 561, 10 ** 6)
 GRID_CASES = [SeCase("grid", 3, 14, 14, 48, 12, seed=5100), SeCase("grid", 2, 33, 17, 1152, 48, per_channel=True, seed=5200)]
 GRID_VALUES = (1, 3)
 FLUSH_PIXELS = (256, 257, 258, 561)
+
+
+# --- rescale ties: sat_u8(cvt(src * gate * out_scale)) with out_scale = 2^-8 (the natural deployment value) and 2^-7 puts
+#     every product src * gate that is an odd multiple of 2^(k-1) on a tie.  The table's out_scales (1 / 255, 1 / 100
+#     and per-channel multiples) never do. ------------------------------------------------------------------------------
+TIE_CASE = SeCase("ties", 3, 14, 14, 64, 12)
+TIE_LOG2 = (8, 7)
+
+
+def tie_data(k, rm):
+    """-> (case, data, stages, counts): generate(TIE_CASE with round mode rm) with out_scales = 2^-k.  Refuses data
+    whose products src * gate do not hold requant_edges' numbers of ties inside the u8 range (assert_enough_ties; the
+    products are never negative)."""
+    case = replace(TIE_CASE, rm=rm)
+    data = dict(generate(case)[0], out_scales=np.array([2.0 ** -k], dtype=np.float32))
+    st = stages(case, data)
+    m = data["src"].astype(np.int64) * st["g"].astype(np.int64)[:, None, None, :]
+    n = E.count_ties_of(m, k, U8, True)
+    E.assert_enough_ties(n, (case.ident(), k))
+    return case, data, st, n

@@ -262,7 +262,23 @@ def test_biases_absent_f32_s32(b1, b2):
         check(case, S.SCALE, S.BAND if case.band_class else S.GENERIC)
 
 
-# ---- 5. the defining properties, on the device -------------------------------------------------------------------------------
+def test_rescale_rounding_ties():
+    """out_scale = 2^-8 and 2^-7 put hundreds of the products src * gate on k + 1/2 (se_ref.tie_data counts them; no
+    out_scale of the table does): nearest-even (rm 0) and floor (rm 1) in sat_u8(cvt(src * gate * out_scale)) on the
+    band and the generic path, bit for bit"""
+    failures = []
+    for k in S.TIE_LOG2:
+        for rm in (0, 1):
+            case, data, st, n = S.tie_data(k, rm)
+            for path in (S.BAND, S.GENERIC):
+                try:
+                    check(case, S.SCALE, path, force_path=path, data_st=(data, st))
+                except AssertionError as e:
+                    failures.append("2^-%d rm %d path %d %r: %s" % (k, rm, path, n, str(e)[:600]))
+    assert not failures, "%d:\n%s" % (len(failures), "\n".join(failures))
+
+
+# ---- 5.the defining properties, on the device -------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", [S.SeCase("def", 3, 14, 14, 64, 12, seed=7400), S.SeCase("def", 2, 33, 17, 1152, 48, per_channel=True, seed=7500),
                                   S.SeCase("def", 2, 7, 7, 72, 5, rm=1, seed=7600), S.SeCase("def", 1, 5, 9, 17, 4, bia1_dt=S.F32, seed=7700)],
                          ids=lambda c: c.ident())

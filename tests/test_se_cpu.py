@@ -67,6 +67,24 @@ def test_case_conditions_hold(case):
     assert S.conditions(case, data, st) == []
 
 
+@pytest.mark.parametrize("k", S.TIE_LOG2)
+@pytest.mark.parametrize("rm", [0, 1])
+def test_rescale_tie_data_holds_ties_and_the_reference_rounds_them_as_integers_say(k, rm):
+    """tie_data's thresholds hold (it asserts them), the ties are what integer arithmetic says they are, and on them the
+    reference gives the even neighbour (rm 0) or the floor (rm 1)"""
+    case, data, st, n = S.tie_data(k, rm)
+    print("SE TIES 2^-%d rm %d: %r of %d" % (k, rm, n, st["dst"].size))
+    assert case.band_class and float(data["out_scales"][0]) == 2.0 ** -k and data["out_scales"].size == 1
+    m = data["src"].astype(np.int64) * st["g"].astype(np.int64)[:, None, None, :]
+    fl = m >> k
+    tie = ((m & ((1 << k) - 1)) == (1 << (k - 1))) & (fl < 255)
+    assert int(tie.sum()) == n["total"] >= 50 and n["below"] >= 15 and n["above"] >= 15
+    want = fl if rm else fl + (fl & 1)
+    assert np.array_equal(st["dst"][tie], want[tie].astype(np.uint8))
+    if rm == 0:
+        assert np.any(st["dst"][tie] == fl[tie]) and np.any(st["dst"][tie] == (fl + 1)[tie])
+
+
 def test_table_covers_its_axes():
     assert {c.c for c in TABLE} == set(S.BAND_C + S.GENERIC_C)
     assert {c.cr for c in TABLE} == set(S.CRS) and {c.bs for c in TABLE} == set(S.BATCHES)

@@ -25,6 +25,7 @@ from .capi import (  # noqa: F401
     COORD_ASYMMETRIC, ResizeDesc, ResizeInfo, Resize,
     FC_AUTO, FC_MFMA, FC_GENERIC, FcDesc, FcInfo, InnerProduct,
     SE_AUTO, SE_BAND, SE_GENERIC, SE_SCALE, SE_GATE, SE_SQUEEZE, SeDesc, SeInfo, SqueezeExcite,
+    WSUM_AUTO, WSUM_VEC, WSUM_GENERIC, WsumDesc, WsumInfo, ScaledSum, wsum_launches,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

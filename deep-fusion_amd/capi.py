@@ -29,6 +29,8 @@ COORD_HALF_PIXEL, COORD_ALIGN_CORNERS, COORD_ASYMMETRIC = 0, 1, 2
 FC_AUTO, FC_MFMA, FC_GENERIC = -1, 0, 1
 SE_AUTO, SE_BAND, SE_GENERIC = -1, 0, 1
 SE_SCALE, SE_GATE, SE_SQUEEZE = 0, 1, 2
+WSUM_AUTO, WSUM_VEC, WSUM_GENERIC = -1, 0, 1
+WSUM_MAX_INPUTS = 8
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -178,6 +180,17 @@ class SeDesc(ctypes.Structure):
 
 class SeInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "slices", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
+
+
+class WsumDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "h", "w", "c", "n_inputs")] + \
+               [("src_dt", ctypes.c_int32 * 8), ("nscales", ctypes.c_int32 * 8)] + \
+               [(n, ctypes.c_int32) for n in ("n_bias", "dst_dt", "round_mode", "post_relu", "lut_in_dt", "force_path")]
+
+
+class WsumInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
 
 
@@ -339,6 +352,12 @@ def lib():
         "dfx_se_submit_host": (i32, [vp, vp, vp]),
         "dfx_se_query": (i32, [vp, ctypes.POINTER(SeInfo)]),
         "dfx_se_destroy": (i32, [vp]),
+        "dfx_wsum_create": (i32, [ctypes.POINTER(WsumDesc), ctypes.POINTER(vp)]),
+        "dfx_wsum_set_params": (i32, [vp, ctypes.POINTER(vp), vp, vp]),
+        "dfx_wsum_submit": (i32, [vp, ctypes.POINTER(vp), vp, vp]),
+        "dfx_wsum_submit_host": (i32, [vp, ctypes.POINTER(vp), vp]),
+        "dfx_wsum_query": (i32, [vp, ctypes.POINTER(WsumInfo)]),
+        "dfx_wsum_destroy": (i32, [vp]),
         "dfx_dwpw_create": (i32, [ctypes.POINTER(DwPwDesc), ctypes.POINTER(vp)]),
         "dfx_dwpw_set_weights": (i32, [vp] * 7),
         "dfx_dwpw_submit": (i32, [vp, vp, vp, vp]),
@@ -358,6 +377,7 @@ def lib():
         "dfx_debug_dwpw_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_fc_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_resize_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_debug_wsum_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -381,6 +401,13 @@ def resize_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_resize_launches(v))
     return v[RESIZE_BAND], v[RESIZE_GENERIC]
+
+
+def wsum_launches():
+    """(vec, generic): dfx_wsum_submit calls of this process that launched each kernel (dfx_debug_wsum_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_wsum_launches(v))
+    return v[WSUM_VEC], v[WSUM_GENERIC]
 
 
 def _check(rc):
@@ -865,6 +892,54 @@ class SqueezeExcite(_Handle):
         assert s1.size == d.nscales1 and s2.size == d.nscales2 and so.size == d.nscales_out
         assert (b1 is None or b1.size == d.cr) and (b2 is None or b2.size == d.c)
         _check(lib().dfx_se_set_weights(self._h, _p(w1), _p(b1), _p(s1), _p(w2), _p(b2), _p(s2), _p(lut), _p(so)))
+
+
+class ScaledSum(_Handle):
+    """dfx_wsum_* handle: dst = post(sum_i float(src_i) * scale_i[k] + bias[k]) over NHWC tensors of one shape and mixed
+    dtypes (include/dfx.h): per-tensor or per-channel scales, optional bias, ReLU and a 256-entry byte table; dst may be
+    an input of its own element size.  src_dtypes / dst_dtype / lut_in: DFX_* codes or numpy dtypes."""
+
+    _OP, _INFO = "dfx_wsum", WsumInfo
+
+    def __init__(self, shape_nhwc, src_dtypes, dst_dtype, nscales, n_bias=0, post_relu=False, lut_in=None,
+                 rm=ROUND_NEAREST, force_path=WSUM_AUTO):
+        code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
+        bs, h, w, c = shape_nhwc
+        d = WsumDesc()
+        d.bs, d.h, d.w, d.c, d.n_inputs = bs, h, w, c, len(src_dtypes)
+        for i, (t, ns) in enumerate(zip(list(src_dtypes)[:8], list(nscales)[:8])):
+            d.src_dt[i], d.nscales[i] = code(t), ns
+        d.n_bias, d.dst_dt, d.round_mode, d.post_relu = n_bias, code(dst_dtype), rm, int(post_relu)
+        d.lut_in_dt, d.force_path = DFX_UNDEF if lut_in is None else code(lut_in), force_path
+        self.desc = d
+        self.shape = self.dst_shape = (bs, h, w, c)
+        self._create(d)
+        self.src_np_dtypes = [_NP[d.src_dt[i]] for i in range(d.n_inputs)]
+        self.dst_np_dtype = _NP[d.dst_dt]
+
+    def set_params(self, scales, bias=None, lut=None):
+        """scales: one array of nscales[i] floats per input; bias: n_bias floats; lut: 256 bytes"""
+        d = self.desc
+        sc = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in scales]
+        assert len(sc) == d.n_inputs and all(s.size == d.nscales[i] for i, s in enumerate(sc))
+        b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32).reshape(-1)
+        assert (b is None and d.n_bias == 0) or (b is not None and b.size == d.n_bias)
+        t = None if lut is None else np.ascontiguousarray(lut).view(np.uint8).reshape(-1)
+        assert t is None or t.size == 256
+        ptrs = _ptr_array(sc, lambda a: a.ctypes.data)
+        _check(lib().dfx_wsum_set_params(self._h, ptrs, _p(b), _p(t)))
+
+    def submit(self, srcs_dev, dst_dev, stream=None):
+        """asynchronous; srcs_dev: torch CUDA tensors (or raw pointers), dst_dev may be one of them"""
+        ptrs = _ptr_array(srcs_dev, lambda t: _dev_ptr(t).value)
+        _check(lib().dfx_wsum_submit(self._h, ptrs, _dev_ptr(dst_dev), _stream_ptr(stream)))
+
+    def submit_host(self, srcs_np):
+        srcs = [np.ascontiguousarray(s, dtype=t) for s, t in zip(srcs_np, self.src_np_dtypes)]
+        assert len(srcs) == self.desc.n_inputs and all(s.shape == self.shape for s in srcs)
+        dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
+        _check(lib().dfx_wsum_submit_host(self._h, _ptr_array(srcs, lambda a: a.ctypes.data), _p(dst)))
+        return dst
 
 
 class DwPwConv(_Handle):

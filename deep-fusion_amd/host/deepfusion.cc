@@ -2316,6 +2316,161 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- scaled element-wise sum (dfx_wsum_*): 1 to 8 nhwc tensors of mixed dtypes, scales, bias, ReLU, table.  The scales,
+// the bias and the table are copied at construction: nothing to hash.  dst may be one of the srcs; every src is registered
+// as a read and dst as a write (op_state), so an in-place op waits for earlier readers of that tensor on other streams.
+// Batch sharding is op_resize's: every tensor is batch-major. ----
+class op_scaled_sum : public op {
+public:
+  op_scaled_sum(const std::vector<std::unique_ptr<memory>> &srcs, const std::vector<std::vector<float>> &scales, std::unique_ptr<memory> &dst,
+                const std::vector<float> &bias, bool post_relu, const std::vector<u8> &table, memory::dtype table_in, round_mode rm)
+      : dst_(dst.get()), h_(nullptr) {
+    using fmt = memory::format;
+    if (!dst_ || srcs.empty() || srcs.size() > DFX_WSUM_MAX_INPUTS) error_and_exit("Init ScaledSum op failed! (1 to 8 sources and a dst)");
+    if (scales.size() != srcs.size()) error_and_exit("Init ScaledSum op failed! (one vector of scales per source)");
+    if (dst_->dim_format() != fmt::nhwc) error_and_exit("Init ScaledSum op failed! (format)");
+    if ((table_in != memory::dtype::undef) != !table.empty() || (!table.empty() && table.size() != 256))
+      error_and_exit("Init ScaledSum op failed! (a table has 256 entries and needs table_in)");
+    auto o = dst_->std_dims();
+    dfx_wsum_desc d;
+    memset(&d, 0, sizeof(d));
+    d.bs = o[0]; d.c = o[1]; d.h = o[2]; d.w = o[3];
+    d.n_inputs = (int)srcs.size();
+    for (size_t i = 0; i < srcs.size(); ++i) {
+      memory *m = srcs[i].get();
+      if (!m || m->dim_format() != fmt::nhwc || m->std_dims() != o) error_and_exit("Init ScaledSum op failed! (format / shape of a source)");
+      srcs_.push_back(m);
+      d.src_dt[i] = to_dfx_dtype(m->data_type());
+      d.nscales[i] = (int)scales[i].size();
+    }
+    d.n_bias = (int)bias.size();
+    d.dst_dt = to_dfx_dtype(dst_->data_type());
+    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.post_relu = post_relu ? 1 : 0;
+    d.lut_in_dt = to_dfx_dtype(table_in);
+    d.force_path = -1;
+    const size_t img = (size_t)d.h * d.w * d.c;
+    for (memory *m : srcs_) src_img_.push_back(img * dtype_size(m->data_type()));
+    dst_img_ = img * dtype_size(dst_->data_type());
+    std::vector<const float *> sp;
+    for (const std::vector<float> &s : scales) sp.push_back(s.data());
+    const float *bp = bias.empty() ? nullptr : bias.data();
+    const u8 *tp = table.empty() ? nullptr : table.data();
+    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
+      shard sh;
+      sh.r = r;
+      dfx_wsum_desc ds = d;
+      ds.bs = r.n;
+      check_dfx(dfx_set_device(r.device), "set device");
+      if (dfx_wsum_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init ScaledSum op failed! (%s)", dfx_last_error());
+      check_dfx(dfx_wsum_set_params(sh.h, sp.data(), bp, tp), "wsum set_params");
+      check_dfx(dfx_stream_create(&sh.stream), "stream create");
+      for (size_t i = 0; i < srcs_.size(); ++i) {
+        void *p = nullptr;
+        check_dfx(dfx_mem_alloc_device(&p, (size_t)r.n * src_img_[i]), "device alloc");
+        sh.src.push_back(p);
+      }
+      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
+      shards_.push_back(sh);
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    if (dfx_wsum_create(&d, &h_) != DFX_OK) error_and_exit("Init ScaledSum op failed! (%s)", dfx_last_error());
+    check_dfx(dfx_wsum_set_params(h_, sp.data(), bp, tp), "wsum set_params");
+    st_.ensure_stream();
+  }
+  ~op_scaled_sum() override {
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      dfx_wsum_destroy(sh.h);
+      dfx_stream_destroy(sh.stream);
+      for (void *p : sh.src) dfx_mem_free_device(p);
+      dfx_mem_free_device(sh.dst);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire(*dst_);
+    dfx_wsum_destroy(h_);
+  }
+
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  void submit_async() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(false);
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled(*dst_);
+    }
+  }
+
+protected:
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard; every source is uploaded before dst's host bytes change)
+    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      for (size_t i = 0; i < srcs_.size(); ++i) {
+        const char *hs = static_cast<const char *>(srcs_[i]->host_data());
+        check_dfx(dfx_memcpy_h2d(sh.src[i], hs + sh.r.n0 * src_img_[i], sh.r.n * src_img_[i], sh.stream), "H2D copy");
+      }
+      check_dfx(dfx_wsum_submit(sh.h, (const void *const *)sh.src.data(), sh.dst, sh.stream), "wsum submit");
+      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    detail::op_state::host_is_current(*dst_);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  void run(bool sync_host) {
+    std::vector<const void *> p;
+    for (memory *m : srcs_) p.push_back(st_.sync_in(*m, sync_host));  // (a source may be dst: uploaded, then overwritten)
+    void *o = st_.device_out(*dst_);
+    st_.profile_begin();
+    check_dfx(dfx_wsum_submit(h_, p.data(), o, st_.stream), "wsum submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "scaled_sum"; }
+
+private:
+  struct shard {
+    detail::shard_range r;
+    dfx_wsum_t *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    std::vector<void *> src;
+    void *dst = nullptr;
+  };
+  std::vector<memory *> srcs_;
+  memory *dst_;
+  dfx_wsum_t *h_;
+  std::vector<size_t> src_img_;  // bytes per image
+  size_t dst_img_;
+  detail::op_state st_;
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
+};
+
 // ---- squeeze-and-excitation (dfx_se_*) and, with no weights, the global average pooling it starts with.  The two weight
 // tensors are plain oihw {cr, c, 1, 1} and {c, cr, 1, 1}; dst may be src.  Weight hashing and batch sharding are
 // op_depthwise_conv's: the op is per image, so shards are independent. ----
@@ -2747,6 +2902,12 @@ std::unique_ptr<op> squeeze_excite(const std::unique_ptr<memory> &src, const std
                                    std::unique_ptr<memory> &dst, std::vector<float> scales1, std::vector<float> scales2,
                                    std::vector<float> out_scales, round_mode rm) {
   return std::unique_ptr<op>(new op_squeeze_excite(src, &wei1, &bia1, &wei2, &bia2, &gate_table, dst, scales1, scales2, out_scales, rm));
+}
+
+std::unique_ptr<op> scaled_sum(const std::vector<std::unique_ptr<memory>> &srcs, const std::vector<std::vector<float>> &scales,
+                               std::unique_ptr<memory> &dst, const std::vector<float> &bias, bool post_relu, const std::vector<u8> &table,
+                               memory::dtype table_in, round_mode rm) {
+  return std::unique_ptr<op>(new op_scaled_sum(srcs, scales, dst, bias, post_relu, table, table_in, rm));
 }
 
 std::unique_ptr<op> global_avg_pool(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst) {

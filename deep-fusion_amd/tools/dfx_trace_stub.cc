@@ -439,4 +439,22 @@ int dfx_se_set_weights(dfx_se_t *h, const int8_t *w1, const void *b1, const floa
 int dfx_se_submit(dfx_se_t *h, const void *src, void *dst, dfx_stream_t s) { return submit1(h, "dfx_se_submit", src, dst, s); }
 int dfx_se_destroy(dfx_se_t *h) { return destroy_handle(h); }
 
+// ---- scaled element-wise sum (dst may be an input) ----
+int dfx_wsum_create(const dfx_wsum_desc *d, dfx_wsum_t **out) {
+  if (!d || !out || d->bs < 1 || d->n_inputs < 1 || d->n_inputs > DFX_WSUM_MAX_INPUTS) return fail(DFX_ERR_INVALID, "bad wsum descriptor");
+  handle *h = new_handle("wsum");
+  const size_t elems = (size_t)d->bs * d->h * d->w * d->c;
+  for (int i = 0; i < d->n_inputs; ++i) h->src.push_back(elems * dt_size(d->src_dt[i]));
+  h->dst = elems * dt_size(d->dst_dt);
+  *out = reinterpret_cast<dfx_wsum_t *>(h);
+  return DFX_OK;
+}
+int dfx_wsum_set_params(dfx_wsum_t *h, const float *const *, const float *, const uint8_t *) {
+  return set_weights(h, "dfx_wsum_set_params", {});
+}
+int dfx_wsum_submit(dfx_wsum_t *h, const void *const *srcs, void *dst, dfx_stream_t s) {
+  return submit(h, "dfx_wsum_submit", srcs, nullptr, dst, s);
+}
+int dfx_wsum_destroy(dfx_wsum_t *h) { return destroy_handle(h); }
+
 }  // extern "C"

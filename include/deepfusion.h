@@ -397,6 +397,26 @@ std::unique_ptr<op> squeeze_excite(const std::unique_ptr<memory> &src,
                                    round_mode rm = round_mode::nearest);
 std::unique_ptr<op> global_avg_pool(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst);
 
+// ---- extension: scaled element-wise sum (dfx_wsum_* in dfx.h): the join of branches that do not share one quantisation
+// step -- the ResNet shortcut, a MobileNetV2 / EfficientNet linear bottleneck, a quantised FPN level add, a conv's s32 / f32
+// result added to a u8 tensor -- in ONE launch, where eltwise_sum() (one dtype, no scale) needs a reorder() per branch
+// first and rounds twice.  srcs: 1 to 8 nhwc tensors of dst's dims, each u8 / s8 / s32 / f32 on its own; scales: one
+// vector per src with 1 or c entries; bias: none, 1 or c floats (zero points, folded constants); dst: nhwc u8 / s8 / f32.
+// dst = cvt(relu?(sum_i float(src_i) * scale_i[k] + bias[k])), every multiply and add a separately rounded f32 operation,
+// left to right; cvt is reorder()'s conversion.  With a 256-entry `table` (table_in = u8 or s8: the type the value is
+// converted to first; index t or t + 128, squeeze_excite()'s convention) the table's byte is stored instead: swish,
+// h-swish or any other activation of a 1-byte tensor is scaled_sum({x}, {{s}}, y, {}, false, table, dtype::s8).  dst may BE
+// any src of its own element size (in place: the op orders itself behind earlier readers of that tensor), and one tensor
+// may be given as several srcs.  c a multiple of 16 runs on a 16-byte kernel, everything else on a generic one.  submit /
+// submit_async / wait and DEEPFUSION_DEVICES sharding over the batch are depthwise_conv()'s. ----
+std::unique_ptr<op> scaled_sum(const std::vector<std::unique_ptr<memory>> &srcs,
+                               const std::vector<std::vector<float>> &scales,
+                               std::unique_ptr<memory> &dst,
+                               const std::vector<float> &bias = {}, bool post_relu = false,
+                               const std::vector<u8> &table = {},
+                               memory::dtype table_in = memory::dtype::undef,
+                               round_mode rm = round_mode::nearest);
+
 // ---- extension: depthwise conv + pointwise conv, the depthwise-separable block (dfx_dwpw_* in dfx.h).  Stage 0 is
 // depthwise_conv() with a u8 result (ReLU implied), stage 1 a 1x1 stride-1 unpadded conv() on that tensor; dst holds,
 // bit for bit, what the two ops give one after the other.  wei_dw: plain oihw s8 {c, 1, kh, kw}; wei_pw: OIhw4i16o4i

@@ -623,6 +623,71 @@ typedef struct dfx_se_info {
 } dfx_se_info;
 typedef struct dfx_se dfx_se_t;
 
+/* ---- scaled element-wise sum: the join of two or more branches that do NOT share one quantisation step -- the ResNet
+ *      shortcut (u8 block output + u8 identity), the MobileNetV2 / EfficientNet linear bottleneck (s8 + s8), a quantised FPN
+ *      level add with per-channel scales, a conv's s32 / f32 result added to a u8 tensor -- and, with a byte table, any
+ *      activation of a 1-byte tensor (swish / h-swish: n_inputs = 1).  dfx_eltwise has no scale anywhere; reorder per branch +
+ *      dfx_eltwise costs two or three extra round trips of the largest tensors and rounds twice.
+ *        src_i  NHWC {bs,h,w,c} of src_dt[i], i < n_inputs <= 8, dtypes independent of each other;  dst NHWC {bs,h,w,c}
+ *        s_i    nscales[i] = 1 (per tensor) or c (per channel) floats;  bias: n_bias = 0, 1 or c floats (zero points and
+ *               folded constants);  lut: 256 bytes
+ *      ARITHMETIC, for element (n,y,x,k).  Every f32 operation is rounded separately and there is never an FMA:
+ *        v      = float(src_0) * s_0[k]            u8 / s8 exact, s32 round-to-nearest-even, f32 as is
+ *        v      = v + float(src_i) * s_i[k]        i = 1 .. n-1, left to right: one multiply, then one add
+ *        v      = v + bias[k]                      only if n_bias != 0
+ *        v      = vmaxps(+0, v)                    only if post_relu: ReLU(-0) = -0, ReLU(NaN) = NaN (dfx_eltwise's rule)
+ *        f32 dst: store v
+ *        no table: dst = cvt<dst_dt>(v)            the reorder's conversion: rint (ties to even; DFX_ROUND_NEAREST) or floor
+ *                                                  (DFX_ROUND_DOWN), NaN -> 0, then clamped to [0,255] / [-128,127]
+ *        table:    t = cvt<lut_in_dt>(v);  dst byte = lut[lut_in_dt == DFX_U8 ? t : t + 128]   (dfx_se's index convention),
+ *                                                  stored verbatim whatever dst_dt (u8 or s8) is
+ *      Denormal values are kept.  Defining properties (tests/test_gpu_wsum.py): n_inputs = 1 without bias, ReLU and table
+ *      equals dfx_reorder NHWC -> NHWC with the same dtypes, scales and round mode; all scales 1.0f over one dtype equals
+ *      dfx_eltwise wherever the f32 sums are exact; n_inputs = 1, scale 1 with a table is the table.  Not built:
+ *      broadcasting, products, NCHW.  Parity unpinned: the reference has no such op. ---- */
+enum { DFX_WSUM_MAX_INPUTS = 8 };
+typedef struct dfx_wsum_desc {
+  int32_t bs, h, w, c;         /* h * w * c < 2^31 (one image); the whole tensor at most 2^40 elements, 64-bit offsets */
+  int32_t n_inputs;            /* 1 .. 8 */
+  int32_t src_dt[8];           /* DFX_U8 | DFX_S8 | DFX_S32 | DFX_F32 each; entries from n_inputs on are ignored */
+  int32_t nscales[8];          /* 1 or c each */
+  int32_t n_bias;              /* 0, 1 or c (f32) */
+  int32_t dst_dt;              /* DFX_U8 | DFX_S8 | DFX_F32 (DFX_S32: DFX_ERR_UNSUPPORTED, as in the reorder) */
+  int32_t round_mode;          /* DFX_ROUND_* */
+  int32_t post_relu;           /* 0 | 1 */
+  int32_t lut_in_dt;           /* DFX_UNDEF: no table; DFX_U8 | DFX_S8: the table's index type (dst_dt must be u8 or s8) */
+  int32_t force_path;          /* -1 auto, else DFX_WSUM_VEC | DFX_WSUM_GENERIC */
+} dfx_wsum_desc;
+enum {  /* dfx_wsum_info.path */
+  DFX_WSUM_VEC = 0,            /* wsum_vec_kernel (wsum.cuh): a lane owns 16 consecutive channels of a pixel: one 16-byte
+                                  load from a 1-byte input, four from a 4-byte input; one 16-byte store, four for f32.  The
+                                  dtype of each input is a wave-uniform runtime switch; dst type, ReLU, table and round mode
+                                  are template parameters.  Per-tensor scales and a single bias travel as kernel arguments;
+                                  per-channel scales, a per-channel bias and the table are staged in LDS once per workgroup.
+                                  Class: c % 16 == 0; the staged constants ((per-channel inputs + per-channel bias) * c
+                                  floats + the table) fit 64 KiB; every pointer 16-byte aligned (checked per submit: other
+                                  pointers take the generic kernel for that submit).  Bit-identical to the generic kernel.
+                                  AUTO RULE: see DFX_WSUM_AUTO_NOTE below. */
+  DFX_WSUM_GENERIC = 1         /* everything else: one thread per output element, grid-stride */
+};
+/* DFX_WSUM_AUTO_NOTE: auto takes DFX_WSUM_VEC in its class only where the tensor has at least 2^19 elements (a vec launch
+ * of 128 workgroups or more), DFX_WSUM_GENERIC below.  On the 10 points of profiles/wsum/bench_wsum.txt (res2 shortcut
+ * 56x56x256 u8 + u8 and u8 + s32, MobileNetV2 14x14x96 s8 + s8, FPN 64x64x256 with per-channel scales, an h-swish table
+ * pass on 112x112x32; N = 1 and 128 / 16; buffers in rotation beyond the Infinity Cache, three legs interleaved) the vec
+ * kernel is 1.3 to 5.4 times faster than the generic one on the 8 points from 802 816 elements up (1.4 to 5.2 TB/s of
+ * algorithmic bytes at N = 16 / 128), but both sit on the launch floor below: 14x14x96 at N = 1 (18 816 elements, 5
+ * workgroups) is 6 % slower on the vec kernel (6.1 against 5.7 us) and the table pass at N = 1 (401 408 elements, 98
+ * workgroups) 1.7 times slower (6.2 against 3.6 us).  The threshold lies between those 98 and the 196 workgroups of the
+ * smallest point the vec kernel wins. */
+typedef struct dfx_wsum_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_bytes;  /* all inputs + dst, one submit */
+  char kernel_name[96];
+} dfx_wsum_info;
+typedef struct dfx_wsum dfx_wsum_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -1002,6 +1067,29 @@ int dfx_se_submit_host(dfx_se_t *h, const void *src_host, void *dst_host); /* sy
 int dfx_se_query(const dfx_se_t *h, dfx_se_info *info);
 int dfx_se_destroy(dfx_se_t *h);
 
+/* ---- scaled element-wise sum (dfx_wsum_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for a size below 1, h * w * c of 2^31 or more, bs * h * w * c beyond 2^40, n_inputs outside 1 .. 8,
+ *      a bad src / dst / table dtype, nscales[i] other than 1 or c, n_bias other than 0, 1 or c, a bad round mode /
+ *      post_relu / force_path, a table with an f32 dst; DFX_ERR_UNSUPPORTED for dst_dt = DFX_S32 and for force_path =
+ *      DFX_WSUM_VEC outside that class.  "No HIP device" is reported only for a valid descriptor.
+ *      set_params: host pointers, copied: scales[i] points to nscales[i] floats for every i < n_inputs; bias to n_bias
+ *      floats (ignored when n_bias = 0); lut to 256 bytes (ignored without a table).  A scale or bias that is not finite
+ *      is DFX_ERR_INVALID.  It may be called again (not while a submit of the handle is in flight).
+ *      submit: asynchronous on `s`; ONE launch; it never writes to the handle and every launch has its own copy of the
+ *      arguments: one handle serves several streams and host threads at once.  DFX_ERR_STATE before set_params.
+ *      srcs_dev[i] and dst must be non-null and aligned to their element.  ALIASING: dst may BE any input whose element
+ *      size equals dst's (every element is read from all inputs before its lane writes it); one buffer may be given as
+ *      several inputs; any other overlap of dst's range with an input's -- a 4-byte input at dst's address when dst is
+ *      1-byte included -- is DFX_ERR_INVALID and nothing is launched.  Pointers that are not 16-byte aligned take the
+ *      generic kernel for that submit, as resize and se do.
+ *      Tuning switch: DFX_WSUM_GRID=n caps the grid of either kernel.  No CPU fallback. ---- */
+int dfx_wsum_create(const dfx_wsum_desc *desc, dfx_wsum_t **out);
+int dfx_wsum_set_params(dfx_wsum_t *h, const float *const *scales, const float *bias, const uint8_t *lut);
+int dfx_wsum_submit(dfx_wsum_t *h, const void *const *srcs_dev, void *dst_dev, dfx_stream_t s);
+int dfx_wsum_submit_host(dfx_wsum_t *h, const void *const *srcs_host, void *dst_host); /* synchronous */
+int dfx_wsum_query(const dfx_wsum_t *h, dfx_wsum_info *info);
+int dfx_wsum_destroy(dfx_wsum_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -1087,6 +1175,8 @@ int dfx_debug_dwpw_requant(const dfx_dwpw_t *h, int32_t out[2]);
  * the generic kernel (out[DFX_RESIZE_GENERIC]) so far.  Process-wide, since submit does not write to the handle; it is
  * how a test sees the per-submit fallback of 16-byte-misaligned pointers, which dfx_resize_query does not report. */
 int dfx_debug_resize_launches(int64_t out[2]);
+/* the same for dfx_wsum_submit: out[DFX_WSUM_VEC], out[DFX_WSUM_GENERIC] */
+int dfx_debug_wsum_launches(int64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,8 @@ from .capi import (  # noqa: F401
     FC_AUTO, FC_MFMA, FC_GENERIC, FcDesc, FcInfo, InnerProduct,
     SE_AUTO, SE_BAND, SE_GENERIC, SE_SCALE, SE_GATE, SE_SQUEEZE, SeDesc, SeInfo, SqueezeExcite,
     WSUM_AUTO, WSUM_VEC, WSUM_GENERIC, WsumDesc, WsumInfo, ScaledSum, wsum_launches,
+    HEAD_TOPK, HEAD_SOFTMAX, HEAD_AUTO, HEAD_PIXEL, HEAD_ROW, HEAD_GENERIC, HeadDesc, HeadInfo, Head, TopK, Softmax,
+    head_launches, softmax_table,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

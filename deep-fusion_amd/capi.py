@@ -31,6 +31,8 @@ SE_AUTO, SE_BAND, SE_GENERIC = -1, 0, 1
 SE_SCALE, SE_GATE, SE_SQUEEZE = 0, 1, 2
 WSUM_AUTO, WSUM_VEC, WSUM_GENERIC = -1, 0, 1
 WSUM_MAX_INPUTS = 8
+HEAD_TOPK, HEAD_SOFTMAX = 0, 1
+HEAD_AUTO, HEAD_PIXEL, HEAD_ROW, HEAD_GENERIC = -1, 0, 1, 2
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -190,6 +192,17 @@ class WsumDesc(ctypes.Structure):
 
 
 class WsumInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
+
+
+class HeadDesc(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("mode", "src_dt", "dst_dt", "c", "src_ld", "dst_ld", "idx_ld", "k")] + \
+               [("out_scale", ctypes.c_float), ("force_path", ctypes.c_int32)]
+
+
+class HeadInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
 
@@ -358,6 +371,11 @@ def lib():
         "dfx_wsum_submit_host": (i32, [vp, ctypes.POINTER(vp), vp]),
         "dfx_wsum_query": (i32, [vp, ctypes.POINTER(WsumInfo)]),
         "dfx_wsum_destroy": (i32, [vp]),
+        "dfx_head_create": (i32, [ctypes.POINTER(HeadDesc), ctypes.POINTER(vp)]),
+        "dfx_head_set_table": (i32, [vp, vp]),
+        "dfx_head_submit": (i32, [vp, vp, vp, vp, vp]),
+        "dfx_head_query": (i32, [vp, ctypes.POINTER(HeadInfo)]),
+        "dfx_head_destroy": (i32, [vp]),
         "dfx_dwpw_create": (i32, [ctypes.POINTER(DwPwDesc), ctypes.POINTER(vp)]),
         "dfx_dwpw_set_weights": (i32, [vp] * 7),
         "dfx_dwpw_submit": (i32, [vp, vp, vp, vp]),
@@ -378,6 +396,7 @@ def lib():
         "dfx_debug_fc_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_resize_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
         "dfx_debug_wsum_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_debug_head_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -408,6 +427,24 @@ def wsum_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_wsum_launches(v))
     return v[WSUM_VEC], v[WSUM_GENERIC]
+
+
+def head_launches():
+    """(pixel, row, generic): dfx_head_submit calls of this process that launched each kernel (dfx_debug_head_launches)"""
+    v = (ctypes.c_int64 * 3)()
+    _check(lib().dfx_debug_head_launches(v))
+    return v[HEAD_PIXEL], v[HEAD_ROW], v[HEAD_GENERIC]
+
+
+def softmax_table(scale, c):
+    """The 256-entry uint32 table of a softmax over `c` channels of 1-byte logits with quantisation step `scale`:
+    E[d] = floor(exp(-d * scale) * floor((2^32 - 1) / c)), d the distance from the row maximum (include/dfx.h).  The sum of
+    any c entries stays within u32, and the probabilities are within 1e-6 absolute of a float64 softmax."""
+    if not 1 <= int(c) <= 65535:
+        raise ValueError("c must lie in 1 .. 65535")
+    top = (2 ** 32 - 1) // int(c)
+    d = np.arange(256, dtype=np.float64)
+    return np.floor(np.exp(-d * float(scale)) * top).astype(np.uint32)
 
 
 def _check(rc):
@@ -940,6 +977,49 @@ class ScaledSum(_Handle):
         dst = np.empty(self.dst_shape, dtype=self.dst_np_dtype)
         _check(lib().dfx_wsum_submit_host(self._h, _ptr_array(srcs, lambda a: a.ctypes.data), _p(dst)))
         return dst
+
+
+class Head(_Handle):
+    """dfx_head_* handle: channel top-k / argmax (mode HEAD_TOPK) or table softmax (HEAD_SOFTMAX) over a row matrix: `rows`
+    rows of `c` valid channels, src_ld elements apart (include/dfx.h).  An NHWC tensor is rows = bs*h*w, src_ld = C.
+    TOPK: dst_dtype is idx's (int32, or uint8 when c <= 256); submit(src, idx, val=None).  SOFTMAX: 1-byte src, dst_dtype
+    float32 or uint8; set_table() first; submit(src, dst)."""
+
+    _OP, _INFO = "dfx_head", HeadInfo
+
+    def __init__(self, rows, c, src_dtype, dst_dtype, mode=HEAD_TOPK, k=1, src_ld=None, dst_ld=None, idx_ld=None,
+                 out_scale=255.0, force_path=HEAD_AUTO):
+        code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
+        d = HeadDesc()
+        d.rows, d.mode, d.src_dt, d.dst_dt, d.c, d.k = rows, mode, code(src_dtype), code(dst_dtype), c, k
+        d.src_ld = c if src_ld is None else src_ld
+        d.dst_ld = c if dst_ld is None else dst_ld
+        d.idx_ld = k if idx_ld is None else idx_ld
+        d.out_scale, d.force_path = out_scale, force_path
+        self.desc = d
+        self._create(d)
+
+    def set_table(self, table):
+        t = np.ascontiguousarray(table, dtype=np.uint32).reshape(-1)
+        assert t.size == 256
+        _check(lib().dfx_head_set_table(self._h, _p(t)))
+
+    def submit(self, src_dev, out_dev, val_dev=None, stream=None):
+        """asynchronous; torch CUDA tensors (or raw pointers); out_dev: idx (TOPK) or dst (SOFTMAX)"""
+        _check(lib().dfx_head_submit(self._h, _dev_ptr(src_dev), _dev_ptr(out_dev),
+                                     None if val_dev is None else _dev_ptr(val_dev), _stream_ptr(stream)))
+
+
+class TopK(Head):
+    def __init__(self, rows, c, src_dtype, idx_dtype=np.int32, k=1, **kw):
+        Head.__init__(self, rows, c, src_dtype, idx_dtype, mode=HEAD_TOPK, k=k, **kw)
+
+
+class Softmax(Head):
+    def __init__(self, rows, c, src_dtype, dst_dtype=np.float32, table=None, **kw):
+        Head.__init__(self, rows, c, src_dtype, dst_dtype, mode=HEAD_SOFTMAX, **kw)
+        if table is not None:
+            self.set_table(table)
 
 
 class DwPwConv(_Handle):

@@ -2471,6 +2471,156 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- net head (dfx_head_*): channel top-k / argmax and table softmax over the rows of an nhwc tensor (rows = bs * h * w,
+// src_ld = C, c_valid <= C).  TOPK writes idx {bs, k, h, w} and, if given, val of src's dtype; SOFTMAX writes dst
+// {bs, C', h, w} with C' >= c_valid; the kernel leaves channels c_valid .. C'-1 of the device copy alone, so after the copy
+// back the host's pad channels are undefined (deepfusion.h says so).  The table is copied at construction: nothing to hash.  src is registered as a read,
+// idx / dst and val as writes (op_state).  Batch sharding is op_scaled_sum's: every tensor is batch-major. ----
+class op_head : public op {
+public:
+  op_head(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &out, memory *val, int mode, int k, int c_valid,
+          const std::array<uint32_t, 256> *table, float out_scale)
+      : src_(src.get()), out_(out.get()), val_(val), h_(nullptr) {
+    using fmt = memory::format;
+    if (!src_ || !out_) error_and_exit("Init Head op failed! (null tensor)");
+    if (src_->dim_format() != fmt::nhwc || out_->dim_format() != fmt::nhwc || (val_ && val_->dim_format() != fmt::nhwc))
+      error_and_exit("Init Head op failed! (format)");
+    auto i = src_->std_dims(), o = out_->std_dims();
+    if (i[0] != o[0] || i[2] != o[2] || i[3] != o[3]) error_and_exit("Init Head op failed! (batch size / height / width do not equal)");
+    if (val_ && (val_->std_dims() != o || val_->data_type() != src_->data_type())) error_and_exit("Init Head op failed! (val must have idx's dims and src's data type)");
+    dfx_head_desc d;
+    memset(&d, 0, sizeof(d));
+    const long long px = (long long)i[2] * i[3];
+    d.rows = (long long)i[0] * px;
+    d.mode = mode;
+    d.src_dt = to_dfx_dtype(src_->data_type());
+    d.dst_dt = to_dfx_dtype(out_->data_type());
+    d.c = c_valid > 0 ? c_valid : i[1];
+    d.src_ld = i[1];
+    d.k = k;
+    if (mode == DFX_HEAD_TOPK) {
+      if (o[1] != k) error_and_exit("Init Head op failed! (idx must be {bs, k, h, w})");
+      d.idx_ld = o[1];
+    } else {
+      d.dst_ld = o[1];
+    }
+    d.out_scale = out_scale;
+    d.force_path = -1;
+    src_img_ = (size_t)px * i[1] * dtype_size(src_->data_type());
+    out_img_ = (size_t)px * o[1] * dtype_size(out_->data_type());
+    val_img_ = val_ ? (size_t)px * o[1] * dtype_size(val_->data_type()) : 0;
+    for (const detail::shard_range &r : detail::plan_shards(i[0])) {
+      shard sh;
+      sh.r = r;
+      dfx_head_desc ds = d;
+      ds.rows = (long long)r.n * px;
+      check_dfx(dfx_set_device(r.device), "set device");
+      if (dfx_head_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init Head op failed! (%s)", dfx_last_error());
+      if (table && dfx_head_set_table(sh.h, table->data()) != DFX_OK) error_and_exit("Init Head op failed! (%s)", dfx_last_error());
+      check_dfx(dfx_stream_create(&sh.stream), "stream create");
+      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
+      check_dfx(dfx_mem_alloc_device(&sh.out, (size_t)r.n * out_img_), "device alloc");
+      if (val_) check_dfx(dfx_mem_alloc_device(&sh.val, (size_t)r.n * val_img_), "device alloc");
+      shards_.push_back(sh);
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    if (dfx_head_create(&d, &h_) != DFX_OK) error_and_exit("Init Head op failed! (%s)", dfx_last_error());
+    if (table && dfx_head_set_table(h_, table->data()) != DFX_OK) error_and_exit("Init Head op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_head() override {
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      dfx_head_destroy(sh.h);
+      dfx_stream_destroy(sh.stream);
+      dfx_mem_free_device(sh.src);
+      dfx_mem_free_device(sh.out);
+      dfx_mem_free_device(sh.val);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire(*out_);
+    dfx_head_destroy(h_);
+  }
+
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    st_.fetch_out(*out_);
+    if (val_) st_.fetch_out(*val_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*out_);
+  }
+  void submit_async() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(false);
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled(*out_);
+    }
+  }
+
+protected:
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
+    const char *hs = static_cast<const char *>(src_->host_data());
+    char *ho = static_cast<char *>(const_cast<void *>(out_->host_data()));
+    char *hv = val_ ? static_cast<char *>(const_cast<void *>(val_->host_data())) : nullptr;
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
+      check_dfx(dfx_head_submit(sh.h, sh.src, sh.out, sh.val, sh.stream), "head submit");
+      check_dfx(dfx_memcpy_d2h(ho + sh.r.n0 * out_img_, sh.out, sh.r.n * out_img_, sh.stream), "D2H copy");
+      if (val_) check_dfx(dfx_memcpy_d2h(hv + sh.r.n0 * val_img_, sh.val, sh.r.n * val_img_, sh.stream), "D2H copy");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    detail::op_state::host_is_current(*out_);
+    if (val_) detail::op_state::host_is_current(*val_);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  void run(bool sync_host) {
+    const void *in = st_.sync_in(*src_, sync_host);
+    void *o = st_.device_out(*out_);
+    void *v = val_ ? st_.device_out(*val_) : nullptr;
+    st_.profile_begin();
+    check_dfx(dfx_head_submit(h_, in, o, v, st_.stream), "head submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "head"; }
+
+private:
+  struct shard {
+    detail::shard_range r;
+    dfx_head_t *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    void *src = nullptr, *out = nullptr, *val = nullptr;
+  };
+  memory *src_, *out_, *val_;
+  dfx_head_t *h_;
+  size_t src_img_, out_img_, val_img_;  // bytes per image
+  detail::op_state st_;
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
+};
+
 // ---- squeeze-and-excitation (dfx_se_*) and, with no weights, the global average pooling it starts with.  The two weight
 // tensors are plain oihw {cr, c, 1, 1} and {c, cr, 1, 1}; dst may be src.  Weight hashing and batch sharding are
 // op_depthwise_conv's: the op is per image, so shards are independent. ----
@@ -2908,6 +3058,19 @@ std::unique_ptr<op> scaled_sum(const std::vector<std::unique_ptr<memory>> &srcs,
                                std::unique_ptr<memory> &dst, const std::vector<float> &bias, bool post_relu, const std::vector<u8> &table,
                                memory::dtype table_in, round_mode rm) {
   return std::unique_ptr<op>(new op_scaled_sum(srcs, scales, dst, bias, post_relu, table, table_in, rm));
+}
+
+std::unique_ptr<op> argmax(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, int c_valid) {
+  return std::unique_ptr<op>(new op_head(src, dst_idx, nullptr, DFX_HEAD_TOPK, 1, c_valid, nullptr, 0.f));
+}
+
+std::unique_ptr<op> top_k(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, memory *dst_val, int k, int c_valid) {
+  return std::unique_ptr<op>(new op_head(src, dst_idx, dst_val, DFX_HEAD_TOPK, k, c_valid, nullptr, 0.f));
+}
+
+std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &dst,
+                            float out_scale, int c_valid) {
+  return std::unique_ptr<op>(new op_head(src, dst, nullptr, DFX_HEAD_SOFTMAX, 0, c_valid, &table, out_scale));
 }
 
 std::unique_ptr<op> global_avg_pool(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst) {

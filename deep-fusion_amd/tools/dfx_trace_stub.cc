@@ -457,4 +457,31 @@ int dfx_wsum_submit(dfx_wsum_t *h, const void *const *srcs, void *dst, dfx_strea
 }
 int dfx_wsum_destroy(dfx_wsum_t *h) { return destroy_handle(h); }
 
+// ---- net head: one read (src), one write (idx or dst) and, when given, a second write (val; its bytes are kept in `lat`) ----
+int dfx_head_create(const dfx_head_desc *d, dfx_head_t **out) {
+  if (!d || !out || d->rows < 1 || d->c < 1 || d->src_ld < d->c) return fail(DFX_ERR_INVALID, "bad head descriptor");
+  handle *h = new_handle("head");
+  const bool topk = d->mode == DFX_HEAD_TOPK;
+  const size_t rows = (size_t)d->rows, ld = (size_t)(topk ? d->idx_ld : d->dst_ld), cols = (size_t)(topk ? d->k : d->c);
+  h->src.push_back(((rows - 1) * d->src_ld + d->c) * dt_size(d->src_dt));
+  h->dst = ((rows - 1) * ld + cols) * dt_size(d->dst_dt);
+  h->lat = topk ? ((rows - 1) * ld + cols) * dt_size(d->src_dt) : 0;
+  *out = reinterpret_cast<dfx_head_t *>(h);
+  return DFX_OK;
+}
+int dfx_head_set_table(dfx_head_t *h, const uint32_t *) { return set_weights(h, "dfx_head_set_table", {}); }
+int dfx_head_submit(dfx_head_t *hv, const void *src, void *idx_or_dst, void *val_or_null, dfx_stream_t s) {
+  handle *h = reinterpret_cast<handle *>(hv);
+  if (!h) return fail(DFX_ERR_INVALID, "null handle");
+  if (!stream_ok(s, "dfx_head_submit")) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_head_submit", {}};
+  add_range(r, src, h->src[0], false);
+  add_range(r, idx_or_dst, h->dst, true);
+  if (val_or_null) add_range(r, val_or_null, h->lat, true);
+  r.ranges.push_back({h->packed, 0, 1, false});
+  g_trace.push_back(r);
+  return DFX_OK;
+}
+int dfx_head_destroy(dfx_head_t *h) { return destroy_handle(h); }
+
 }  // extern "C"

@@ -417,6 +417,30 @@ std::unique_ptr<op> scaled_sum(const std::vector<std::unique_ptr<memory>> &srcs,
                                memory::dtype table_in = memory::dtype::undef,
                                round_mode rm = round_mode::nearest);
 
+// ---- extension: the net head (dfx_head_* in dfx.h): what turns the last layer's logits into the answer without leaving
+// the device.  src: an nhwc tensor {bs, C, h, w} of u8 / s8 / s32 / f32 -- a classifier's inner_product() dst {bs, oc, 1, 1}
+// or a segmentation net's resize()d logits; every pixel is a row of C channels of which the first c_valid take part
+// (c_valid = 0: all; DeepLab's 21 logits padded to 32 are read in place with c_valid = 21, whatever the pad channels hold).
+//   argmax(src, dst_idx)              dst_idx {bs, 1, h, w} s32, or u8 for c_valid <= 256: 1 byte per pixel instead of C
+//   top_k(src, dst_idx, dst_val, k)   k in 1 .. 8: dst_idx {bs, k, h, w}; dst_val (may be null) of idx's dims and src's dtype:
+//                                     the k largest elements, value descending, the lower channel first among equal values;
+//                                     f32 orders by IEEE totalOrder (-NaN < -Inf < -0 < +0 < +Inf < +NaN); bits verbatim
+//   softmax(src, table, dst)          u8 / s8 src only (reorder() s32 / f32 logits to 1 byte first); dst {bs, C', h, w} f32 or
+//                                     u8, C' >= c_valid.  The kernel does not write the channels from c_valid on; submit()
+//                                     and download() copy the whole tensor back, so on the HOST those pad channels are
+//                                     UNDEFINED afterwards (they hold what dst's device copy held).  No exp runs anywhere:
+//                                     `table` is E[d] = floor(exp(-d * s) * floor((2^32 - 1) / c_valid)) for the logits'
+//                                     quantisation step s, indexed by the distance d from the row maximum; p = float(E[d]) /
+//                                     float(sum of the row's E), one correctly rounded division; u8 dst: rint(p * out_scale)
+//                                     clamped to [0, 255].  A table with E[0] = 0 or c_valid * max(E) > 2^32 - 1 is refused.
+// Bit-exact and the same on every kernel path.  submit / submit_async / wait and DEEPFUSION_DEVICES sharding over the batch
+// are scaled_sum()'s. ----
+std::unique_ptr<op> argmax(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, int c_valid = 0);
+std::unique_ptr<op> top_k(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, memory *dst_val /* may be null */,
+                          int k, int c_valid = 0);
+std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array<uint32_t, 256> &table,
+                            std::unique_ptr<memory> &dst, float out_scale = 255.f, int c_valid = 0);
+
 // ---- extension: depthwise conv + pointwise conv, the depthwise-separable block (dfx_dwpw_* in dfx.h).  Stage 0 is
 // depthwise_conv() with a u8 result (ReLU implied), stage 1 a 1x1 stride-1 unpadded conv() on that tensor; dst holds,
 // bit for bit, what the two ops give one after the other.  wei_dw: plain oihw s8 {c, 1, kh, kw}; wei_pw: OIhw4i16o4i

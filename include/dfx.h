@@ -688,6 +688,88 @@ typedef struct dfx_wsum_info {
 } dfx_wsum_info;
 typedef struct dfx_wsum dfx_wsum_t;
 
+/* ---- net head: channel top-k / argmax and softmax over a ROW MATRIX, the last layer of every network README lists -- a
+ *      classifier's {bs, 1000} logits behind dfx_fc (softmax / top-5) and a segmentation net's logits behind dfx_resize
+ *      (argmax: 1 byte per pixel instead of 21, or 32 with the band kernel's padding).
+ *        src    `rows` rows of `c` valid channels, consecutive rows src_ld ELEMENTS apart.  No layout change: an NHWC
+ *               {bs,h,w,C} tensor is rows = bs*h*w, src_ld = C, c <= C (DeepLab's 21 logits padded to 32 are read in
+ *               place); dfx_fc's {bs, oc} dst is rows = bs.  Channels c .. src_ld-1 of a row NEVER take part, whatever
+ *               they hold.
+ *      DFX_HEAD_TOPK (argmax is k = 1): src u8 / s8 / s32 / f32, k in 1 .. 8, k <= c.
+ *        ORDER  total.  Integers order as themselves; f32 orders by IEEE totalOrder on the bit pattern:
+ *               -NaN < -Inf < ... < -0 < +0 < ... < +Inf < +NaN.  Row r's results are its k largest elements sorted by
+ *               (value descending, channel index ascending): equal values keep the lower index first.  Because the order
+ *               is total and ties are decided by the index, all (value, index) pairs of a row are distinct, so a
+ *               sequential scan and ANY tree reduction give the same bits: the three kernels agree bit for bit.
+ *        idx    {rows, k}, rows idx_ld elements apart, dst_dt = DFX_S32, or DFX_U8 when c <= 256
+ *        val    optional (may be NULL at submit): {rows, k} of src's dtype, rows idx_ld elements apart: the elements
+ *               themselves, bits verbatim (NaN payloads, -0, denormals)
+ *      DFX_HEAD_SOFTMAX: 1-byte src only (u8 / s8; a 4-byte src is DFX_ERR_UNSUPPORTED: dfx_reorder it to 1 byte first).
+ *        No exp runs on the device or anywhere in the library: the caller gives a 256-entry uint32 table E
+ *        (dfx_head_set_table), indexed by the distance from the row maximum.  For row r:
+ *          m   = max_k src[r,k]                    as an integer
+ *          d_k = m - src[r,k]                      0 .. 255 for both dtypes
+ *          S   = sum_k E[d_k]                      exact in u32 (set_table refuses a table that could overflow it)
+ *          p_k = float(E[d_k]) / float(S)          each conversion rounds once to nearest even; ONE correctly rounded f32
+ *                                                  division
+ *          f32 dst: store p_k
+ *          u8 dst:  v = p_k * out_scale            one separately rounded multiply, no FMA;  then the reorder's conversion
+ *                                                  (rint to even, clamped to [0,255])
+ *        dst rows are dst_ld >= c elements apart; elements c .. dst_ld-1 are NOT written.
+ *        THE TABLE.  E[d] = floor(exp(-d * s) * floor((2^32 - 1) / c)) for a logit step s (Python: dfa.softmax_table(s, c))
+ *        keeps S within u32 for every row and is within 1e-6 absolute of a float64 softmax for c up to 65535.
+ *      Not built: the argmax fused into dfx_resize's store, softmax of s32 / f32 logits, k > 8, NCHW, softmax + top-k in
+ *      one launch.  Parity unpinned: the reference has no such op. ---- */
+enum { DFX_HEAD_TOPK = 0, DFX_HEAD_SOFTMAX = 1 };  /* dfx_head_desc.mode */
+enum { DFX_HEAD_MAX_K = 8, DFX_HEAD_MAX_C = 65535 };
+typedef struct dfx_head_desc {
+  int64_t rows;                /* >= 1; rows * max(src_ld, dst_ld or idx_ld) <= 2^40, 64-bit offsets */
+  int32_t mode;                /* DFX_HEAD_TOPK | DFX_HEAD_SOFTMAX */
+  int32_t src_dt;              /* DFX_U8 | DFX_S8 | DFX_S32 | DFX_F32 (softmax: u8 / s8 only) */
+  int32_t dst_dt;              /* TOPK: idx type DFX_S32 | DFX_U8 (u8 needs c <= 256);  SOFTMAX: DFX_F32 | DFX_U8 */
+  int32_t c;                   /* valid channels, 1 .. 65535 */
+  int32_t src_ld;              /* elements between rows of src, >= c */
+  int32_t dst_ld;              /* SOFTMAX: elements between rows of dst, >= c;  TOPK: ignored */
+  int32_t idx_ld;              /* TOPK: elements between rows of idx (and of val), >= k;  SOFTMAX: ignored */
+  int32_t k;                   /* TOPK: 1 .. 8, <= c;  SOFTMAX: ignored */
+  float out_scale;             /* SOFTMAX with u8 dst: finite (255.0f for full range);  ignored otherwise */
+  int32_t force_path;          /* -1 auto, else DFX_HEAD_PIXEL | DFX_HEAD_ROW | DFX_HEAD_GENERIC */
+} dfx_head_desc;
+enum {  /* dfx_head_info.path */
+  DFX_HEAD_PIXEL = 0,          /* head_pixel_kernel (head.cuh): a lane owns a row (segmentation: millions of short rows).
+                                  Class: 1-byte src; TOPK with k = 1, or SOFTMAX; src_ld % 16 == 0 and src_ld <= 160;
+                                  every pointer 16-byte aligned (checked per submit: others take the generic kernel for
+                                  that submit).  16-byte loads, the last group masked by c. */
+  DFX_HEAD_ROW = 1,            /* head_row_kernel: a wave owns a row, four rows per workgroup (classifier: few long rows).
+                                  Class: any dtype, any k, either mode; src_ld * element size % 16 == 0; pointers 16-byte
+                                  aligned per submit.  Lanes scan 16-byte groups at a stride of 64 groups and meet through
+                                  wave shuffles on (key, index) pairs. */
+  DFX_HEAD_GENERIC = 2         /* one thread per row, a sequential scan, any alignment and src_ld, grid-stride.  It
+                                  defines the arithmetic of the other two. */
+};
+/* DFX_HEAD_AUTO_NOTE: auto takes DFX_HEAD_PIXEL everywhere in its class, except a softmax of 160-byte rows, which takes
+ * DFX_HEAD_ROW; outside the pixel class it takes DFX_HEAD_ROW in its class where a row has at least 160 bytes (src_ld *
+ * element size), and DFX_HEAD_GENERIC everywhere else.  On the 20 points of profiles/head/bench_head.txt (MI355X, buffers in
+ * rotation beyond the Infinity Cache, forced legs alternating): the pixel kernel beats the generic one on all 10 points of
+ * its class -- argmax and softmax u8 -> u8 at 1x65x65, 16x129x129 and 4x513x513 x 21/32, 8x512x1024x19/32 and
+ * 8x128x128x150/160 -- by 1.1x (4.4 against 5.0 us on the launch floor) to 6.5x, 35 us (2.4 TB/s of valid channels +
+ * idx) for the Cityscapes-size argmax.  The row kernel beats the generic one on all 11 points with rows of 160 bytes or
+ * more (150/160 u8: 1.5x and 2.6x; top-5 / softmax of {bs, 1000} s8 and f32 at bs 1, 8, 128: 18x to 90x, 4.7 to 11.4 us)
+ * and loses on the 7 points with 32-byte rows above the launch floor (7x to 39x: 62 of a wave's 64 lanes idle; at 4225
+ * rows, on the launch floor, it is 7 % and 13 % faster than the generic one and slower than the pixel one), so it is not on auto below 160 bytes; rows between 32 and 160
+ * bytes are unmeasured and stay generic.  At 8x128x128x150/160 the softmax takes
+ * 153 us on the row kernel against 181 (pixel) and 393 (generic), the argmax 12.5 us on the pixel kernel against 53.8 (row):
+ * hence the one exception. */
+typedef struct dfx_head_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_bytes;  /* what one submit must read and write: rows * c src elements + idx (TOPK; val, when
+                                  given, adds rows * k src elements) or + rows * c dst elements (SOFTMAX) */
+  char kernel_name[96];        /* mode, dtypes, k and path: "head_row<topk5,s8->s32>", "head_pixel<softmax,u8->u8>" */
+} dfx_head_info;
+typedef struct dfx_head dfx_head_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -1090,6 +1172,26 @@ int dfx_wsum_submit_host(dfx_wsum_t *h, const void *const *srcs_host, void *dst_
 int dfx_wsum_query(const dfx_wsum_t *h, dfx_wsum_info *info);
 int dfx_wsum_destroy(dfx_wsum_t *h);
 
+/* ---- net head: top-k / argmax and softmax (dfx_head_desc above).  The descriptor is validated before anything touches
+ *      a device: DFX_ERR_INVALID for a bad mode / dtype / force_path, rows < 1, c outside 1 .. 65535, src_ld < c, k
+ *      outside 1 .. 8 or above c, idx_ld < k, a u8 idx with c > 256, dst_ld < c, an out_scale that is not finite, more
+ *      than 2^40 elements; DFX_ERR_UNSUPPORTED for softmax of a 4-byte src and for a force_path outside that path's
+ *      class.  "No HIP device" is reported only for a valid descriptor.
+ *      set_table (SOFTMAX only; DFX_ERR_INVALID on a TOPK handle): 256 host uint32, copied.  DFX_ERR_INVALID for
+ *      E[0] == 0 (S could be 0) and for (uint64)c * max(E) > 2^32 - 1 (S could leave u32).  It may be called again (not
+ *      while a submit of the handle is in flight).
+ *      submit: asynchronous on `s`; ONE launch; it never writes to the handle: one handle serves several streams and host
+ *      threads at once.  TOPK: idx_or_dst is idx, val_or_null is val or NULL.  SOFTMAX: idx_or_dst is dst, val_or_null
+ *      must be NULL; DFX_ERR_STATE before set_table.  Pointers must be non-null (but val) and aligned to their element;
+ *      an output that overlaps src or the other output is DFX_ERR_INVALID and nothing is launched.  Pointers that are
+ *      not 16-byte aligned take the generic kernel for that submit.
+ *      Tuning switch: DFX_HEAD_GRID=n caps the grid of any path.  No CPU fallback. ---- */
+int dfx_head_create(const dfx_head_desc *desc, dfx_head_t **out);
+int dfx_head_set_table(dfx_head_t *h, const uint32_t *table256);
+int dfx_head_submit(dfx_head_t *h, const void *src_dev, void *idx_or_dst_dev, void *val_or_null_dev, dfx_stream_t s);
+int dfx_head_query(const dfx_head_t *h, dfx_head_info *info);
+int dfx_head_destroy(dfx_head_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -1177,6 +1279,8 @@ int dfx_debug_dwpw_requant(const dfx_dwpw_t *h, int32_t out[2]);
 int dfx_debug_resize_launches(int64_t out[2]);
 /* the same for dfx_wsum_submit: out[DFX_WSUM_VEC], out[DFX_WSUM_GENERIC] */
 int dfx_debug_wsum_launches(int64_t out[2]);
+/* the same for dfx_head_submit: out[DFX_HEAD_PIXEL], out[DFX_HEAD_ROW], out[DFX_HEAD_GENERIC] */
+int dfx_debug_head_launches(int64_t out[3]);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,8 @@ from .capi import (  # noqa: F401
     WSUM_AUTO, WSUM_VEC, WSUM_GENERIC, WsumDesc, WsumInfo, ScaledSum, wsum_launches,
     HEAD_TOPK, HEAD_SOFTMAX, HEAD_AUTO, HEAD_PIXEL, HEAD_ROW, HEAD_GENERIC, HeadDesc, HeadInfo, Head, TopK, Softmax,
     head_launches, softmax_table,
+    SELECT_ALL, SELECT_PEAK3, SELECT_AUTO, SELECT_HIST, SELECT_GENERIC, SELECT_MAX_K, SelectDesc, SelectInfo, SelectTopK,
+    select_launches,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

@@ -33,6 +33,9 @@ WSUM_AUTO, WSUM_VEC, WSUM_GENERIC = -1, 0, 1
 WSUM_MAX_INPUTS = 8
 HEAD_TOPK, HEAD_SOFTMAX = 0, 1
 HEAD_AUTO, HEAD_PIXEL, HEAD_ROW, HEAD_GENERIC = -1, 0, 1, 2
+SELECT_ALL, SELECT_PEAK3 = 0, 1
+SELECT_AUTO, SELECT_HIST, SELECT_GENERIC = -1, 0, 1
+SELECT_MAX_K, SELECT_MAX_GATHER = 4096, 4
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -205,6 +208,19 @@ class HeadDesc(ctypes.Structure):
 class HeadInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
                [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
+
+
+class SelectDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "h", "w", "c", "src_ld", "src_dt", "k", "idx_ld", "peak", "min_val",
+                                             "n_gather")] + \
+               [("row_bytes", ctypes.c_int32 * 4), ("pixel_stride_bytes", ctypes.c_int32 * 4), ("force_path", ctypes.c_int32)]
+
+
+class SelectInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "chunks", "chunk_pixels", "grid", "grid_image", "block", "block_image",
+                                             "lds_bytes", "launches", "device")] + \
+               [("scratch_bytes", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
 
 
 class DwPwDesc(ctypes.Structure):
@@ -397,6 +413,11 @@ def lib():
         "dfx_debug_resize_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
         "dfx_debug_wsum_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
         "dfx_debug_head_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_select_create": (i32, [ctypes.POINTER(SelectDesc), ctypes.POINTER(vp)]),
+        "dfx_select_submit": (i32, [vp, vp, vp, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), vp]),
+        "dfx_select_query": (i32, [vp, ctypes.POINTER(SelectInfo)]),
+        "dfx_select_destroy": (i32, [vp]),
+        "dfx_debug_select_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -434,6 +455,13 @@ def head_launches():
     v = (ctypes.c_int64 * 3)()
     _check(lib().dfx_debug_head_launches(v))
     return v[HEAD_PIXEL], v[HEAD_ROW], v[HEAD_GENERIC]
+
+
+def select_launches():
+    """(hist, generic): dfx_select_submit calls of this process that ran on each path (dfx_debug_select_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_select_launches(v))
+    return v[SELECT_HIST], v[SELECT_GENERIC]
 
 
 def softmax_table(scale, c):
@@ -1020,6 +1048,37 @@ class Softmax(Head):
         Head.__init__(self, rows, c, src_dtype, dst_dtype, mode=HEAD_SOFTMAX, **kw)
         if table is not None:
             self.set_table(table)
+
+
+class SelectTopK(_Handle):
+    """dfx_select_* handle: the k best elements of every image of an NHWC u8 / s8 score tensor {bs, h, w, src_ld} (c valid
+    channels), optionally only 3x3 local maxima (peak=SELECT_PEAK3) and only elements >= min_val, ordered by (value
+    descending, element index ascending); rows of up to four byte maps gathered behind it (include/dfx.h).  gather: a
+    (row_bytes, pixel_stride_bytes) pair per map."""
+
+    _OP, _INFO = "dfx_select", SelectInfo
+
+    def __init__(self, bs, h, w, c, src_dtype, k, src_ld=None, idx_ld=None, peak=SELECT_ALL, min_val=None, gather=(),
+                 force_path=SELECT_AUTO):
+        d = SelectDesc()
+        d.bs, d.h, d.w, d.c, d.k, d.peak, d.force_path = bs, h, w, c, k, peak, force_path
+        d.src_dt = src_dtype if isinstance(src_dtype, int) else _DT[np.dtype(src_dtype)]
+        d.src_ld = c if src_ld is None else src_ld
+        d.idx_ld = k if idx_ld is None else idx_ld
+        d.min_val = (-128 if d.src_dt == DFX_S8 else 0) if min_val is None else min_val
+        d.n_gather = len(gather)
+        for i, (rb, st) in enumerate(list(gather)[:4]):
+            d.row_bytes[i], d.pixel_stride_bytes[i] = rb, st
+        self.desc = d
+        self._create(d)
+
+    def submit(self, src_dev, idx_dev, count_dev, val_dev=None, gather_src=(), gather_dst=(), stream=None):
+        """asynchronous; torch CUDA tensors (or raw pointers); idx int32 {bs, idx_ld}, count int32 {bs}, val of src's dtype"""
+        gs = _ptr_array(gather_src, lambda t: _dev_ptr(t).value) if len(gather_src) else None
+        gd = _ptr_array(gather_dst, lambda t: _dev_ptr(t).value) if len(gather_dst) else None
+        _check(lib().dfx_select_submit(self._h, _dev_ptr(src_dev), _dev_ptr(idx_dev),
+                                       None if val_dev is None else _dev_ptr(val_dev), _dev_ptr(count_dev), gs, gd,
+                                       _stream_ptr(stream)))
 
 
 class DwPwConv(_Handle):

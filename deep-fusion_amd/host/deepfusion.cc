@@ -2621,6 +2621,95 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- image-wide top-K with peak filter (dfx_select_*): the k best elements of every image of an nhwc score tensor,
+// optionally only 3x3 local maxima and only elements >= min_val, with whole pixel rows of further nhwc tensors gathered
+// behind it.  src and the gather sources are registered as reads, idx, count, val and the gather destinations as writes
+// (op_state).  One handle on one device: DEEPFUSION_DEVICES does not shard this op (its results are per image, but a
+// detector's batch is small). ----
+class op_select : public op {
+public:
+  op_select(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &idx, memory *val, std::unique_ptr<memory> &count, int k,
+            bool peak3, int min_val, int c_valid, const std::vector<memory *> &gsrc, const std::vector<memory *> &gdst)
+      : src_(src.get()), idx_(idx.get()), val_(val), count_(count.get()), gsrc_(gsrc), gdst_(gdst), h_(nullptr) {
+    using fmt = memory::format;
+    using dt = memory::dtype;
+    if (!src_ || !idx_ || !count_) error_and_exit("Init Select op failed! (null tensor)");
+    if (src_->dim_format() != fmt::nhwc) error_and_exit("Init Select op failed! (format)");
+    auto i = src_->std_dims(), o = idx_->std_dims();
+    if (idx_->data_type() != dt::s32 || o[0] != i[0] || o[1] != k || o[2] != 1 || o[3] != 1)
+      error_and_exit("Init Select op failed! (idx must be s32 {bs, k, 1, 1})");
+    if (val_ && (val_->std_dims() != o || val_->data_type() != src_->data_type()))
+      error_and_exit("Init Select op failed! (val must have idx's dims and src's data type)");
+    if (count_->data_type() != dt::s32 || count_->size() != (size_t)i[0]) error_and_exit("Init Select op failed! (count must be s32 {bs})");
+    if (gsrc_.size() != gdst_.size() || gsrc_.size() > (size_t)DFX_SELECT_MAX_GATHER) error_and_exit("Init Select op failed! (gather lists)");
+    dfx_select_desc d;
+    memset(&d, 0, sizeof(d));
+    d.bs = i[0]; d.h = i[2]; d.w = i[3];
+    d.c = c_valid > 0 ? c_valid : i[1];
+    d.src_ld = i[1];
+    d.src_dt = to_dfx_dtype(src_->data_type());
+    d.k = k;
+    d.idx_ld = k;
+    d.peak = peak3 ? DFX_SELECT_PEAK3 : DFX_SELECT_ALL;
+    d.min_val = min_val == select_all_values ? (src_->data_type() == dt::s8 ? -128 : 0) : min_val;
+    d.n_gather = (int)gsrc_.size();
+    for (size_t g = 0; g < gsrc_.size(); ++g) {
+      memory *s = gsrc_[g], *t = gdst_[g];
+      if (!s || !t || s->dim_format() != fmt::nhwc || t->dim_format() != fmt::nhwc) error_and_exit("Init Select op failed! (gather tensor)");
+      auto sd = s->std_dims(), td = t->std_dims();
+      if (sd[0] != i[0] || sd[2] != i[2] || sd[3] != i[3]) error_and_exit("Init Select op failed! (a gather source must share bs, h, w with src)");
+      if (t->data_type() != s->data_type() || td[0] != i[0] || td[1] != sd[1] || td[2] != k || td[3] != 1)
+        error_and_exit("Init Select op failed! (a gather destination must be {bs, C, k, 1} of its source's type)");
+      d.row_bytes[g] = d.pixel_stride_bytes[g] = (int)(sd[1] * dtype_size(s->data_type()));
+    }
+    d.force_path = -1;
+    if (dfx_select_create(&d, &h_) != DFX_OK) error_and_exit("Init Select op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_select() override {
+    st_.retire(*idx_);
+    dfx_select_destroy(h_);
+  }
+
+  void submit() override {
+    run(true);
+    st_.fetch_out(*idx_);
+    st_.fetch_out(*count_);
+    if (val_) st_.fetch_out(*val_);
+    for (memory *t : gdst_) st_.fetch_out(*t);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*idx_);
+  }
+  void submit_async() override { run(false); }
+  void wait() override {
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*idx_);
+  }
+
+protected:
+  void infer() override { run(true); }
+  void run(bool sync_host) {
+    const void *in = st_.sync_in(*src_, sync_host);
+    const void *gs[DFX_SELECT_MAX_GATHER] = {nullptr, nullptr, nullptr, nullptr};
+    void *gd[DFX_SELECT_MAX_GATHER] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t g = 0; g < gsrc_.size(); ++g) gs[g] = st_.sync_in(*gsrc_[g], sync_host);
+    void *o = st_.device_out(*idx_);
+    void *c = st_.device_out(*count_);
+    void *v = val_ ? st_.device_out(*val_) : nullptr;
+    for (size_t g = 0; g < gdst_.size(); ++g) gd[g] = st_.device_out(*gdst_[g]);
+    st_.profile_begin();
+    check_dfx(dfx_select_submit(h_, in, o, v, c, gs, gd, st_.stream), "select submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "select"; }
+
+private:
+  memory *src_, *idx_, *val_, *count_;
+  std::vector<memory *> gsrc_, gdst_;
+  dfx_select_t *h_;
+  detail::op_state st_;
+};
+
 // ---- squeeze-and-excitation (dfx_se_*) and, with no weights, the global average pooling it starts with.  The two weight
 // tensors are plain oihw {cr, c, 1, 1} and {c, cr, 1, 1}; dst may be src.  Weight hashing and batch sharding are
 // op_depthwise_conv's: the op is per image, so shards are independent. ----
@@ -3071,6 +3160,12 @@ std::unique_ptr<op> top_k(const std::unique_ptr<memory> &src, std::unique_ptr<me
 std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &dst,
                             float out_scale, int c_valid) {
   return std::unique_ptr<op>(new op_head(src, dst, nullptr, DFX_HEAD_SOFTMAX, 0, c_valid, &table, out_scale));
+}
+
+std::unique_ptr<op> select_top_k(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, memory *dst_val,
+                                 std::unique_ptr<memory> &dst_count, int k, bool peak3, int min_val, int c_valid,
+                                 const std::vector<memory *> &gather_src, const std::vector<memory *> &gather_dst) {
+  return std::unique_ptr<op>(new op_select(src, dst_idx, dst_val, dst_count, k, peak3, min_val, c_valid, gather_src, gather_dst));
 }
 
 std::unique_ptr<op> global_avg_pool(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst) {

@@ -484,4 +484,43 @@ int dfx_head_submit(dfx_head_t *hv, const void *src, void *idx_or_dst, void *val
 }
 int dfx_head_destroy(dfx_head_t *h) { return destroy_handle(h); }
 
+// ---- image-wide top-K: reads src and the gather sources (`src`); writes idx (`dst`), val when given (`lat`), count and the
+// gather destinations (this op borrows no host tensors: `wei` holds the bytes of count and of each gather destination) ----
+int dfx_select_create(const dfx_select_desc *d, dfx_select_t **out) {
+  if (!d || !out || d->bs < 1 || d->c < 1 || d->src_ld < d->c || d->k < 1 || d->idx_ld < d->k || d->n_gather < 0 ||
+      d->n_gather > DFX_SELECT_MAX_GATHER)
+    return fail(DFX_ERR_INVALID, "bad select descriptor");
+  handle *h = new_handle("select");
+  const size_t px = (size_t)d->bs * d->h * d->w, rows = ((size_t)d->bs - 1) * d->idx_ld + d->k;
+  h->src.push_back((px - 1) * d->src_ld + d->c);
+  h->dst = rows * 4;
+  h->lat = rows;
+  h->wei.push_back((size_t)d->bs * 4);
+  for (int i = 0; i < d->n_gather; ++i) {
+    h->src.push_back((px - 1) * d->pixel_stride_bytes[i] + d->row_bytes[i]);
+    h->wei.push_back((size_t)d->bs * d->k * d->row_bytes[i]);
+  }
+  *out = reinterpret_cast<dfx_select_t *>(h);
+  return DFX_OK;
+}
+int dfx_select_submit(dfx_select_t *hv, const void *src, void *idx, void *val_or_null, void *count, const void *const *gsrc,
+                      void *const *gdst, dfx_stream_t s) {
+  handle *h = reinterpret_cast<handle *>(hv);
+  if (!h) return fail(DFX_ERR_INVALID, "null handle");
+  if (!stream_ok(s, "dfx_select_submit")) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_select_submit", {}};
+  add_range(r, src, h->src[0], false);
+  add_range(r, idx, h->dst, true);
+  if (val_or_null) add_range(r, val_or_null, h->lat, true);
+  add_range(r, count, h->wei[0], true);
+  for (size_t i = 1; i < h->src.size(); ++i) {
+    add_range(r, gsrc[i - 1], h->src[i], false);
+    add_range(r, gdst[i - 1], h->wei[i], true);
+  }
+  r.ranges.push_back({h->packed, 0, 1, false});
+  g_trace.push_back(r);
+  return DFX_OK;
+}
+int dfx_select_destroy(dfx_select_t *h) { return destroy_handle(h); }
+
 }  // extern "C"

@@ -441,6 +441,25 @@ std::unique_ptr<op> top_k(const std::unique_ptr<memory> &src, std::unique_ptr<me
 std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array<uint32_t, 256> &table,
                             std::unique_ptr<memory> &dst, float out_scale = 255.f, int c_valid = 0);
 
+// ---- extension: image-wide top-K with peak filter (dfx_select_* in dfx.h): what a detector does behind its last conv,
+// without leaving the device.  src: an nhwc score tensor {bs, C, h, w} of u8 / s8 (a conv()'s heat map); the first c_valid
+// channels of a pixel take part (0: all).  Per image, the k (1 .. 4096) best elements that are >= min_val and, with peak3,
+// >= their 3x3 neighbours of the same channel inside the image (CenterNet's max_pool == heat), ordered by value descending,
+// element index e = (y * w + x) * c_valid + channel ascending:
+//   dst_idx    s32 {bs, k, 1, 1}: the e's, -1 from the image's count on
+//   dst_val    may be null; src's dtype, idx's dims: the elements themselves, 0 from the count on
+//   dst_count  s32 {bs, 1, 1, 1}: min(k, candidates)
+//   gather_src / gather_dst   up to four pairs: source nhwc {bs, Ci, h, w} of any dtype (wh / offset maps, box deltas),
+//              destination nhwc {bs, Ci, k, 1} of the same dtype: the whole pixel row of every selected element, zero rows
+//              from the count on
+// Bit-exact and the same on every kernel path.  submit / submit_async / wait are scaled_sum()'s; DEEPFUSION_DEVICES does
+// not shard this op.  s32 / f32 scores, k > 4096, NMS and box decoding are not built. ----
+enum { select_all_values = -2147483647 - 1 };  // min_val: the dtype's minimum, every element passes
+std::unique_ptr<op> select_top_k(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, memory *dst_val /* may be null */,
+                                 std::unique_ptr<memory> &dst_count, int k, bool peak3 = false, int min_val = select_all_values,
+                                 int c_valid = 0, const std::vector<memory *> &gather_src = std::vector<memory *>(),
+                                 const std::vector<memory *> &gather_dst = std::vector<memory *>());
+
 // ---- extension: depthwise conv + pointwise conv, the depthwise-separable block (dfx_dwpw_* in dfx.h).  Stage 0 is
 // depthwise_conv() with a u8 result (ReLU implied), stage 1 a 1x1 stride-1 unpadded conv() on that tensor; dst holds,
 // bit for bit, what the two ops give one after the other.  wei_dw: plain oihw s8 {c, 1, kh, kw}; wei_pw: OIhw4i16o4i

@@ -718,8 +718,9 @@ typedef struct dfx_wsum dfx_wsum_t;
  *        dst rows are dst_ld >= c elements apart; elements c .. dst_ld-1 are NOT written.
  *        THE TABLE.  E[d] = floor(exp(-d * s) * floor((2^32 - 1) / c)) for a logit step s (Python: dfa.softmax_table(s, c))
  *        keeps S within u32 for every row and is within 1e-6 absolute of a float64 softmax for c up to 65535.
- *      Not built: the argmax fused into dfx_resize's store, softmax of s32 / f32 logits, k > 8, NCHW, softmax + top-k in
- *      one launch.  Parity unpinned: the reference has no such op. ---- */
+ *      Not built: the argmax fused into dfx_resize's store, softmax of s32 / f32 logits, NCHW, softmax + top-k in one
+ *      launch.  k > 8 over the channels of one row is dfx_select's (h = w = 1, k up to 4096, 1-byte scores), as is a
+ *      selection that crosses pixels.  Parity unpinned: the reference has no such op. ---- */
 enum { DFX_HEAD_TOPK = 0, DFX_HEAD_SOFTMAX = 1 };  /* dfx_head_desc.mode */
 enum { DFX_HEAD_MAX_K = 8, DFX_HEAD_MAX_C = 65535 };
 typedef struct dfx_head_desc {
@@ -769,6 +770,89 @@ typedef struct dfx_head_info {
   char kernel_name[96];        /* mode, dtypes, k and path: "head_row<topk5,s8->s32>", "head_pixel<softmax,u8->u8>" */
 } dfx_head_info;
 typedef struct dfx_head dfx_head_t;
+
+/* ---- image-wide top-K with peak filter: what every detector does behind its last conv -- CenterNet's 100 best of a
+ *      128 x 128 x 80 heat map that are 3x3 local maxima, the 1000 best anchors of a RetinaNet / SSD level above a score
+ *      threshold, an RPN's 2000 pre-NMS proposals -- on the device, with the rows of the regression maps (wh / offset, box
+ *      deltas) gathered behind it.  dfx_head selects over the channels of ONE pixel; this op selects over a whole image.
+ *        src    NHWC {bs, h, w, src_ld}, u8 or s8; c valid channels, 1 <= c <= src_ld <= 65535.  Channels c .. src_ld-1
+ *               NEVER take part, whatever they hold.  A {bs, N} row matrix is h = w = 1, c = N.
+ *        e      the element index inside an image, over the VALID channels: e = (y * w + x) * c + k, so pixel = e / c and
+ *               class = e % c.  h * w * c <= 2^31 - 1; bs * h * w * src_ld <= 2^40.
+ *        CANDIDATES.  Element (y, x, k) is a candidate iff (1) src >= min_val (the dtype's minimum: all) and (2) with
+ *               peak = DFX_SELECT_PEAK3 it is >= every element of the same channel and image at (y + dy, x + dx), dy, dx in
+ *               {-1, 0, 1}, that lies inside the image -- exactly "dfx_pool MAX 3x3 / 1, pad 1 equals src"; equal neighbours
+ *               are both candidates.  DFX_SELECT_ALL skips (2).
+ *        ORDER  dfx_head's: value descending, e ascending.  All (value, e) pairs are distinct, so the result does not
+ *               depend on how the work is cut or scheduled: every kernel gives the same bits.
+ *        RESULT for image r: count[r] = min(k, candidates); idx[r][0 .. count-1] the e's of the best candidates in that
+ *               order (s32 {bs, k}, rows idx_ld >= k apart); the same entries of the optional val the elements themselves
+ *               (src's dtype, the same leading dimension).  Entries count .. k-1 are written too: idx -1, val 0; elements
+ *               k .. idx_ld-1 are not written.  count is s32 {bs}, always written.  k may exceed h * w * c.
+ *        GATHER n_gather in 0 .. 4 byte maps that share bs, h, w with src: source i has pixel_stride_bytes[i] bytes per
+ *               pixel, of which the first row_bytes[i] (1 .. 1024) are copied verbatim, for entry j < count[r] with pixel
+ *               p = idx / c, from offset (r * h * w + p) * pixel_stride_bytes[i] into out_i[r][j]; out_i is {bs, k,
+ *               row_bytes[i]}, dense; rows j >= count[r] are zero-filled.  Bytes only: dtypes do not matter.
+ *      The algorithm is exact for 1-byte scores: a histogram of the 256 keys, the threshold key, compaction, a sort of at
+ *      most 4096 pairs.  Not built: s32 / f32 scores (DFX_ERR_UNSUPPORTED: they need a multi-pass radix), k > 4096, NMS and
+ *      box decoding, windows other than 3x3, NCHW, the peak test fused into the producing conv's epilogue, a sigmoid
+ *      table in front (dfx_wsum with a table today).  Parity unpinned: the reference has no such op. ---- */
+enum { DFX_SELECT_ALL = 0, DFX_SELECT_PEAK3 = 1 };  /* dfx_select_desc.peak */
+enum { DFX_SELECT_MAX_K = 4096, DFX_SELECT_MAX_GATHER = 4, DFX_SELECT_MAX_ROW_BYTES = 1024 };
+typedef struct dfx_select_desc {
+  int32_t bs, h, w;
+  int32_t c;                   /* valid channels, 1 .. 65535 */
+  int32_t src_ld;              /* elements between pixels of src, c .. 65535 */
+  int32_t src_dt;              /* DFX_U8 | DFX_S8 (DFX_S32 / DFX_F32: DFX_ERR_UNSUPPORTED) */
+  int32_t k;                   /* 1 .. DFX_SELECT_MAX_K */
+  int32_t idx_ld;              /* elements between rows of idx (and of val), >= k */
+  int32_t peak;                /* DFX_SELECT_ALL | DFX_SELECT_PEAK3 */
+  int32_t min_val;             /* in src's dtype range; the dtype's minimum admits every element */
+  int32_t n_gather;            /* 0 .. DFX_SELECT_MAX_GATHER */
+  int32_t row_bytes[4];        /* 1 .. DFX_SELECT_MAX_ROW_BYTES */
+  int32_t pixel_stride_bytes[4]; /* row_bytes[i] .. 65536 */
+  int32_t force_path;          /* -1 auto, else DFX_SELECT_HIST | DFX_SELECT_GENERIC */
+} dfx_select_desc;
+enum {  /* dfx_select_info.path */
+  DFX_SELECT_HIST = 0,         /* four launches (select.cuh).  Class: src_ld % 16 == 0; src and every output 16-byte
+                                  aligned (checked per submit: others take the generic kernel for that submit).  An image
+                                  is cut into chunks of consecutive pixels.  A: a workgroup per (image, chunk), 16-byte
+                                  loads, the candidate test on 16 channels at once, per-wave LDS histograms, plain stores
+                                  into a slab [bs][chunks][256].  B: a workgroup per image finds the threshold key and every
+                                  chunk's offsets and tie-bin quota from the slab alone.  C: the grid of A writes (key, e)
+                                  pairs into cand[bs][k]; the tie bin goes to the lowest e's through an ordered rank.  D: a
+                                  workgroup per image sorts at most 4096 pairs in LDS, stores idx / val / fill / count and
+                                  gathers.  No flags, spins, arrival counters or global atomics. */
+  DFX_SELECT_GENERIC = 1       /* one workgroup per image does all of it, byte loads, any alignment and src_ld.  It
+                                  defines the bits. */
+};
+/* DFX_SELECT_AUTO_NOTE: auto takes DFX_SELECT_HIST in its class from images of 4096 bytes (h * w * src_ld) on, and
+ * DFX_SELECT_GENERIC below that and outside the class.  On the 15 points of profiles/select/bench_select.txt (MI355X,
+ * buffers in rotation beyond the Infinity Cache, forced legs alternating) the histogram path beats the generic kernel on all
+ * 13 points whose image has more than one pixel: CenterNet 128x128x80 peak3 k 100 at bs 1 / 8 / 32 in 60 / 73 / 150 us
+ * against 7.9 to 8.4 ms; a RetinaNet level 100x136x720 min 128 k 1000 at bs 1 / 8 in 99 / 117 us against 19 ms; RPN
+ * 200x304x3/16 k 2000 in 62 against 384 us; 64-channel peak3 maps from 64x64 down to 8x8 (4096 bytes: 25.9 against 32.3 us
+ * at bs 1, 28.6 against 34.8 at bs 8).  It loses on both classifier rows {bs, 1000/1008} k 100 (25.7 against 17.0 us at bs 1,
+ * 30.3 against 18.1 at bs 128): four launches against one on a kilobyte of work.  Images between 1008 and 4096 bytes are
+ * unmeasured and stay generic.  Nothing is near the floor of reading src once: the best point, RetinaNet bs 8, takes 8.8
+ * times as long (DESIGN.md section 4.18 says what bounds it). */
+typedef struct dfx_select_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t chunks;              /* chunks per image (1 on the generic path) */
+  int32_t chunk_pixels;        /* pixels per chunk (h * w on the generic path) */
+  int32_t grid;                /* workgroups of launches A and C (generic: of the one launch) */
+  int32_t grid_image;          /* workgroups of launches B and D: one per image */
+  int32_t block;               /* lanes of launches A and C (generic: of the one launch) */
+  int32_t block_image;         /* lanes of launches B and D */
+  int32_t lds_bytes;           /* the largest of the path's kernels */
+  int32_t launches;            /* per submit */
+  int32_t device;
+  uint64_t scratch_bytes;      /* slab + plan + cand, owned by the handle (0 on the generic path) */
+  uint64_t algorithmic_bytes;  /* bs * h * w * c src + idx + count + the gather rows read and written (val, when given,
+                                  adds bs * k) */
+  char kernel_name[96];        /* "select_hist<peak3,u8,k100>", "select_generic<all,s8,k1000>" */
+} dfx_select_info;
+typedef struct dfx_select dfx_select_t;
 
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
@@ -1192,6 +1276,29 @@ int dfx_head_submit(dfx_head_t *h, const void *src_dev, void *idx_or_dst_dev, vo
 int dfx_head_query(const dfx_head_t *h, dfx_head_info *info);
 int dfx_head_destroy(dfx_head_t *h);
 
+/* ---- image-wide top-K with peak filter (dfx_select_desc above).  The descriptor is validated before anything touches
+ *      a device: DFX_ERR_INVALID for sizes outside the limits stated at the descriptor, a bad dtype / peak mode /
+ *      force_path, idx_ld < k, a min_val outside src's dtype, a bad gather entry; DFX_ERR_UNSUPPORTED for an s32 / f32 src
+ *      and for force_path = DFX_SELECT_HIST with src_ld % 16 != 0.  "No HIP device" is reported only for a valid
+ *      descriptor.
+ *      submit: asynchronous on `s`.  val may be NULL; gather_src / gather_dst are arrays of n_gather device pointers (may
+ *      be NULL when n_gather is 0).  DFX_ERR_INVALID, with nothing launched and every output untouched, for a null
+ *      pointer, an idx or count that is not 4-byte aligned, and any output (idx, val, count, a gather destination) that
+ *      overlaps src, a gather source or another output.  Pointers (src, idx, val, count, gather destinations) that are
+ *      not 16-byte aligned take the generic kernel for that submit.
+ *      Histogram path: the handle owns the scratch its four launches meet in (slab, plan, cand), so its submits are
+ *      SERIALISED on the device, as dfx_se's: submits on one stream are ordered by the stream; once the handle has seen a
+ *      second stream every submit records an event behind its last launch and a submit on another stream than the
+ *      previous one's first waits for it, on the device.  The host never blocks, and submit does not write to the handle
+ *      otherwise.  Generic path: one launch with its own arguments; submits are independent.
+ *      Tuning switch: DFX_SELECT_CHUNK=n sets the pixels per chunk (raised until an image has at most 1024 chunks).
+ *      No CPU fallback.  Auto: DFX_SELECT_AUTO_NOTE above. ---- */
+int dfx_select_create(const dfx_select_desc *desc, dfx_select_t **out);
+int dfx_select_submit(dfx_select_t *h, const void *src_dev, void *idx_dev, void *val_or_null_dev, void *count_dev,
+                      const void *const *gather_src_dev, void *const *gather_dst_dev, dfx_stream_t s);
+int dfx_select_query(const dfx_select_t *h, dfx_select_info *info);
+int dfx_select_destroy(dfx_select_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -1281,6 +1388,9 @@ int dfx_debug_resize_launches(int64_t out[2]);
 int dfx_debug_wsum_launches(int64_t out[2]);
 /* the same for dfx_head_submit: out[DFX_HEAD_PIXEL], out[DFX_HEAD_ROW], out[DFX_HEAD_GENERIC] */
 int dfx_debug_head_launches(int64_t out[3]);
+/* the same for dfx_select_submit: out[DFX_SELECT_HIST], out[DFX_SELECT_GENERIC] (a submit counts once, whatever the
+ * number of its launches) */
+int dfx_debug_select_launches(int64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,7 @@ from .capi import (  # noqa: F401
     head_launches, softmax_table,
     SELECT_ALL, SELECT_PEAK3, SELECT_AUTO, SELECT_HIST, SELECT_GENERIC, SELECT_MAX_K, SelectDesc, SelectInfo, SelectTopK,
     select_launches,
+    NMS_BOXES, NMS_DECODE, NMS_AUTO, NMS_MASK, NMS_GENERIC, NMS_MAX_N, NmsDesc, NmsIo, NmsInfo, BoxNms, nms_launches, box_tables,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

@@ -36,6 +36,9 @@ HEAD_AUTO, HEAD_PIXEL, HEAD_ROW, HEAD_GENERIC = -1, 0, 1, 2
 SELECT_ALL, SELECT_PEAK3 = 0, 1
 SELECT_AUTO, SELECT_HIST, SELECT_GENERIC = -1, 0, 1
 SELECT_MAX_K, SELECT_MAX_GATHER = 4096, 4
+NMS_BOXES, NMS_DECODE = 0, 1
+NMS_AUTO, NMS_MASK, NMS_GENERIC = -1, 0, 1
+NMS_MAX_N = 4096
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -219,6 +222,24 @@ class SelectDesc(ctypes.Structure):
 class SelectInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "chunks", "chunk_pixels", "grid", "grid_image", "block", "block_image",
                                              "lds_bytes", "launches", "device")] + \
+               [("scratch_bytes", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
+class NmsDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "n", "max_out", "keep_ld", "mode", "per_class", "classes", "anchors_per_pixel",
+                                             "n_anchors", "row_bytes", "idx_ld")] + \
+               [("iou_thr", ctypes.c_float), ("clip_w", ctypes.c_float), ("clip_h", ctypes.c_float), ("force_path", ctypes.c_int32)]
+
+
+class NmsIo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("boxes", "idx", "deltas", "anchors", "tab_c", "tab_s", "count_in", "keep", "count",
+                                              "boxes_out")]
+
+
+class NmsInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "tiles", "grid_prep", "grid_mask", "grid_scan", "block_prep", "block_mask",
+                                             "block_scan", "lds_bytes", "launches", "device")] + \
                [("scratch_bytes", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
                 ("kernel_name", ctypes.c_char * 96)]
 
@@ -418,6 +439,11 @@ def lib():
         "dfx_select_query": (i32, [vp, ctypes.POINTER(SelectInfo)]),
         "dfx_select_destroy": (i32, [vp]),
         "dfx_debug_select_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_nms_create": (i32, [ctypes.POINTER(NmsDesc), ctypes.POINTER(vp)]),
+        "dfx_nms_submit": (i32, [vp, ctypes.POINTER(NmsIo), vp]),
+        "dfx_nms_query": (i32, [vp, ctypes.POINTER(NmsInfo)]),
+        "dfx_nms_destroy": (i32, [vp]),
+        "dfx_debug_nms_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -462,6 +488,23 @@ def select_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_select_launches(v))
     return v[SELECT_HIST], v[SELECT_GENERIC]
+
+
+def nms_launches():
+    """(mask, generic): dfx_nms_submit calls of this process that ran on each path (dfx_debug_nms_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_nms_launches(v))
+    return v[NMS_MASK], v[NMS_GENERIC]
+
+
+def box_tables(scale, zero_point, weight_xy, weight_wh, clip=float(np.log(1000.0 / 16)), dtype=np.uint8):
+    """The two 256-entry f32 tables of dfx_nms's DECODE mode for 1-byte deltas of `dtype` (uint8 or int8) with quantisation
+    (q - zero_point) * scale, indexed by the RAW byte: tab_c = d / weight_xy (dx, dy) and tab_s = exp(min(d / weight_wh,
+    clip)) (dw, dh) -- torchvision's BoxCoder with its bbox_xform_clip.  Computed in float64, rounded once to f32."""
+    raw = np.arange(256, dtype=np.uint8)
+    q = raw.view(np.int8).astype(np.float64) if np.dtype(dtype) == np.int8 else raw.astype(np.float64)
+    d = (q - float(zero_point)) * float(scale)
+    return (d / float(weight_xy)).astype(np.float32), np.exp(np.minimum(d / float(weight_wh), float(clip))).astype(np.float32)
 
 
 def softmax_table(scale, c):
@@ -1079,6 +1122,37 @@ class SelectTopK(_Handle):
         _check(lib().dfx_select_submit(self._h, _dev_ptr(src_dev), _dev_ptr(idx_dev),
                                        None if val_dev is None else _dev_ptr(val_dev), _dev_ptr(count_dev), gs, gd,
                                        _stream_ptr(stream)))
+
+
+class BoxNms(_Handle):
+    """dfx_nms_* handle: greedy NMS over n <= 4096 candidates per image in priority order (what SelectTopK emits), on boxes
+    (mode NMS_BOXES) or with the boxes decoded from anchors and 1-byte deltas through two tables (NMS_DECODE, box_tables());
+    per-class or class-agnostic; at most max_out survivors (include/dfx.h)."""
+
+    _OP, _INFO = "dfx_nms", NmsInfo
+
+    def __init__(self, bs, n, max_out, iou_thr, mode=NMS_BOXES, per_class=False, classes=1, anchors_per_pixel=1, n_anchors=None,
+                 row_bytes=None, idx_ld=None, keep_ld=None, clip=None, force_path=NMS_AUTO):
+        d = NmsDesc()
+        d.bs, d.n, d.max_out, d.mode, d.per_class, d.classes, d.force_path = bs, n, max_out, mode, int(per_class), classes, force_path
+        d.anchors_per_pixel = anchors_per_pixel
+        d.n_anchors = (2 ** 31 - 1) // max(1, classes) if n_anchors is None else n_anchors
+        d.row_bytes = 4 * anchors_per_pixel if row_bytes is None else row_bytes
+        d.idx_ld = n if idx_ld is None else idx_ld
+        d.keep_ld = max_out if keep_ld is None else keep_ld
+        d.iou_thr = iou_thr
+        d.clip_w, d.clip_h = (0.0, 0.0) if clip is None else clip
+        self.desc = d
+        self._create(d)
+
+    def submit(self, keep_dev, count_dev, boxes=None, idx=None, deltas=None, anchors=None, tab_c=None, tab_s=None, count_in=None,
+               boxes_out=None, stream=None):
+        """asynchronous; torch CUDA tensors (or raw pointers); keep int32 {bs, keep_ld}, count int32 {bs}"""
+        io = NmsIo()
+        for name, t in (("boxes", boxes), ("idx", idx), ("deltas", deltas), ("anchors", anchors), ("tab_c", tab_c), ("tab_s", tab_s),
+                        ("count_in", count_in), ("keep", keep_dev), ("count", count_dev), ("boxes_out", boxes_out)):
+            setattr(io, name, None if t is None else _dev_ptr(t).value)
+        _check(lib().dfx_nms_submit(self._h, ctypes.byref(io), _stream_ptr(stream)))
 
 
 class DwPwConv(_Handle):

@@ -2710,6 +2710,114 @@ private:
   detail::op_state st_;
 };
 
+// ---- box decode + greedy NMS (dfx_nms_*): what a detector does behind select_top_k().  boxes (or idx, deltas and anchors),
+// the two tables and count_in are registered as reads, keep, count and boxes_out as writes (op_state).  The tables are two
+// small tensors of the op's own.  One handle on one device: DEEPFUSION_DEVICES does not shard this op, as it does not
+// shard select_top_k(). ----
+class op_nms : public op {
+public:
+  op_nms(memory *boxes, memory *idx, memory *deltas, memory *anchors, const std::array<float, 256> *tab_c, const std::array<float, 256> *tab_s,
+         memory *count_in, memory *keep, memory *count, memory *boxes_out, float iou_thr, int classes, bool per_class, int apx, float clip_w,
+         float clip_h)
+      : boxes_(boxes), idx_(idx), deltas_(deltas), anchors_(anchors), count_in_(count_in), keep_(keep), count_(count), boxes_out_(boxes_out),
+        h_(nullptr) {
+    using fmt = memory::format;
+    using dt = memory::dtype;
+    const bool decode = boxes_ == nullptr;
+    if (!keep_ || !count_ || (decode && (!idx_ || !deltas_ || !anchors_))) error_and_exit("Init Nms op failed! (null tensor)");
+    if (!decode && per_class && !idx_) error_and_exit("Init Nms op failed! (per-class NMS on boxes needs idx)");
+    auto o = keep_->std_dims();
+    const int bs = o[0], max_out = o[1];
+    if (keep_->data_type() != dt::s32 || o[2] != 1 || o[3] != 1) error_and_exit("Init Nms op failed! (keep must be s32 {bs, max_out, 1, 1})");
+    if (count_->data_type() != dt::s32 || count_->size() != (size_t)bs) error_and_exit("Init Nms op failed! (count must be s32 {bs})");
+    if (count_in_ && (count_in_->data_type() != dt::s32 || count_in_->size() != (size_t)bs)) error_and_exit("Init Nms op failed! (count_in must be s32 {bs})");
+    int n = 0;
+    dfx_nms_desc d;
+    memset(&d, 0, sizeof(d));
+    if (decode) {
+      auto i = idx_->std_dims(), q = deltas_->std_dims(), a = anchors_->std_dims();
+      n = i[1];
+      if (idx_->data_type() != dt::s32 || i[0] != bs || i[2] != 1 || i[3] != 1) error_and_exit("Init Nms op failed! (idx must be s32 {bs, n, 1, 1})");
+      if (deltas_->dim_format() != fmt::nhwc || dtype_size(deltas_->data_type()) != 1 || q[0] != bs || q[2] != n || q[3] != 1)
+        error_and_exit("Init Nms op failed! (deltas must be a 1-byte nhwc tensor {bs, C, n, 1})");
+      if (anchors_->dim_format() != fmt::nhwc || anchors_->data_type() != dt::f32 || a[1] != 4 || a[2] != 1 || a[3] != 1)
+        error_and_exit("Init Nms op failed! (anchors must be f32 nhwc {n_anchors, 4, 1, 1})");
+      d.row_bytes = q[1];
+      d.n_anchors = a[0];
+      tab_c_.reset(new memory(memory::nchw_dims{1, 256, 1, 1}, fmt::nhwc, dt::f32));
+      tab_s_.reset(new memory(memory::nchw_dims{1, 256, 1, 1}, fmt::nhwc, dt::f32));
+      memcpy(tab_c_->data(), tab_c->data(), 1024);
+      memcpy(tab_s_->data(), tab_s->data(), 1024);
+    } else {
+      auto b = boxes_->std_dims();
+      n = b[2];
+      if (boxes_->dim_format() != fmt::nhwc || boxes_->data_type() != dt::f32 || b[0] != bs || b[1] != 4 || b[3] != 1)
+        error_and_exit("Init Nms op failed! (boxes must be f32 nhwc {bs, 4, n, 1})");
+      if (idx_ && (idx_->data_type() != dt::s32 || idx_->std_dims() != memory::nchw_dims{bs, n, 1, 1}))
+        error_and_exit("Init Nms op failed! (idx must be s32 {bs, n, 1, 1})");
+      d.n_anchors = classes > 0 ? 2147483647 / classes : 1;
+    }
+    if (boxes_out_) {
+      auto b = boxes_out_->std_dims();
+      if (boxes_out_->dim_format() != fmt::nhwc || boxes_out_->data_type() != dt::f32 || b[0] != bs || b[1] != 4 || b[2] != max_out || b[3] != 1)
+        error_and_exit("Init Nms op failed! (boxes_out must be f32 nhwc {bs, 4, max_out, 1})");
+    }
+    d.bs = bs; d.n = n; d.max_out = max_out; d.keep_ld = max_out;
+    d.mode = decode ? DFX_NMS_DECODE : DFX_NMS_BOXES;
+    d.per_class = per_class ? 1 : 0;
+    d.classes = classes; d.anchors_per_pixel = apx; d.idx_ld = n;
+    d.iou_thr = iou_thr; d.clip_w = clip_w; d.clip_h = clip_h;
+    d.force_path = -1;
+    if (dfx_nms_create(&d, &h_) != DFX_OK) error_and_exit("Init Nms op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_nms() override {
+    st_.retire(*keep_);
+    dfx_nms_destroy(h_);
+  }
+
+  void submit() override {
+    run(true);
+    st_.fetch_out(*keep_);
+    st_.fetch_out(*count_);
+    if (boxes_out_) st_.fetch_out(*boxes_out_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*keep_);
+  }
+  void submit_async() override { run(false); }
+  void wait() override {
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*keep_);
+  }
+
+protected:
+  void infer() override { run(true); }
+  void run(bool sync_host) {
+    dfx_nms_io io;
+    memset(&io, 0, sizeof(io));
+    if (boxes_) io.boxes = st_.sync_in(*boxes_, sync_host);
+    if (idx_) io.idx = st_.sync_in(*idx_, sync_host);
+    if (deltas_) io.deltas = st_.sync_in(*deltas_, sync_host);
+    if (anchors_) io.anchors = st_.sync_in(*anchors_, sync_host);
+    if (tab_c_) io.tab_c = st_.sync_in(*tab_c_, false);
+    if (tab_s_) io.tab_s = st_.sync_in(*tab_s_, false);
+    if (count_in_) io.count_in = st_.sync_in(*count_in_, sync_host);
+    io.keep = st_.device_out(*keep_);
+    io.count = st_.device_out(*count_);
+    if (boxes_out_) io.boxes_out = st_.device_out(*boxes_out_);
+    st_.profile_begin();
+    check_dfx(dfx_nms_submit(h_, &io, st_.stream), "nms submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "nms"; }
+
+private:
+  memory *boxes_, *idx_, *deltas_, *anchors_, *count_in_, *keep_, *count_, *boxes_out_;
+  std::unique_ptr<memory> tab_c_, tab_s_;
+  dfx_nms_t *h_;
+  detail::op_state st_;
+};
+
 // ---- squeeze-and-excitation (dfx_se_*) and, with no weights, the global average pooling it starts with.  The two weight
 // tensors are plain oihw {cr, c, 1, 1} and {c, cr, 1, 1}; dst may be src.  Weight hashing and batch sharding are
 // op_depthwise_conv's: the op is per image, so shards are independent. ----
@@ -3166,6 +3274,20 @@ std::unique_ptr<op> select_top_k(const std::unique_ptr<memory> &src, std::unique
                                  std::unique_ptr<memory> &dst_count, int k, bool peak3, int min_val, int c_valid,
                                  const std::vector<memory *> &gather_src, const std::vector<memory *> &gather_dst) {
   return std::unique_ptr<op>(new op_select(src, dst_idx, dst_val, dst_count, k, peak3, min_val, c_valid, gather_src, gather_dst));
+}
+
+std::unique_ptr<op> box_nms(const std::unique_ptr<memory> &boxes, memory *idx, memory *count_in, std::unique_ptr<memory> &dst_keep,
+                            std::unique_ptr<memory> &dst_count, memory *dst_boxes, float iou_thr, int classes) {
+  return std::unique_ptr<op>(new op_nms(boxes.get(), idx, nullptr, nullptr, nullptr, nullptr, count_in, dst_keep.get(), dst_count.get(), dst_boxes,
+                                        iou_thr, classes > 0 ? classes : 1, classes > 0, 1, 0.f, 0.f));
+}
+
+std::unique_ptr<op> box_nms(const std::unique_ptr<memory> &idx, const std::unique_ptr<memory> &deltas, const std::unique_ptr<memory> &anchors,
+                            const std::array<float, 256> &tab_c, const std::array<float, 256> &tab_s, memory *count_in,
+                            std::unique_ptr<memory> &dst_keep, std::unique_ptr<memory> &dst_count, memory *dst_boxes, float iou_thr,
+                            int classes, bool per_class, int anchors_per_pixel, float clip_w, float clip_h) {
+  return std::unique_ptr<op>(new op_nms(nullptr, idx.get(), deltas.get(), anchors.get(), &tab_c, &tab_s, count_in, dst_keep.get(), dst_count.get(),
+                                        dst_boxes, iou_thr, classes, per_class, anchors_per_pixel, clip_w, clip_h));
 }
 
 std::unique_ptr<op> global_avg_pool(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst) {

@@ -523,4 +523,41 @@ int dfx_select_submit(dfx_select_t *hv, const void *src, void *idx, void *val_or
 }
 int dfx_select_destroy(dfx_select_t *h) { return destroy_handle(h); }
 
+// ---- box decode + NMS: reads the mode's inputs (`src`, in the order boxes | idx, deltas, anchors, tab_c, tab_s; count_in when
+// given: bs * 4 bytes); writes keep (`dst`), count (`wei[0]`) and boxes_out when given (`lat`) ----
+int dfx_nms_create(const dfx_nms_desc *d, dfx_nms_t **out) {
+  if (!d || !out || d->bs < 1 || d->n < 1 || d->max_out < 1 || d->max_out > d->n || d->keep_ld < d->max_out) return fail(DFX_ERR_INVALID, "bad nms descriptor");
+  handle *h = new_handle("nms");
+  const size_t e = (size_t)d->bs * d->n;
+  h->src.push_back(d->mode == DFX_NMS_DECODE ? 0 : e * 16);                                                      // boxes
+  h->src.push_back(d->mode == DFX_NMS_DECODE || d->per_class ? (((size_t)d->bs - 1) * d->idx_ld + d->n) * 4 : 0);  // idx
+  h->src.push_back(d->mode == DFX_NMS_DECODE ? (e - 1) * d->row_bytes + 4 * (size_t)d->anchors_per_pixel : 0);    // deltas
+  h->src.push_back(d->mode == DFX_NMS_DECODE ? (size_t)d->n_anchors * 16 : 0);                                   // anchors
+  h->src.push_back(d->mode == DFX_NMS_DECODE ? 1024 : 0);                                                        // a table
+  h->dst = (((size_t)d->bs - 1) * d->keep_ld + d->max_out) * 4;
+  h->lat = (size_t)d->bs * d->max_out * 16;
+  h->wei.push_back((size_t)d->bs * 4);
+  *out = reinterpret_cast<dfx_nms_t *>(h);
+  return DFX_OK;
+}
+int dfx_nms_submit(dfx_nms_t *hv, const dfx_nms_io *io, dfx_stream_t s) {
+  handle *h = reinterpret_cast<handle *>(hv);
+  if (!h || !io) return fail(DFX_ERR_INVALID, "null handle");
+  if (!stream_ok(s, "dfx_nms_submit")) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_nms_submit", {}};
+  const void *in[6] = {io->boxes, io->idx, io->deltas, io->anchors, io->tab_c, io->tab_s};
+  for (int i = 0; i < 6; ++i) {
+    const size_t bytes = h->src[i < 5 ? i : 4];
+    if (bytes && in[i]) add_range(r, in[i], bytes, false);
+  }
+  if (io->count_in) add_range(r, io->count_in, h->wei[0], false);
+  add_range(r, io->keep, h->dst, true);
+  add_range(r, io->count, h->wei[0], true);
+  if (io->boxes_out) add_range(r, io->boxes_out, h->lat, true);
+  r.ranges.push_back({h->packed, 0, 1, false});
+  g_trace.push_back(r);
+  return DFX_OK;
+}
+int dfx_nms_destroy(dfx_nms_t *h) { return destroy_handle(h); }
+
 }  // extern "C"

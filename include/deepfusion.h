@@ -453,12 +453,35 @@ std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array
 //              destination nhwc {bs, Ci, k, 1} of the same dtype: the whole pixel row of every selected element, zero rows
 //              from the count on
 // Bit-exact and the same on every kernel path.  submit / submit_async / wait are scaled_sum()'s; DEEPFUSION_DEVICES does
-// not shard this op.  s32 / f32 scores, k > 4096, NMS and box decoding are not built. ----
+// not shard this op.  s32 / f32 scores and k > 4096 are not built; NMS and box decoding: box_nms() below. ----
 enum { select_all_values = -2147483647 - 1 };  // min_val: the dtype's minimum, every element passes
 std::unique_ptr<op> select_top_k(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, memory *dst_val /* may be null */,
                                  std::unique_ptr<memory> &dst_count, int k, bool peak3 = false, int min_val = select_all_values,
                                  int c_valid = 0, const std::vector<memory *> &gather_src = std::vector<memory *>(),
                                  const std::vector<memory *> &gather_dst = std::vector<memory *>());
+
+// ---- extension: box decode + greedy NMS (dfx_nms_* in dfx.h): the steps between select_top_k() and a detector's answer,
+// without leaving the device.  Per image, n <= 4096 candidates in priority order (position 0 best: what select_top_k()
+// emits; scores are never looked at), standard greedy suppression by IoU > iou_thr, at most max_out survivors.
+//   dst_keep   s32 {bs, max_out, 1, 1}: the kept positions ascending, -1 from the count on
+//   dst_count  s32 {bs, 1, 1, 1}
+//   dst_boxes  may be null; f32 nhwc {bs, 4, max_out, 1}: the kept boxes (x1, y1, x2, y2), zeros from the count on
+//   count_in   may be null; s32 {bs, 1, 1, 1}: select_top_k()'s dst_count -- positions from it on do not exist
+// First form: boxes f32 nhwc {bs, 4, n, 1}; classes > 0 makes it per class with label = idx % classes (idx s32 {bs, n, 1, 1}
+// is then required), classes = 0 class-agnostic (idx is not read).
+// Second form: the boxes are decoded on the device from idx (select_top_k()'s dst_idx over a score map of
+// anchors_per_pixel * classes channels), deltas (its gather destination of the 1-byte delta map, nhwc {bs, C >= 4 A, n, 1}),
+// anchors f32 nhwc {n_anchors, 4, 1, 1} and two tables indexed by the raw delta byte (dx / wx -> tab_c, exp(min(dw / ww,
+// clip)) -> tab_s): torchvision's BoxCoder.decode_single; clip_w > 0 clips to the image like clip_boxes_to_image.
+// Bit-exact and the same on every kernel path.  submit / submit_async / wait are select_top_k()'s; DEEPFUSION_DEVICES does
+// not shard this op.  Min-size filtering, soft-NMS, rotated boxes and n > 4096 are not built. ----
+std::unique_ptr<op> box_nms(const std::unique_ptr<memory> &boxes, memory *idx /* may be null */, memory *count_in /* may be null */,
+                            std::unique_ptr<memory> &dst_keep, std::unique_ptr<memory> &dst_count, memory *dst_boxes /* may be null */,
+                            float iou_thr, int classes = 0);
+std::unique_ptr<op> box_nms(const std::unique_ptr<memory> &idx, const std::unique_ptr<memory> &deltas, const std::unique_ptr<memory> &anchors,
+                            const std::array<float, 256> &tab_c, const std::array<float, 256> &tab_s, memory *count_in /* may be null */,
+                            std::unique_ptr<memory> &dst_keep, std::unique_ptr<memory> &dst_count, memory *dst_boxes /* may be null */,
+                            float iou_thr, int classes, bool per_class, int anchors_per_pixel, float clip_w = 0.f, float clip_h = 0.f);
 
 // ---- extension: depthwise conv + pointwise conv, the depthwise-separable block (dfx_dwpw_* in dfx.h).  Stage 0 is
 // depthwise_conv() with a u8 result (ReLU implied), stage 1 a 1x1 stride-1 unpadded conv() on that tensor; dst holds,

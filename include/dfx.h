@@ -794,8 +794,8 @@ typedef struct dfx_head dfx_head_t;
  *               p = idx / c, from offset (r * h * w + p) * pixel_stride_bytes[i] into out_i[r][j]; out_i is {bs, k,
  *               row_bytes[i]}, dense; rows j >= count[r] are zero-filled.  Bytes only: dtypes do not matter.
  *      The algorithm is exact for 1-byte scores: a histogram of the 256 keys, the threshold key, compaction, a sort of at
- *      most 4096 pairs.  Not built: s32 / f32 scores (DFX_ERR_UNSUPPORTED: they need a multi-pass radix), k > 4096, NMS and
- *      box decoding, windows other than 3x3, NCHW, the peak test fused into the producing conv's epilogue, a sigmoid
+ *      most 4096 pairs.  Not built: s32 / f32 scores (DFX_ERR_UNSUPPORTED: they need a multi-pass radix), k > 4096 (NMS and
+ *      box decoding: dfx_nms below), windows other than 3x3, NCHW, the peak test fused into the producing conv's epilogue, a sigmoid
  *      table in front (dfx_wsum with a table today).  Parity unpinned: the reference has no such op. ---- */
 enum { DFX_SELECT_ALL = 0, DFX_SELECT_PEAK3 = 1 };  /* dfx_select_desc.peak */
 enum { DFX_SELECT_MAX_K = 4096, DFX_SELECT_MAX_GATHER = 4, DFX_SELECT_MAX_ROW_BYTES = 1024 };
@@ -853,6 +853,100 @@ typedef struct dfx_select_info {
   char kernel_name[96];        /* "select_hist<peak3,u8,k100>", "select_generic<all,s8,k1000>" */
 } dfx_select_info;
 typedef struct dfx_select dfx_select_t;
+
+/* ---- box decode + greedy non-maximum suppression: what a RetinaNet / SSD level or an RPN does behind its top-K, on the
+ *      device.  Per image r the op takes n <= 4096 candidates in PRIORITY ORDER, position 0 best -- what dfx_select emits --
+ *      and never looks at a score.  Every floating-point operation below is ONE separately rounded f32 operation in the
+ *      order written, so the result is a function of the inputs alone and every kernel gives the same bits.
+ *        count_in s32 {bs} or NULL: n_valid[r] = min(max(count_in[r], 0), n), n without it.  Positions >= n_valid do not exist.
+ *        mode = DFX_NMS_BOXES   boxes f32 {bs, n, 4} as (x1, y1, x2, y2), dense.
+ *        mode = DFX_NMS_DECODE  idx s32 {bs, n}, rows idx_ld apart (select's idx); deltas {bs, n, row_bytes} bytes (a select
+ *               gather destination: the pixel row of a delta map, 4 * A bytes used); anchors f32 {n_anchors, 4}, shared by
+ *               all images; tab_c, tab_s f32 [256], indexed by the RAW byte (the caller builds them: no exp in the library).
+ *               With e = idx[j]: anchor g = e / classes, a = g % A; bytes q0..q3 = row[4a .. 4a+3] (dx, dy, dw, dh);
+ *                 aw = ax2 - ax1, ah = ay2 - ay1, acx = ax1 + 0.5 * aw, acy = ay1 + 0.5 * ah,
+ *                 cx = acx + tab_c[q0] * aw, cy = acy + tab_c[q1] * ah, w = aw * tab_s[q2], hh = ah * tab_s[q3],
+ *                 x1 = cx - 0.5 * w, y1 = cy - 0.5 * hh, x2 = cx + 0.5 * w, y2 = cy + 0.5 * hh;
+ *               then, if clip_w > 0: x = x < 0 ? 0 : x; x = x > clip_w ? clip_w : x on x1 and x2, likewise y with clip_h
+ *               (the comparisons exactly so: a NaN stays a NaN).  torchvision's BoxCoder.decode_single and
+ *               clip_boxes_to_image with dx / wx and exp(min(dw / ww, clip)) folded into the tables.
+ *        INVALID  an entry with e < 0 or e >= n_anchors * classes (wherever idx is read): never kept, never suppresses.
+ *        LABELS   per_class = 1: label = idx[j] % classes (BOXES mode then needs idx, which it does not read otherwise);
+ *               per_class = 0: all labels are equal.
+ *        TEST   for positions i < j, a = box i, b = box j (the lower position is always a): area(x) = (x2 - x1) * (y2 - y1);
+ *               xx1 = a.x1 > b.x1 ? a.x1 : b.x1, yy1 likewise; xx2 = a.x2 < b.x2 ? a.x2 : b.x2, yy2 likewise;
+ *               w = xx2 - xx1; w = w > 0 ? w : 0, h likewise; inter = w * h; u = (area_a + area_b) - inter; i suppresses j
+ *               iff the labels are equal and inter / u > iou_thr (0 / 0 is NaN and does not suppress): torchvision's nms.
+ *        GREEDY walk j upward; a valid j is kept iff no KEPT i < j suppresses it; stop once max_out are kept.
+ *        RESULT keep s32 {bs, max_out}, rows keep_ld >= max_out apart: the kept positions ascending, -1 behind the count
+ *               (elements max_out .. keep_ld-1 are not written); count s32 {bs}; the optional boxes_out f32 {bs, max_out, 4}:
+ *               the kept boxes (decoded in DECODE mode), zeros behind the count.
+ *      Not built: min-size filtering, soft-NMS, rotated boxes, scores re-sorted after the decode, CenterNet's decode (it
+ *      needs no NMS), n > 4096.  Parity unpinned: the reference has no such op. ---- */
+enum { DFX_NMS_BOXES = 0, DFX_NMS_DECODE = 1 };  /* dfx_nms_desc.mode */
+enum { DFX_NMS_MAX_N = 4096 };
+typedef struct dfx_nms_desc {
+  int32_t bs;
+  int32_t n;                   /* candidates per image, 1 .. DFX_NMS_MAX_N */
+  int32_t max_out;             /* 1 .. n */
+  int32_t keep_ld;             /* elements between rows of keep, >= max_out */
+  int32_t mode;                /* DFX_NMS_BOXES | DFX_NMS_DECODE */
+  int32_t per_class;           /* 0 | 1 */
+  int32_t classes;             /* >= 1 */
+  int32_t anchors_per_pixel;   /* A >= 1 */
+  int32_t n_anchors;           /* >= 1; n_anchors * classes <= 2^31 - 1 */
+  int32_t row_bytes;           /* DECODE: bytes between delta rows, >= 4 * A */
+  int32_t idx_ld;              /* elements between rows of idx, >= n */
+  float iou_thr;               /* finite */
+  float clip_w, clip_h;        /* DECODE: clip_w > 0 clips to [0, clip_w] x [0, clip_h] */
+  int32_t force_path;          /* -1 auto, else DFX_NMS_MASK | DFX_NMS_GENERIC */
+} dfx_nms_desc;
+/* the device pointers of one submit */
+typedef struct dfx_nms_io {
+  const void *boxes;           /* BOXES */
+  const void *idx;             /* DECODE, and BOXES with per_class; else may be NULL */
+  const void *deltas, *anchors, *tab_c, *tab_s;  /* DECODE */
+  const void *count_in;        /* may be NULL */
+  void *keep, *count;
+  void *boxes_out;             /* may be NULL */
+} dfx_nms_io;
+enum {  /* dfx_nms_info.path */
+  DFX_NMS_MASK = 0,            /* three launches (nms.cuh) through scratch owned by the handle.  Class, checked per submit:
+                                  boxes / idx / anchors and every output 16-byte aligned (others take the generic kernel for
+                                  that submit).  A: decode (or copy) into box[bs][n] float4 and lab[bs][n].  B: one wave per
+                                  64 x 64 tile of the upper triangle, lane t owns row box t, the 64 column boxes are LDS
+                                  broadcast reads; one u64 "row suppresses column" per lane, stored plainly.  C: one wave per
+                                  image, lane l holds word l of the removed bitmap; per 64-row block the diagonal tile is
+                                  resolved serially, then every lane ORs its word of the kept rows (512 coalesced bytes per
+                                  row).  No flags, spins, arrival counters or global atomics. */
+  DFX_NMS_GENERIC = 1          /* one workgroup of 1024 lanes per image: boxes, labels and an alive map in LDS, a serial walk
+                                  with a barrier per kept box.  One launch, no scratch, any alignment.  It defines the bits. */
+};
+/* DFX_NMS_AUTO_NOTE: auto takes DFX_NMS_MASK for n >= 200 and max_out >= 100, the smallest of each at which it was measured
+ * and won, and DFX_NMS_GENERIC below either.  On the 24 points of profiles/nms/bench_nms.txt (MI355X, buffers in rotation,
+ * forced legs alternating; us, mask against generic) the mask path beats the generic kernel on all 20 detector points: a
+ * RetinaNet level n 1000, 80 classes, max_out 100 in 30.2 against 52.2 at bs 1 and 31.0 against 52.6 at bs 8, max_out 300 in
+ * 51.6 / 53.5 against 143.9 / 145.3; RPN n 2000, thr 0.7, max_out 1000 in 148 / 158 against 675 / 679; SSD n 200 in 38.9 / 41.5
+ * against 77.5 / 83.4; n 4096 at 3.4 % kept in 78.7 / 134.7 against 476 / 481 and at 67 % kept in 364 / 420 against 2435 / 2458;
+ * BOXES mode within 2 us of DECODE everywhere.  It loses where little is kept: n 1000 with max_out 20 takes 20.4 / 21.5 against
+ * 12.5 / 13.0 (three launches against one barrier per kept box), and n 100 is a tie (21.4 / 24.9 against 22.4 / 23.1); those
+ * stay generic, as do the unmeasured sizes between.  Against the host round trip it replaces (D2H, scalar loop, H2D: its
+ * two copies alone are 17 to 42 us) the mask path is 2x to 140x faster at bs 8 and from n 2000 on, and NOT faster at bs 1
+ * with n <= 1000: 29.3 against 28.3 us, 51.6 against 49.1, 38.9 against 34.1 (DESIGN.md section 4.19 says what bounds it). */
+typedef struct dfx_nms_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t tiles;               /* 64 x 64 tiles of the upper triangle per image (0 on the generic path) */
+  int32_t grid_prep, grid_mask, grid_scan;  /* workgroups of launches A, B, C (generic: grid_scan is its one launch) */
+  int32_t block_prep, block_mask, block_scan;
+  int32_t lds_bytes;           /* the largest of the path's kernels */
+  int32_t launches;            /* per submit */
+  int32_t device;
+  uint64_t scratch_bytes;      /* box + lab + mask + tile table, owned by the handle (0 on the generic path) */
+  uint64_t algorithmic_bytes;  /* boxes (or idx + 4 * A delta bytes + an anchor) read, keep + count written; boxes_out, when
+                                  given, adds bs * max_out * 16 */
+  char kernel_name[96];        /* "nms_mask<decode,perclass,n1000>", "nms_generic<boxes,agnostic,n200>" */
+} dfx_nms_info;
+typedef struct dfx_nms dfx_nms_t;
 
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
@@ -1299,6 +1393,24 @@ int dfx_select_submit(dfx_select_t *h, const void *src_dev, void *idx_dev, void 
 int dfx_select_query(const dfx_select_t *h, dfx_select_info *info);
 int dfx_select_destroy(dfx_select_t *h);
 
+/* ---- box decode + greedy NMS (dfx_nms_desc above).  The descriptor is validated before anything touches a device:
+ *      DFX_ERR_INVALID for bs < 1, n outside 1 .. 4096, max_out outside 1 .. n, keep_ld < max_out, a bad mode / per_class /
+ *      force_path, classes, anchors_per_pixel or n_anchors below 1, n_anchors * classes beyond 2^31 - 1, an iou_thr that is
+ *      not finite, and in DECODE mode row_bytes < 4 * A, idx_ld < n (also BOXES with per_class), a clip_w or clip_h that is
+ *      NaN, or clip_w > 0 without clip_h >= 0.  "No HIP device" is reported only for a valid descriptor.
+ *      submit: asynchronous on `s`; every pointer of dfx_nms_io is a device pointer.  DFX_ERR_INVALID, with nothing launched
+ *      and every output untouched, for a null io, a null pointer the mode needs (BOXES: boxes, and idx with per_class;
+ *      DECODE: idx, deltas, anchors, tab_c, tab_s; always keep and count), an f32 / s32 pointer that is not 4-byte aligned,
+ *      and any output (keep, count, boxes_out) that overlaps an input or another output.  Pointers (boxes, idx, anchors,
+ *      keep, count, boxes_out) that are not 16-byte aligned take the generic kernel for that submit.
+ *      Mask path: the handle owns the scratch its three launches meet in (box, lab, mask), so its submits are SERIALISED
+ *      on the device exactly as dfx_select's histogram path: the host never blocks.  Generic path: one launch with its own
+ *      arguments; submits are independent.  No CPU fallback.  Auto: DFX_NMS_AUTO_NOTE above. ---- */
+int dfx_nms_create(const dfx_nms_desc *desc, dfx_nms_t **out);
+int dfx_nms_submit(dfx_nms_t *h, const dfx_nms_io *io, dfx_stream_t s);
+int dfx_nms_query(const dfx_nms_t *h, dfx_nms_info *info);
+int dfx_nms_destroy(dfx_nms_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -1391,6 +1503,8 @@ int dfx_debug_head_launches(int64_t out[3]);
 /* the same for dfx_select_submit: out[DFX_SELECT_HIST], out[DFX_SELECT_GENERIC] (a submit counts once, whatever the
  * number of its launches) */
 int dfx_debug_select_launches(int64_t out[2]);
+/* the same for dfx_nms_submit: out[DFX_NMS_MASK], out[DFX_NMS_GENERIC] */
+int dfx_debug_nms_launches(int64_t out[2]);
 
 #ifdef __cplusplus
 }

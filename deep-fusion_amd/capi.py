@@ -422,6 +422,7 @@ def lib():
         "dfx_debug_scribble_lds": (i32, [ctypes.c_uint, vp]),
         "dfx_debug_set_tuning": (i32, [ctypes.c_char_p, ctypes.c_char_p]),
         "dfx_debug_conv_sched": (i32, [vp, ctypes.POINTER(ctypes.c_int32), i32]),
+        "dfx_debug_conv_unit_px": (i32, [vp]),
         "dfx_debug_conv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_catconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
         "dfx_debug_dwconv_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
@@ -649,6 +650,13 @@ class Conv(_Handle):
         v = (ctypes.c_int32 * len(ConvSched._fields))()
         _check(lib().dfx_debug_conv_sched(self._h, v, len(v)))
         return ConvSched(*v)
+
+    def unit_px(self):
+        """pixels per pixel-run unit (dfx_debug_conv_unit_px), 0 for row / column units; launches nothing."""
+        v = lib().dfx_debug_conv_unit_px(self._h)
+        if v < 0:
+            _check(v)
+        return v
 
 
 class Pool(_Handle):

@@ -14,7 +14,8 @@
 //    minimises instructions per MFMA and keeps four waves per SIMD.
 //    The 3x3 and 1x1 weights, packed in MFMA fragment order by the host, are copied to LDS
 //    ONCE per CU.
-//  * Work = "units" (TH output rows x TW output columns of one image).  A CU walks a
+//  * Work = "units" (TH output rows x TW output columns of one image; or, MfmaGeom::upx, a run of
+//    consecutive pixels of one image that need not start at a row's first column).  A CU walks a
 //    sequence of units k = 0, 1, ...: loader wave L owns the units with k % 2 == L (the
 //    first `static_rounds` of them statically, the rest from a device-side queue: the
 //    balance211 of op_conv.cc:155-156 made dynamic), stages the unit's input halo tile into
@@ -136,7 +137,8 @@ constexpr int CTL_END = 1;    // [2] first k without a unit, per loader (INT_MAX
 constexpr int CTL_FULL = 4;   // [4] generations published into slot s
 constexpr int CTL_DONE = 8;   // [4] 64 x the tile claims counted off on slot s (cumulative)
 constexpr int CTL_INFO = 16;  // [4][4] per slot: dst pixel index of the unit's first pixel, (th << 16) | tw of
-                              // the (possibly clipped) unit, ceil(2^32 / tiles per row) or 0, unused --
+                              // the (possibly clipped) unit, ceil(2^32 / tiles per row) or 0, unused
+                              // (pixel-run units: first pixel, (pixels << 16) | 1, start column, unused) --
                               // computed once per unit by the loader so that a tile claim costs no division
 
 __device__ __forceinline__ v16i mfma_i8(v4i a, v4i b, v16i c) {
@@ -176,6 +178,12 @@ struct MfmaGeom {  // unit decomposition chosen by the host (dfx_api.hip)
   int half_from;       // unit ids >= half_from denote HALF units (th / 2 rows): id half_from + 2 i + j is half j of unit
                        // half_from + i; total_units counts them.  INT_MAX: none.  The tail of a store-bound op: the
                        // queue's granule is what a workgroup still holds when the queue runs dry (dfx_api.hip)
+  int upx;             // > 0: PIXEL-RUN units (conv_mfma.cuh only; store-bound ops whose row units end in a partial tile).
+                       // Unit u of an image is its pixels [u * upx, min((u + 1) * upx, oh * ow)) in row-major order, upx a
+                       // multiple of 32: every tile is full except the last of an image.  linear == 1, tw == ow, ux == 1,
+                       // uy = units per image, ntu = upx / 32, no half units; th = the most output rows a run touches,
+                       // ceil((ow - 1 + upx) / ow): the halo tile is always th + 2 full-width rows from the run's first row
+                       // and the run's start column travels in the unit record.  0: row / column units as above
   int *queue;          // [0] next unit, [1] finished loaders; both 0 between launches
 #ifdef DFX_STAMPS
   unsigned long long *prof;  // diagnostic build only: [workgroup][wave][16] cycle sums
@@ -253,6 +261,13 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // profiles/r03/probe_coexec.jsonl).  All requant arithmetic is therefore written with scalar float operations
 // and the library is built with -fno-slp-vectorize so that hipcc does not pack them again;
 // tests/test_isa_hazards_cpu.py checks that no packed-f32 instruction is left in the conv kernels.
+
+// A compute wave that waits for its tile's unit polls the slot's flag and unit record (five LDS loads, two
+// v_readfirstlane) every s_sleep(DFX_TILE_WAIT_SLEEP) = 64 cycles each: these polls are counted by SQ_INSTS_LDS /
+// SQ_INSTS_VALU like useful work (pixel-run A/B).  Other values: diagnostic builds only.
+#ifndef DFX_TILE_WAIT_SLEEP
+#define DFX_TILE_WAIT_SLEEP 1
+#endif
 
 #ifndef DFX_RING
 #define DFX_RING 5  // conv0 fragment prefetch depth (k-steps in flight): LDS latency is several hundred cycles under load
@@ -593,7 +608,8 @@ __global__ __launch_bounds__(MFMA_THREADS, 4) void conv_mfma_fused_kernel(ConvAr
   auto unit_origin = [&](int unit, const uint8_t *&src_n, int &y0, int &x0) {
     int n, uyi, uxi, hrow, hth;
     unit_split(unit, n, uyi, uxi, hrow, hth);
-    y0 = uyi * g.th + hrow - a.pt;
+    // (pixel run uyi of the image starts in output row uyi * upx / ow: the host keeps oh * ow * ow < 2^31)
+    y0 = (g.upx ? (int)__umulhi((unsigned)(uyi * g.upx), g.tw_magic) : uyi * g.th + hrow) - a.pt;
     x0 = uxi * g.tw - a.pl;
     src_n = a.src + (size_t)n * a.ih * a.iw * IC;
   };
@@ -602,6 +618,14 @@ __global__ __launch_bounds__(MFMA_THREADS, 4) void conv_mfma_fused_kernel(ConvAr
   auto unit_info = [&](int unit, int &pix0, int &thtw, int &tprm) {
     int n, uyi, uxi, hrow, hth;
     unit_split(unit, n, uyi, uxi, hrow, hth);
+    if (g.upx) {  // pixel run: published as `pixels` rows of ONE column (the tile decode takes the row length from
+                  // g.tw in linear mode), and the start column inside the halo tile's first row in tprm's place
+      const int P0 = uyi * g.upx, y0 = (int)__umulhi((unsigned)P0, g.tw_magic);
+      pix0 = n * a.oh * a.ow + P0;
+      thtw = (min(g.upx, a.oh * a.ow - P0) << 16) | 1;
+      tprm = P0 - y0 * g.tw;
+      return;
+    }
     const int y0 = uyi * g.th + hrow, x0 = uxi * g.tw;
     const int th = max(0, min(hth, a.oh - y0)), tw = min(g.tw, a.ow - x0);  // (0 rows: the second half of a bottom unit)
     const int tpr = g.pool ? (tw + 15) >> 4 : (tw + 31) >> 5;
@@ -770,6 +794,8 @@ __global__ __launch_bounds__(MFMA_THREADS, 4) void conv_mfma_fused_kernel(ConvAr
       padside[m] = e < 2 * pad_half ? side : 2;  // 2 = no entry
       padoff[m] = (((r / CP) * LW + (side ? LW - 1 : 0)) * CP + (r % CP)) * 16;
     }
+    // (pixel-run units always load g.th + 2 rows, g.th = the most rows a run touches: the row tests below are about
+    //  the rows LOADED, so a run near the bottom that touches fewer rows takes the clamped form like a border unit)
     const bool fast_ok = 2 * pad_half <= 128 && (g.th + 2) * a.iw * CP < 65536;
     auto unit_fast = [&](int unit, const uint8_t *&base_u, int &left, int &right) {
       const uint8_t *src_n;
@@ -1016,7 +1042,7 @@ __global__ __launch_bounds__(MFMA_THREADS, 4) void conv_mfma_fused_kernel(ConvAr
     for (int spin = 0; spin < MFMA_SPIN_LIMIT; ++spin) {  // (bounded: a protocol error must not hang the GPU)
       if (__builtin_amdgcn_readfirstlane(lk.full) >= gen + 1) { have = true; info = lk.info; break; }
       if (__builtin_amdgcn_readfirstlane(lk.end) <= k) break;
-      __builtin_amdgcn_s_sleep(1);
+      __builtin_amdgcn_s_sleep(DFX_TILE_WAIT_SLEEP);
       lk = look(s, p);
     }
     const int t_cur = t, k_cur = k, ti_cur = ti;
@@ -1047,7 +1073,7 @@ __global__ __launch_bounds__(MFMA_THREADS, 4) void conv_mfma_fused_kernel(ConvAr
     const int pix0 = __builtin_amdgcn_readfirstlane(info[0]);
     const int thtw = __builtin_amdgcn_readfirstlane(info[1]);
     const int th = thtw >> 16, tw = thtw & 0xffff;
-    const int npx = th * tw;
+    const int npx = th * tw;  // (a pixel run is published as npx x 1, see unit_info)
     const int tiles_per_row = (tw + 31) >> 5;
     const int tiles_per_row16 = (tw + 15) >> 4;  // pooled ops: tiles of 2 rows x 16 columns
     const int ntiles = g.pool ? (th >> 1) * tiles_per_row16 : g.linear ? (npx + 31) >> 5 : th * tiles_per_row;
@@ -1072,9 +1098,10 @@ __global__ __launch_bounds__(MFMA_THREADS, 4) void conv_mfma_fused_kernel(ConvAr
         obase = (size_t)pix0 + (size_t)tr * (a.ow >> 1) + 8 * tc;  // pooled pixel index
       } else if (g.linear) {
         nvalid = min(32, npx - 32 * ti_now);
-        const int pc = 32 * ti_now + min(l31, nvalid - 1);
-        ty = tw == 1 ? pc : (int)__umulhi((unsigned)pc, g.tw_magic);  // tw == g.tw in linear mode
-        tx = pc - ty * tw;
+        const int xs = g.upx ? __builtin_amdgcn_readfirstlane(info[2]) : 0;  // pixel run: its start column
+        const int pc = xs + 32 * ti_now + min(l31, nvalid - 1);
+        ty = g.tw == 1 ? pc : (int)__umulhi((unsigned)pc, g.tw_magic);  // (rows are g.tw == ow long in linear mode)
+        tx = pc - ty * g.tw;
         obase = (size_t)pix0 + 32 * ti_now;
       } else {
         const int tprm = __builtin_amdgcn_readfirstlane(info[2]);

@@ -87,7 +87,7 @@ int dfx::fail(int code, const char *fmt, ...) {  // (declared in dfx_internal.h)
 // ---- testing / tuning switches.  The environment is read ONCE, when the
 //      library is first used; tests flip a switch afterwards with dfx_debug_set_tuning(). ----
 namespace {
-const char *const kTuningKeys[] = {"DFX_MAX_TH", "DFX_FORCE_GEOM", "DFX_STATIC_ROUNDS", "DFX_NO_FAST", "DFX_NO_MAGIC", "DFX_NO_LAZY", "DFX_HALF_UNITS", "DFX_NO_ROLES", "DFX_STORE_BOUND_BYTES",
+const char *const kTuningKeys[] = {"DFX_MAX_TH", "DFX_FORCE_GEOM", "DFX_UNIT_PX", "DFX_STATIC_ROUNDS", "DFX_NO_FAST", "DFX_NO_MAGIC", "DFX_NO_LAZY", "DFX_HALF_UNITS", "DFX_NO_ROLES", "DFX_STORE_BOUND_BYTES",
                                    "DFX_STREAM_PXB", "DFX_STREAM_BLOCKING", "DFX_STREAM_PLANES", "DFX_STREAM_OCC_PAR",
                                    "DFX_STREAM_DIRECT", "DFX_STREAM_PW", "DFX_DIRECT_NPB", "DFX_DIRECT_NW", "DFX_DIRECT_WO1", "DFX_STREAM_GRID", "DFX_DEBUG_PTRS", "DFX_DWCONV_GRID", "DFX_DWCONV_BAND", "DFX_DWPW_GRID", "DFX_DWPW_TH", "DFX_GCONV_GRID", "DFX_GCONV_TILE", "DFX_FC_SPLITK", "DFX_FC_GRID", "DFX_IMGCONV_GRID", "DFX_DECONV_GRID", "DFX_DILCONV_GRID", "DFX_DILCONV_SLAB", "DFX_DILCONV_STRIPS", "DFX_RESIZE_ROWS", "DFX_RESIZE_MAX_GRID", "DFX_SE_SLICES", "DFX_SE_GRID", "DFX_WSUM_GRID", "DFX_HEAD_GRID", "DFX_SELECT_CHUNK",
                                    "DEEPFUSION_PROFILE"};
@@ -373,6 +373,13 @@ static size_t store_bound_bytes() {
   return 512;
 }
 
+static bool roles_eligible(const dfx_conv_desc &d);
+// pixels per pixel-run unit of a store-bound op (0: row units), see pick_geometry; DFX_UNIT_PX overrides it.
+// Chosen by measurement on the s32 headline (profiles/ab_unit_px.txt): runs of 96 pixels -- three full tiles, 33
+// units per 56 x 56 image, 5 halo rows -- 75.8 us against 78.1 us for 2-row units; 128 (4 tiles, 6 halo rows) 78.1,
+// 160 80.2: the lazy queue's granule and the halo rows a loader stages per unit weigh more than the tile count.
+constexpr int kDefaultUnitPx = 96;
+
 static bool pick_geometry(const dfx_conv_desc &d, MfmaGeom &g, int &lds, int ctrl_bytes = MFMA_CTRL_BYTES) {
   const int ICB = d.ic / 32, OCB = d.oc / 32, NCB = d.oc1x1 / 32;
   const size_t fixed = (size_t)OCB * 9 * ICB * 1024 + (size_t)NCB * OCB * 1024 +
@@ -446,7 +453,39 @@ static bool pick_geometry(const dfx_conv_desc &d, MfmaGeom &g, int &lds, int ctr
     }
     g.th = th;
   }
-  g.uy = (d.oh + g.th - 1) / g.th;
+  // Pixel-run units (MfmaGeom::upx): a unit is a run of U consecutive pixels of one image in
+  // row-major order, U a multiple of 32, instead of th whole rows.  Every 32-pixel tile is then full except the last
+  // one of an image (2-row units of a 56-wide image are 3.5 tiles: every fourth tile ran its MFMAs and requant
+  // arithmetic for 16 pixels nobody stores).  For store-bound ops whose row units end in a partial tile; never with
+  // fused pooling, a forced geometry, or a shape the role-specialised kernel could take (conv_mfma_roles.cuh has
+  // no decode for these units, and which kernel runs is only known once the weights are -- see half_from below).
+  // A unit that starts anywhere in a row touches at most rmax = ceil((ow - 1 + U) / ow) output rows; its halo tile
+  // is always rmax + 2 full-width rows, which must fit a ring slot and -- for the default rule, a matter of speed --
+  // the loader's registers (no oversize path; a forced U may take it: write_rest decodes these units like any other).
+  // The fields below are reported as th = rmax, tw = ow, uy = units per image, ux = 1.
+  g.upx = 0;
+  {
+    const bool store_bound = hbm_bound_dst && (size_t)(d.oc1x1 > 0 ? d.oc1x1 : d.oc) * 4 >= store_bound_bytes();
+    int U = store_bound ? kDefaultUnitPx : 0;
+    bool forced = false;
+    if (const char *e = tune("DFX_UNIT_PX")) {  // tuning aid: 0 = off, N = U wherever it is legal (store-bound or not)
+      U = atoi(e);
+      forced = true;
+    }
+    const long long opx = (long long)d.oh * d.ow;
+    // (U < 2^15: the unit record packs pixels << 16; opx * ow < 2^31: pixel / ow by multiply-high with tw_magic)
+    if (U >= 32 && U % 32 == 0 && U < 32768 && g.linear && (g.th * g.tw) % 32 != 0 && !g.pool && !roles_eligible(d) &&
+        !tune("DFX_FORCE_GEOM") && d.ow >= 2 && d.ow < 65536 && opx * d.ow < (1LL << 31)) {
+      const int rmax = (d.ow - 1 + U + d.ow - 1) / d.ow;
+      const size_t chunks = (size_t)(rmax + 2) * (d.ow + 2) * (d.ic / 16);
+      if ((chunks + 63) / 64 * 1024 + 1024 <= tile_max && (forced || chunks <= (size_t)64 * MFMA_LC)) {
+        g.upx = U;
+        g.th = rmax;
+        g.tw = d.ow;
+      }
+    }
+  }
+  g.uy = g.upx ? (int)(((long long)d.oh * d.ow + g.upx - 1) / g.upx) : (d.oh + g.th - 1) / g.th;
   g.ux = (d.ow + g.tw - 1) / g.tw;
   g.total_units = d.bs * g.uy * g.ux;
   g.row_chunks = (g.tw + 2) * (d.ic / 16);
@@ -457,7 +496,8 @@ static bool pick_geometry(const dfx_conv_desc &d, MfmaGeom &g, int &lds, int ctr
   g.upi_magic = g.uy * g.ux > 1 ? (unsigned)(((1ull << 32) + g.uy * g.ux - 1) / (g.uy * g.ux)) : 0u;
   g.ux_magic = g.ux > 1 ? (unsigned)(((1ull << 32) + g.ux - 1) / g.ux) : 0u;
   g.ntu = g.pool ? (g.th / 2) * ((g.tw + 15) / 16)
-                 : g.linear ? (g.th * g.tw + 31) / 32 : g.th * (g.tw / 32);  // tile claims per unit
+          : g.upx ? g.upx / 32
+                  : g.linear ? (g.th * g.tw + 31) / 32 : g.th * (g.tw / 32);  // tile claims per unit
   g.ntu_magic = (unsigned)(((1ull << 32) + g.ntu - 1) / g.ntu);
   g.claim_limit = (int)std::min<long long>(0x7ffffff0LL, (long long)g.ntu * ((long long)g.total_units + 4));
   lds = (int)(fixed + (size_t)MFMA_NB * g.tile_stride);
@@ -1070,7 +1110,7 @@ int dfx_conv_create(const dfx_conv_desc *desc, dfx_conv_t **out) {
       // (dfx_conv_set_weights), after total_units is fixed, so every op whose SHAPE fits the role-specialised
       // kernel goes without half units, also where it later falls back to conv_mfma.cuh.
       h->geom.half_from = 0x7fffffff;
-      if (h->geom.lazy_queue && !h->geom.pool && h->geom.th % 2 == 0 && !h->roles_ok) {
+      if (h->geom.lazy_queue && !h->geom.pool && h->geom.th % 2 == 0 && !h->roles_ok && !h->geom.upx) {  // (pixel-run units have no halves)
         const int half_tiles = h->geom.linear ? ((h->geom.th / 2) * h->geom.tw + 31) / 32 : (h->geom.th / 2) * (h->geom.tw / 32);
         long long nh = half_tiles >= 7 ? 4LL * teams : 0;
         if (const char *e = tune("DFX_HALF_UNITS")) nh = std::max(0, atoi(e));
@@ -1737,6 +1777,13 @@ int dfx_debug_conv_sched(const dfx_conv_t *h, int32_t *out, int n) {
                          g.pool, h->grid * MFMA_TEAMS, (h->roles_ok && h->roles) ? 1 : 0, waits};
   for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
   return DFX_OK;
+}
+
+// test hook: pixels per pixel-run unit of a resident-weight op (MfmaGeom::upx), 0 = row / column units or another
+// kernel family.  Launches nothing.
+int dfx_debug_conv_unit_px(const dfx_conv_t *h) {
+  if (!h) return fail(DFX_ERR_INVALID, "conv_unit_px: null argument");
+  return h->geom.queue ? h->geom.upx : 0;
 }
 
 // test hook: the requant route dfx_conv_set_weights proved for each stage, in ONE numbering for every kernel family

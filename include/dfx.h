@@ -1465,6 +1465,11 @@ int dfx_debug_set_tuning(const char *key, const char *value);
  *   12 ring_waits      stream waits the queue-ring guard of dfx_conv_submit has issued on this handle so far
  * DFX_ERR_UNSUPPORTED for an op without a unit queue (any other kernel). */
 int dfx_debug_conv_sched(const dfx_conv_t *h, int32_t *out, int n);
+/* Read-only: pixels per unit when the op runs PIXEL-RUN units (a unit = a run of that many consecutive pixels of one
+ * image in row-major order, a multiple of 32; dfx_debug_conv_sched then reports th = the most rows such a run
+ * touches, tw = ow, uy = units per image, ux = 1); 0 for row / column units and for every other kernel.  Launches
+ * nothing. */
+int dfx_debug_conv_unit_px(const dfx_conv_t *h);
 /* Read-only: the requant route dfx_conv_set_weights proved for stage 0 (out[0]) and stage 1 (out[1]) from the
  * actual weights, bias and scales; launches nothing.  One numbering for every kernel family:
  *    0 exact   the reference's arithmetic step by step (x86 conversion semantics emulated)

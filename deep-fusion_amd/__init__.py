@@ -31,6 +31,8 @@ from .capi import (  # noqa: F401
     SELECT_ALL, SELECT_PEAK3, SELECT_AUTO, SELECT_HIST, SELECT_GENERIC, SELECT_MAX_K, SelectDesc, SelectInfo, SelectTopK,
     select_launches,
     NMS_BOXES, NMS_DECODE, NMS_AUTO, NMS_MASK, NMS_GENERIC, NMS_MAX_N, NmsDesc, NmsIo, NmsInfo, BoxNms, nms_launches, box_tables,
+    ROI_BATCHED, ROI_LIST, ROIALIGN_AUTO, ROIALIGN_TILE, ROIALIGN_GENERIC, RoiAlignDesc, RoiAlignIo, RoiAlignInfo, RoiAlign,
+    roialign_launches, roi_level_thresholds,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

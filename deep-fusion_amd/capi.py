@@ -39,6 +39,8 @@ SELECT_MAX_K, SELECT_MAX_GATHER = 4096, 4
 NMS_BOXES, NMS_DECODE = 0, 1
 NMS_AUTO, NMS_MASK, NMS_GENERIC = -1, 0, 1
 NMS_MAX_N = 4096
+ROI_BATCHED, ROI_LIST = 0, 1
+ROIALIGN_AUTO, ROIALIGN_TILE, ROIALIGN_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -244,6 +246,22 @@ class NmsInfo(ctypes.Structure):
                 ("kernel_name", ctypes.c_char * 96)]
 
 
+class RoiAlignDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "n", "mode", "levels", "c", "dt")] + \
+               [("h", ctypes.c_int32 * 4), ("w", ctypes.c_int32 * 4), ("src_ld", ctypes.c_int32 * 4),
+                ("spatial_scale", ctypes.c_float * 4), ("level_area_thr", ctypes.c_float * 3)] + \
+               [(n, ctypes.c_int32) for n in ("ph", "pw", "sampling_ratio", "aligned", "dst_ld", "force_path")]
+
+
+class RoiAlignIo(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p * 4)] + [(n, ctypes.c_void_p) for n in ("boxes", "count", "batch_idx", "dst")]
+
+
+class RoiAlignInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "launches", "device", "rows_per_group")] + \
+               [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
+
+
 class DwPwDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t", "pad_l",
                                              "oc", "dst_dt", "bia0_dt", "bia1_dt", "relu", "round_mode0", "round_mode1",
@@ -445,6 +463,11 @@ def lib():
         "dfx_nms_query": (i32, [vp, ctypes.POINTER(NmsInfo)]),
         "dfx_nms_destroy": (i32, [vp]),
         "dfx_debug_nms_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_roialign_create": (i32, [ctypes.POINTER(RoiAlignDesc), ctypes.POINTER(vp)]),
+        "dfx_roialign_submit": (i32, [vp, ctypes.POINTER(RoiAlignIo), vp]),
+        "dfx_roialign_query": (i32, [vp, ctypes.POINTER(RoiAlignInfo)]),
+        "dfx_roialign_destroy": (i32, [vp]),
+        "dfx_debug_roialign_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -496,6 +519,22 @@ def nms_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_nms_launches(v))
     return v[NMS_MASK], v[NMS_GENERIC]
+
+
+def roialign_launches():
+    """(tile, generic): dfx_roialign_submit calls of this process that launched each kernel (dfx_debug_roialign_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_roialign_launches(v))
+    return v[ROIALIGN_TILE], v[ROIALIGN_GENERIC]
+
+
+def roi_level_thresholds(k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6):
+    """The k_max - k_min f32 area thresholds of dfx_roialign's level rule that reproduce torchvision's LevelMapper,
+    level = clamp(floor(canonical_level + log2(sqrt(area) / canonical_scale) + eps), k_min, k_max) - k_min: the mapper steps
+    from level k - 1 to k at sqrt(area) = canonical_scale * 2^(k - canonical_level - eps), so threshold i is the square of
+    that for k = k_min + 1 + i.  Computed in float64, rounded once to f32."""
+    k = np.arange(int(k_min) + 1, int(k_max) + 1, dtype=np.float64)
+    return ((float(canonical_scale) * np.exp2(k - float(canonical_level) - float(eps))) ** 2).astype(np.float32)
 
 
 def box_tables(scale, zero_point, weight_xy, weight_wh, clip=float(np.log(1000.0 / 16)), dtype=np.uint8):
@@ -1161,6 +1200,41 @@ class BoxNms(_Handle):
                         ("count_in", count_in), ("keep", keep_dev), ("count", count_dev), ("boxes_out", boxes_out)):
             setattr(io, name, None if t is None else _dev_ptr(t).value)
         _check(lib().dfx_nms_submit(self._h, ctypes.byref(io), _stream_ptr(stream)))
+
+
+class RoiAlign(_Handle):
+    """dfx_roialign_* handle: torchvision's roi_align over 1 .. 4 NHWC feature maps of one dtype (u8, s8, f32), the level of a
+    RoI chosen by its area against `level_area_thr` (roi_level_thresholds()).  level_shapes: (h, w) per level of tensors
+    {bs, h, w, src_ld}; mode ROI_BATCHED takes BoxNms's boxes_out {bs, n, 4} and count, ROI_LIST boxes {n, 4} and batch_idx
+    {n}; dst {R, ph, pw, dst_ld} (include/dfx.h)."""
+
+    _OP, _INFO = "dfx_roialign", RoiAlignInfo
+
+    def __init__(self, bs, n, level_shapes, c, dtype, out_hw, spatial_scales, sampling_ratio=2, aligned=False, mode=ROI_BATCHED,
+                 level_area_thr=(), src_ld=None, dst_ld=None, force_path=ROIALIGN_AUTO):
+        d = RoiAlignDesc()
+        d.bs, d.n, d.mode, d.levels, d.c = bs, n, mode, len(level_shapes), c
+        d.dt = dtype if isinstance(dtype, int) else _DT[np.dtype(dtype)]
+        for l, (h, w) in enumerate(list(level_shapes)[:4]):
+            d.h[l], d.w[l] = h, w
+            d.src_ld[l] = c if src_ld is None else src_ld[l]
+            d.spatial_scale[l] = spatial_scales[l]
+        for i, t in enumerate(list(level_area_thr)[:3]):
+            d.level_area_thr[i] = t
+        d.ph, d.pw = out_hw
+        d.sampling_ratio, d.aligned, d.force_path = sampling_ratio, int(aligned), force_path
+        d.dst_ld = c if dst_ld is None else dst_ld
+        self.desc = d
+        self._create(d)
+
+    def submit(self, levels_dev, boxes_dev, dst_dev, count=None, batch_idx=None, stream=None):
+        """asynchronous; torch CUDA tensors (or raw pointers); levels_dev: one tensor per level"""
+        io = RoiAlignIo()
+        for l, t in enumerate(levels_dev):
+            io.src[l] = None if t is None else _dev_ptr(t).value
+        for name, t in (("boxes", boxes_dev), ("count", count), ("batch_idx", batch_idx), ("dst", dst_dev)):
+            setattr(io, name, None if t is None else _dev_ptr(t).value)
+        _check(lib().dfx_roialign_submit(self._h, ctypes.byref(io), _stream_ptr(stream)))
 
 
 class DwPwConv(_Handle):

@@ -2818,6 +2818,96 @@ private:
   detail::op_state st_;
 };
 
+// ---- RoIAlign (dfx_roialign_*): what a two-stage detector does behind box_nms().  The levels, boxes and count / batch_idx
+// are registered as reads, dst as a write (op_state).  One handle on one device: DEEPFUSION_DEVICES does not shard this op,
+// as it does not shard select_top_k(). ----
+class op_roialign : public op {
+public:
+  op_roialign(const std::vector<memory *> &levels, const std::vector<float> &scales, const std::vector<float> &thr, memory *boxes, memory *count,
+              memory *batch_idx, memory *dst, int sampling_ratio, bool aligned, int c_valid)
+      : levels_(levels), boxes_(boxes), count_(count), batch_idx_(batch_idx), dst_(dst), h_(nullptr) {
+    using fmt = memory::format;
+    using dt = memory::dtype;
+    if (levels_.empty() || levels_.size() > (size_t)DFX_ROIALIGN_MAX_LEVELS || !levels_[0] || !boxes_ || !dst_)
+      error_and_exit("Init RoiAlign op failed! (null tensor, or not 1 .. 4 levels)");
+    if (scales.size() != levels_.size() || thr.size() + 1 != levels_.size())
+      error_and_exit("Init RoiAlign op failed! (one spatial scale per level and levels - 1 area thresholds)");
+    if (batch_idx_ && count_) error_and_exit("Init RoiAlign op failed! (count belongs to the batched form)");
+    auto l0 = levels_[0]->std_dims(), o = dst_->std_dims(), b = boxes_->std_dims();
+    const int bs = l0[0];
+    dfx_roialign_desc d;
+    memset(&d, 0, sizeof(d));
+    for (size_t l = 0; l < levels_.size(); ++l) {
+      memory *m = levels_[l];
+      if (!m || m->dim_format() != fmt::nhwc || m->data_type() != levels_[0]->data_type()) error_and_exit("Init RoiAlign op failed! (levels must be nhwc of one dtype)");
+      auto i = m->std_dims();
+      if (i[0] != bs || i[1] != l0[1]) error_and_exit("Init RoiAlign op failed! (levels must share bs and C)");
+      d.h[l] = i[2]; d.w[l] = i[3]; d.src_ld[l] = i[1]; d.spatial_scale[l] = scales[l];
+      if (l) d.level_area_thr[l - 1] = thr[l - 1];
+    }
+    if (boxes_->dim_format() != fmt::nhwc || boxes_->data_type() != dt::f32 || b[1] != 4 || b[3] != 1)
+      error_and_exit("Init RoiAlign op failed! (boxes must be f32 nhwc {bs, 4, n, 1} or {R, 4, 1, 1})");
+    if (batch_idx_) {
+      if (b[2] != 1 || batch_idx_->data_type() != dt::s32 || batch_idx_->size() != (size_t)b[0])
+        error_and_exit("Init RoiAlign op failed! (the list form takes boxes {R, 4, 1, 1} and batch_idx s32 {R, 1, 1, 1})");
+      d.mode = DFX_ROI_LIST; d.n = b[0];
+    } else {
+      if (b[0] != bs) error_and_exit("Init RoiAlign op failed! (batched boxes must be {bs, 4, n, 1})");
+      if (count_ && (count_->data_type() != dt::s32 || count_->size() != (size_t)bs)) error_and_exit("Init RoiAlign op failed! (count must be s32 {bs})");
+      d.mode = DFX_ROI_BATCHED; d.n = b[2];
+    }
+    const long long rows = d.mode == DFX_ROI_LIST ? d.n : (long long)bs * d.n;
+    if (dst_->dim_format() != fmt::nhwc || dst_->data_type() != levels_[0]->data_type() || o[0] != rows || o[1] != l0[1])
+      error_and_exit("Init RoiAlign op failed! (dst must be nhwc {R, C, ph, pw} of the levels' dtype)");
+    d.bs = bs; d.levels = (int)levels_.size();
+    d.c = c_valid > 0 ? c_valid : l0[1];
+    d.dt = to_dfx_dtype(dst_->data_type());
+    d.ph = o[2]; d.pw = o[3]; d.dst_ld = o[1];
+    d.sampling_ratio = sampling_ratio; d.aligned = aligned ? 1 : 0;
+    d.force_path = -1;
+    if (dfx_roialign_create(&d, &h_) != DFX_OK) error_and_exit("Init RoiAlign op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_roialign() override {
+    st_.retire(*dst_);
+    dfx_roialign_destroy(h_);
+  }
+
+  void submit() override {
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  void submit_async() override { run(false); }
+  void wait() override {
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+
+protected:
+  void infer() override { run(true); }
+  void run(bool sync_host) {
+    dfx_roialign_io io;
+    memset(&io, 0, sizeof(io));
+    for (size_t l = 0; l < levels_.size(); ++l) io.src[l] = st_.sync_in(*levels_[l], sync_host);
+    io.boxes = st_.sync_in(*boxes_, sync_host);
+    if (count_) io.count = st_.sync_in(*count_, sync_host);
+    if (batch_idx_) io.batch_idx = st_.sync_in(*batch_idx_, sync_host);
+    io.dst = st_.device_out(*dst_);
+    st_.profile_begin();
+    check_dfx(dfx_roialign_submit(h_, &io, st_.stream), "roialign submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "roialign"; }
+
+private:
+  std::vector<memory *> levels_;
+  memory *boxes_, *count_, *batch_idx_, *dst_;
+  dfx_roialign_t *h_;
+  detail::op_state st_;
+};
+
 // ---- squeeze-and-excitation (dfx_se_*) and, with no weights, the global average pooling it starts with.  The two weight
 // tensors are plain oihw {cr, c, 1, 1} and {c, cr, 1, 1}; dst may be src.  Weight hashing and batch sharding are
 // op_depthwise_conv's: the op is per image, so shards are independent. ----
@@ -3288,6 +3378,12 @@ std::unique_ptr<op> box_nms(const std::unique_ptr<memory> &idx, const std::uniqu
                             int classes, bool per_class, int anchors_per_pixel, float clip_w, float clip_h) {
   return std::unique_ptr<op>(new op_nms(nullptr, idx.get(), deltas.get(), anchors.get(), &tab_c, &tab_s, count_in, dst_keep.get(), dst_count.get(),
                                         dst_boxes, iou_thr, classes, per_class, anchors_per_pixel, clip_w, clip_h));
+}
+
+std::unique_ptr<op> roi_align(const std::vector<memory *> &levels, const std::vector<float> &spatial_scales,
+                              const std::vector<float> &level_area_thr, memory *boxes, memory *count, memory *batch_idx,
+                              std::unique_ptr<memory> &dst, int sampling_ratio, bool aligned, int c_valid) {
+  return std::unique_ptr<op>(new op_roialign(levels, spatial_scales, level_area_thr, boxes, count, batch_idx, dst.get(), sampling_ratio, aligned, c_valid));
 }
 
 std::unique_ptr<op> global_avg_pool(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst) {

@@ -560,4 +560,35 @@ int dfx_nms_submit(dfx_nms_t *hv, const dfx_nms_io *io, dfx_stream_t s) {
 }
 int dfx_nms_destroy(dfx_nms_t *h) { return destroy_handle(h); }
 
+// ---- RoIAlign: reads the levels (`src[0 .. levels-1]`), boxes (`wei[0]`) and count or batch_idx when given (`wei[1]`);
+// writes dst (`dst`) ----
+int dfx_roialign_create(const dfx_roialign_desc *d, dfx_roialign_t **out) {
+  if (!d || !out || d->bs < 1 || d->n < 1 || d->levels < 1 || d->levels > DFX_ROIALIGN_MAX_LEVELS || d->c < 1 || d->dst_ld < d->c || d->ph < 1 ||
+      d->pw < 1)
+    return fail(DFX_ERR_INVALID, "bad roialign descriptor");
+  handle *h = new_handle("roialign");
+  const size_t es = d->dt == DFX_F32 ? 4 : 1, rows = d->mode == DFX_ROI_LIST ? (size_t)d->n : (size_t)d->bs * d->n;
+  for (int l = 0; l < d->levels; ++l) h->src.push_back((((size_t)d->bs * d->h[l] * d->w[l] - 1) * d->src_ld[l] + d->c) * es);
+  h->dst = ((rows * d->ph * d->pw - 1) * d->dst_ld + d->c) * es;
+  h->wei.push_back(rows * 16);
+  h->wei.push_back(d->mode == DFX_ROI_LIST ? rows * 4 : (size_t)d->bs * 4);
+  *out = reinterpret_cast<dfx_roialign_t *>(h);
+  return DFX_OK;
+}
+int dfx_roialign_submit(dfx_roialign_t *hv, const dfx_roialign_io *io, dfx_stream_t s) {
+  handle *h = reinterpret_cast<handle *>(hv);
+  if (!h || !io) return fail(DFX_ERR_INVALID, "null handle");
+  if (!stream_ok(s, "dfx_roialign_submit")) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_roialign_submit", {}};
+  for (size_t l = 0; l < h->src.size(); ++l) add_range(r, io->src[l], h->src[l], false);
+  add_range(r, io->boxes, h->wei[0], false);
+  if (io->count) add_range(r, io->count, h->wei[1], false);
+  if (io->batch_idx) add_range(r, io->batch_idx, h->wei[1], false);
+  add_range(r, io->dst, h->dst, true);
+  r.ranges.push_back({h->packed, 0, 1, false});
+  g_trace.push_back(r);
+  return DFX_OK;
+}
+int dfx_roialign_destroy(dfx_roialign_t *h) { return destroy_handle(h); }
+
 }  // extern "C"

@@ -483,6 +483,25 @@ std::unique_ptr<op> box_nms(const std::unique_ptr<memory> &idx, const std::uniqu
                             std::unique_ptr<memory> &dst_keep, std::unique_ptr<memory> &dst_count, memory *dst_boxes /* may be null */,
                             float iou_thr, int classes, bool per_class, int anchors_per_pixel, float clip_w = 0.f, float clip_h = 0.f);
 
+// ---- extension: RoIAlign (dfx_roialign_* in dfx.h): the step between box_nms() and a two-stage detector's heads
+// (inner_product() over 7 x 7 tiles, conv() / deconvolution() over 14 x 14 ones), without leaving the device: torchvision's
+// roi_align forward with every f32 step rounded separately in a fixed order.
+//   levels          1 .. 4 nhwc tensors {bs, C, h_l, w_l} of one dtype (u8, s8, f32); the first c_valid channels take part (0: all)
+//   spatial_scales  one per level; level_area_thr: levels - 1 thresholds on (x2 - x1) * (y2 - y1), non-decreasing -- the
+//                   level of a RoI is the number of thresholds its area reaches (torchvision's LevelMapper squared: dfx.h)
+//   boxes           batch_idx null: f32 nhwc {bs, 4, n, 1}, box_nms()'s dst_boxes, with count (may be null; s32 {bs, 1, 1, 1},
+//                   box_nms()'s dst_count): RoI j of image r reads image r, rows from the count on are zeros.
+//                   batch_idx given (s32 {R, 1, 1, 1}): boxes f32 nhwc {R, 4, 1, 1}, row i reads image batch_idx[i]; an index
+//                   outside [0, bs) gives a row of zeros; count must be null.
+//   dst             nhwc {R, C, ph, pw} of the levels' dtype, R = bs * n or R; its height and width are the bin counts (1 .. 64)
+// Bit-exact and the same on every kernel path.  submit / submit_async / wait are box_nms()'s; DEEPFUSION_DEVICES does not
+// shard this op, as it does not shard select_top_k().  Adaptive sampling (sampling_ratio 0), RoIPool / max mode, rotated
+// RoIs, NCHW, position-sensitive pooling and u8 -> f32 output are not built. ----
+std::unique_ptr<op> roi_align(const std::vector<memory *> &levels, const std::vector<float> &spatial_scales,
+                              const std::vector<float> &level_area_thr, memory *boxes, memory *count /* may be null */,
+                              memory *batch_idx /* null: batched */, std::unique_ptr<memory> &dst, int sampling_ratio = 2,
+                              bool aligned = false, int c_valid = 0);
+
 // ---- extension: depthwise conv + pointwise conv, the depthwise-separable block (dfx_dwpw_* in dfx.h).  Stage 0 is
 // depthwise_conv() with a u8 result (ReLU implied), stage 1 a 1x1 stride-1 unpadded conv() on that tensor; dst holds,
 // bit for bit, what the two ops give one after the other.  wei_dw: plain oihw s8 {c, 1, kh, kw}; wei_pw: OIhw4i16o4i

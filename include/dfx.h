@@ -948,6 +948,101 @@ typedef struct dfx_nms_info {
 } dfx_nms_info;
 typedef struct dfx_nms dfx_nms_t;
 
+/* ---- RoIAlign: the step between an RPN's kept boxes and a two-stage detector's heads (Faster R-CNN's 7 x 7 box head,
+ *      Mask R-CNN's 14 x 14 mask head), on the device.  Every floating-point operation below is ONE separately rounded f32
+ *      operation in the order written, so the result is a function of the inputs alone and every kernel gives the same bits.
+ *        LEVELS  1 .. 4 feature maps of one dtype (u8, s8 or f32), level l NHWC {bs, h[l], w[l], c} with pixel stride
+ *               src_ld[l] >= c elements (pad channels are never read), h[l], w[l] in 1 .. 65535, and its own
+ *               spatial_scale[l], finite and > 0.
+ *        ROIS   mode = DFX_ROI_BATCHED  boxes f32 {bs, n, 4} as (x1, y1, x2, y2), dense: dfx_nms's boxes_out with n = its
+ *               max_out.  count s32 {bs} or NULL (dfx_nms's count): n_valid[r] = min(max(count[r], 0), n), n without it.
+ *               RoI j of image r reads image r; R = bs * n output rows, rows at positions >= n_valid[r] are zeros.
+ *               mode = DFX_ROI_LIST     boxes f32 {R, 4} with R = n, batch_idx s32 {R}: row i reads image batch_idx[i]; a row
+ *               whose index lies outside [0, bs) is zeros.
+ *        OUTPUT dst {R, ph, pw, c} NHWC of src's dtype with pixel stride dst_ld >= c; elements c .. dst_ld-1 of a pixel
+ *               are not written.  ph, pw in 1 .. 64; sampling_ratio S in 1 .. 4 (torchvision's adaptive sampling_ratio = 0
+ *               is DFX_ERR_UNSUPPORTED); aligned 0 or 1.
+ *        LEVEL  area = (x2 - x1) * (y2 - y1); the level is the number of i < levels - 1 with area >= level_area_thr[i]
+ *               (finite, non-decreasing; a NaN area gives level 0).  No log2 on the device: the caller builds the thresholds.
+ *        ARITHMETIC, with s the level's scale, o = aligned ? 0.5f : 0.0f, H and W the level's size:
+ *               rsw = x1 * s - o, rsh = y1 * s - o, rew = x2 * s - o, reh = y2 * s - o              (a mul, then a sub)
+ *               rw = rew - rsw, rh = reh - rsh; if (!aligned) { rw = rw > 1 ? rw : 1; rh = rh > 1 ? rh : 1; }
+ *               bw = rw / (float)pw, bh = rh / (float)ph
+ *               for bin row p and iy in 0 .. S-1:  y = (rsh + (float)p * bh) + (((float)iy + 0.5f) * bh) / (float)S
+ *                 yvalid = (y >= -1.0f && y <= (float)H)          (this form exactly: a NaN is invalid)
+ *                 if (y <= 0) y = 0; yl = (int)y; if (yl >= H - 1) { yh = yl = H - 1; y = (float)yl; } else yh = yl + 1
+ *                 ly = y - (float)yl, hy = 1.0f - ly              (likewise x, xl, xh, lx, hx, xvalid from rsw, bw, W)
+ *               sample(iy, ix) = yvalid && xvalid ? ((w1 * v1 + w2 * v2) + w3 * v3) + w4 * v4 : +0.0f
+ *                 with w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx and v1 = src[yl][xl], v2 = src[yl][xh],
+ *                 v3 = src[yh][xl], v4 = src[yh][xh] converted to f32
+ *               acc = +0.0f; acc += sample(iy, ix), iy ascending, ix ascending within iy; out = acc / (float)(S * S)
+ *               u8 / s8: out is rounded to nearest even and saturated, as dfx_reorder and dfx_resize convert; f32 is stored
+ *               as it is.  A sample is left out only by its valid bits, never because a weight is zero: an f32 Inf under
+ *               a zero weight gives NaN on every kernel.
+ *      Nothing can fault: invalid coordinates never become addresses and every index that is used is clamped into the map.
+ *      This is torchvision's roi_align forward.  Parity unpinned: torchvision's build may contract the multiplies and adds.
+ *      Not built: adaptive sampling, RoIPool / max mode, rotated RoIs, NCHW, position-sensitive pooling, u8 -> f32
+ *      output. ---- */
+enum { DFX_ROI_BATCHED = 0, DFX_ROI_LIST = 1 };  /* dfx_roialign_desc.mode */
+enum { DFX_ROIALIGN_MAX_LEVELS = 4, DFX_ROIALIGN_MAX_BINS = 64, DFX_ROIALIGN_MAX_SAMPLING = 4 };
+typedef struct dfx_roialign_desc {
+  int32_t bs;
+  int32_t n;                   /* BATCHED: RoIs per image (R = bs * n); LIST: R */
+  int32_t mode;                /* DFX_ROI_BATCHED | DFX_ROI_LIST */
+  int32_t levels;              /* 1 .. 4 */
+  int32_t c;
+  int32_t dt;                  /* DFX_U8 | DFX_S8 | DFX_F32 */
+  int32_t h[4], w[4];          /* 1 .. 65535 each; entries from `levels` on are ignored */
+  int32_t src_ld[4];           /* elements between pixels of a level, >= c */
+  float spatial_scale[4];      /* finite, > 0 */
+  float level_area_thr[3];     /* levels - 1 used: finite, non-decreasing */
+  int32_t ph, pw;              /* 1 .. 64 */
+  int32_t sampling_ratio;      /* 1 .. 4; 0 is DFX_ERR_UNSUPPORTED */
+  int32_t aligned;             /* 0 | 1 */
+  int32_t dst_ld;              /* elements between pixels of dst, >= c */
+  int32_t force_path;          /* -1 auto, else DFX_ROIALIGN_TILE | DFX_ROIALIGN_GENERIC */
+} dfx_roialign_desc;
+/* the device pointers of one submit */
+typedef struct dfx_roialign_io {
+  const void *src[4];          /* the levels */
+  const void *boxes;
+  const void *count;           /* BATCHED; may be NULL */
+  const void *batch_idx;       /* LIST */
+  void *dst;
+} dfx_roialign_io;
+enum {  /* dfx_roialign_info.path */
+  DFX_ROIALIGN_TILE = 0,       /* one launch (roialign.cuh).  Class: u8 / s8 with c % 16 == 0 or f32 with c % 4 == 0, and every
+                                  ld a whole number of 16 bytes; checked per submit: every level, boxes and dst 16-byte aligned
+                                  (others take the generic kernel for that submit).  A workgroup owns one RoI, or a run of
+                                  bin rows of one where the plan splits RoIs because R is small against the CU count; its
+                                  lanes write the two per-axis sample tables (low / high offset, two weights, valid) into
+                                  LDS, one barrier, then a lane owns one 16-byte channel group of one bin: four 16-byte
+                                  corner loads per sample, bytes converted in registers, one 16-byte store.  No atomics,
+                                  flags or cross-workgroup communication. */
+  DFX_ROIALIGN_GENERIC = 1     /* one thread per output element; any c, ld and alignment.  It defines the bits. */
+};
+/* DFX_ROIALIGN_AUTO_NOTE: auto takes DFX_ROIALIGN_TILE inside its class for c * sizeof(element) >= 256 bytes, R >= 100
+ * RoIs and ph * pw >= 49 bins, the smallest of each at which it was measured and won, and DFX_ROIALIGN_GENERIC below any
+ * of them and outside the class.  On the 8 points of profiles/roialign/bench_roialign.txt (MI355X, buffers in rotation,
+ * forced legs alternating; us, tile against generic; S 2, levels by area) the tile kernel wins on every one: the Faster
+ * R-CNN-FPN box head (4 levels x 256 u8, n 1000, 7 x 7) in 27.3 against 162.7 at bs 1 and 181 against 1183 at bs 8; the
+ * mask head (n 100, 14 x 14) in 15.7 against 67.4 and 79.8 against 483; a C4 head (50 x 76 x 1024 u8, n 300, 14 x 14) in
+ * 116 against 687 and 650 against 5116; the box head in f32 in 65.5 against 184 and 486 against 1220.  Nothing smaller
+ * was timed (fewer channels, fewer RoIs, fewer bins, S other than 2 -- S is not part of the rule), so those stay on the
+ * generic kernel; DFX_ROIALIGN_TILE is reachable there with force_path and gives the same bits.  What bounds it:
+ * DESIGN.md section 4.20. */
+typedef struct dfx_roialign_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t grid, block;
+  int32_t lds_bytes;
+  int32_t launches;            /* per submit: 1 */
+  int32_t device;
+  int32_t rows_per_group;      /* tile path: bin rows a workgroup owns (ph unless the plan splits RoIs); 0 on generic */
+  uint64_t algorithmic_bytes;  /* boxes + count / batch_idx read, four corner pixels per sample read, dst written */
+  char kernel_name[96];        /* "roialign_tile<u8,7x7,s2,l4>", "roialign_generic<f32,14x14,s2,l1>" */
+} dfx_roialign_info;
+typedef struct dfx_roialign dfx_roialign_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -1411,6 +1506,23 @@ int dfx_nms_submit(dfx_nms_t *h, const dfx_nms_io *io, dfx_stream_t s);
 int dfx_nms_query(const dfx_nms_t *h, dfx_nms_info *info);
 int dfx_nms_destroy(dfx_nms_t *h);
 
+/* ---- RoIAlign (dfx_roialign_desc above).  The descriptor is validated before anything touches a device: DFX_ERR_INVALID
+ *      for bs or n below 1, a bad mode / aligned / force_path, levels outside 1 .. 4, c < 1, a dtype other than u8 / s8 /
+ *      f32, an h or w outside 1 .. 65535, an ld below c, a scale that is not finite and > 0, thresholds that are not finite
+ *      and non-decreasing, ph or pw outside 1 .. 64, a sampling_ratio outside 0 .. 4, and a force_path of
+ *      DFX_ROIALIGN_TILE outside its class; DFX_ERR_UNSUPPORTED for sampling_ratio 0 and for what the kernels' 32-bit byte
+ *      offsets cannot address: dst, or any level, of 2^32 bytes or more.  "No HIP device" is reported only for a valid
+ *      descriptor.
+ *      submit: asynchronous on `s`; every pointer of dfx_roialign_io is a device pointer.  DFX_ERR_INVALID, with nothing
+ *      launched and dst untouched, for a null io, a null level, boxes, dst, or batch_idx in LIST mode, an f32 / s32 pointer
+ *      that is not 4-byte aligned, and a dst that overlaps an input.  A level, boxes or dst that is not 16-byte aligned
+ *      takes the generic kernel for that submit.  One launch with its own arguments: submits are independent, from any
+ *      thread on any stream.  No CPU fallback.  Auto: DFX_ROIALIGN_AUTO_NOTE above. ---- */
+int dfx_roialign_create(const dfx_roialign_desc *desc, dfx_roialign_t **out);
+int dfx_roialign_submit(dfx_roialign_t *h, const dfx_roialign_io *io, dfx_stream_t s);
+int dfx_roialign_query(const dfx_roialign_t *h, dfx_roialign_info *info);
+int dfx_roialign_destroy(dfx_roialign_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -1510,6 +1622,8 @@ int dfx_debug_head_launches(int64_t out[3]);
 int dfx_debug_select_launches(int64_t out[2]);
 /* the same for dfx_nms_submit: out[DFX_NMS_MASK], out[DFX_NMS_GENERIC] */
 int dfx_debug_nms_launches(int64_t out[2]);
+/* the same for dfx_roialign_submit: out[DFX_ROIALIGN_TILE], out[DFX_ROIALIGN_GENERIC] */
+int dfx_debug_roialign_launches(int64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,7 @@ NMS_AUTO, NMS_MASK, NMS_GENERIC = -1, 0, 1
 NMS_MAX_N = 4096
 ROI_BATCHED, ROI_LIST = 0, 1
 ROIALIGN_AUTO, ROIALIGN_TILE, ROIALIGN_GENERIC = -1, 0, 1
+BMM_AUTO, BMM_MFMA, BMM_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -262,6 +263,18 @@ class RoiAlignInfo(ctypes.Structure):
                [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
 
 
+class BmmDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("batch0", "batch1", "m", "n", "k", "trans_b", "a_dt", "b_dt", "dst_dt", "relu",
+                                              "round_mode", "nscales", "force_path")] + \
+               [(n, ctypes.c_int64) for n in ("a_s0", "a_s1", "lda", "b_s0", "b_s1", "ldb", "c_s0", "c_s1", "ldc")]
+
+
+class BmmInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
 class DwPwDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t", "pad_l",
                                              "oc", "dst_dt", "bia0_dt", "bia1_dt", "relu", "round_mode0", "round_mode1",
@@ -468,6 +481,13 @@ def lib():
         "dfx_roialign_query": (i32, [vp, ctypes.POINTER(RoiAlignInfo)]),
         "dfx_roialign_destroy": (i32, [vp]),
         "dfx_debug_roialign_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_bmm_create": (i32, [ctypes.POINTER(BmmDesc), ctypes.POINTER(vp)]),
+        "dfx_bmm_set_scales": (i32, [vp, vp]),
+        "dfx_bmm_submit": (i32, [vp, vp, vp, vp, vp]),
+        "dfx_bmm_query": (i32, [vp, ctypes.POINTER(BmmInfo)]),
+        "dfx_bmm_destroy": (i32, [vp]),
+        "dfx_debug_bmm_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_debug_bmm_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -526,6 +546,23 @@ def roialign_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_roialign_launches(v))
     return v[ROIALIGN_TILE], v[ROIALIGN_GENERIC]
+
+
+def bmm_launches():
+    """(mfma, generic): dfx_bmm_submit calls of this process that launched each kernel (dfx_debug_bmm_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_bmm_launches(v))
+    return v[BMM_MFMA], v[BMM_GENERIC]
+
+
+def attention_strides(bs, heads, t, d, ld=None):
+    """(s0, s1, ld) in elements of the per-head {T, d} matrices of a head-sliced {bs, T, heads * d} NHWC tensor whose
+    rows are `ld` elements apart (heads * d when None): matrix (b0, b1) = (image, head) starts at b0 * s0 + b1 * s1.
+    What dfa.MatMul takes as a_strides / b_strides / c_strides with batch = (bs, heads)."""
+    ld = heads * d if ld is None else int(ld)
+    if min(bs, heads, t, d) < 1 or ld < heads * d:
+        raise ValueError("bs, heads, t, d must be positive and ld at least heads * d")
+    return t * ld, d, ld
 
 
 def roi_level_thresholds(k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6):
@@ -1235,6 +1272,46 @@ class RoiAlign(_Handle):
         for name, t in (("boxes", boxes_dev), ("count", count), ("batch_idx", batch_idx), ("dst", dst_dev)):
             setattr(io, name, None if t is None else _dev_ptr(t).value)
         _check(lib().dfx_roialign_submit(self._h, ctypes.byref(io), _stream_ptr(stream)))
+
+
+class MatMul(_Handle):
+    """dfx_bmm_* handle: batched int8 matrix product of two device tensors (include/dfx.h): C[g] = requant(A[g] . B[g]^T)
+    (trans_b, B {N, K}: Q.K^T) or A[g] . B[g] (B {K, N}: P.V) over batch = (batch0, batch1) matrices.  a_strides / b_strides /
+    c_strides are (s0, s1, ld) in elements (None: densely packed); a batch stride of 0 broadcasts A or B.  A u8 or s8, B s8,
+    C any of the four dtypes.  set_scales() first; submit(a, b, c)."""
+
+    _OP, _INFO, _ROUTES = "dfx_bmm", BmmInfo, 1
+
+    def __init__(self, batch, m, n, k, a_dtype=np.uint8, dst_dtype=np.int8, trans_b=True, a_strides=None, b_strides=None,
+                 c_strides=None, relu=False, rm=ROUND_NEAREST, nscales=1, b_dtype=np.int8, force_path=BMM_AUTO, scales=None):
+        code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
+        batch0, batch1 = (1, batch) if isinstance(batch, int) else batch
+        brows, bcols = (n, k) if trans_b else (k, n)
+
+        def dense(rows, cols):
+            return batch1 * rows * cols, rows * cols, cols
+
+        d = BmmDesc()
+        d.batch0, d.batch1, d.m, d.n, d.k, d.trans_b = batch0, batch1, m, n, k, int(bool(trans_b))
+        d.a_dt, d.b_dt, d.dst_dt = code(a_dtype), code(b_dtype), code(dst_dtype)
+        d.relu, d.round_mode, d.nscales, d.force_path = int(relu), rm, nscales, force_path
+        d.a_s0, d.a_s1, d.lda = dense(m, k) if a_strides is None else a_strides
+        d.b_s0, d.b_s1, d.ldb = dense(brows, bcols) if b_strides is None else b_strides
+        d.c_s0, d.c_s1, d.ldc = dense(m, n) if c_strides is None else c_strides
+        self.desc = d
+        self._create(d)
+        if scales is not None:
+            self.set_scales(scales)
+
+    def set_scales(self, scales):
+        """1 or n floats (the descriptor's nscales); may be called again"""
+        s = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+        assert s.size == self.desc.nscales, (s.size, self.desc.nscales)
+        _check(lib().dfx_bmm_set_scales(self._h, _p(s)))
+
+    def submit(self, a_dev, b_dev, c_dev, stream=None):
+        """asynchronous; torch CUDA tensors (or raw pointers)"""
+        _check(lib().dfx_bmm_submit(self._h, _dev_ptr(a_dev), _dev_ptr(b_dev), _dev_ptr(c_dev), _stream_ptr(stream)))
 
 
 class DwPwConv(_Handle):

@@ -1,0 +1,186 @@
+// bmm_api.hip -- host side of the batched int8 matrix product (dfx_bmm_* of include/dfx.h): descriptor validation, the
+// path and the grids (all planned in bmm_plan.h), the device copy of the scales with the requant route proved from the
+// shape, the overlap check and the choice of the kernel per submit, launches.  The kernels are in bmm.cuh / bmm.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "dfx_internal.h"
+#include "bmm.cuh"
+#include "bmm_plan.h"
+#include "requant_host.h"
+
+namespace dfx {
+int launch_bmm_mfma(const BmmArgs &a, int grid, hipStream_t s, bool fast);
+int launch_bmm_generic(const BmmArgs &a, int grid, hipStream_t s);
+}
+using namespace dfx;
+
+struct dfx_bmm {
+  dfx_bmm_desc d;
+  int device = 0;
+  int path = DFX_BMM_GENERIC;
+  int grid[2] = {0, 0};        // per path; [path] and [DFX_BMM_GENERIC] (the per-submit fallback) are used
+  BmmArgs args = {};           // everything but a / b / c; copied per launch
+  float *d_scale = nullptr;    // [n rounded up to 32]
+  int n_pad = 0;
+  std::atomic<int> scales_set{0};
+  int route = 0;               // 0 exact, 1 fast (dfx_debug_conv_requant's numbering); MFMA path only
+  char kernel_name[96] = "";
+};
+
+namespace {
+
+// launches since the library was loaded, by the kernel that ran; process-wide, because submit does not write to the
+// handle (dfx_debug_bmm_launches)
+std::atomic<long long> g_launches[2];
+
+long long grid_cap() {
+  const char *e = tuning_value("DFX_BMM_GRID");  // testing aid
+  return e ? std::max(1ll, atoll(e)) : 0;
+}
+
+void set_name(dfx_bmm *h) {
+  const dfx_bmm_desc &d = h->d;
+  const char *form = d.trans_b ? "nt" : "nn";
+  if (h->path == DFX_BMM_MFMA)
+    snprintf(h->kernel_name, sizeof(h->kernel_name), "bmm_mfma<%s,%s,%s> %s", form, dt_name(d.a_dt), dt_name(d.dst_dt),
+             !h->scales_set.load() ? "(no scales)" : h->route ? "fast" : "exact");
+  else
+    snprintf(h->kernel_name, sizeof(h->kernel_name), "bmm_generic<%s,%s,%s> exact", form, dt_name(d.a_dt), dt_name(d.dst_dt));
+}
+
+}  // namespace
+
+extern "C" {
+
+int dfx_bmm_create(const dfx_bmm_desc *desc, dfx_bmm_t **out) {
+  if (!desc || !out) return fail(DFX_ERR_INVALID, "bmm_create: null argument");
+  *out = nullptr;
+  const dfx_bmm_desc &d = *desc;
+  const char *why = "";
+  const int rc = bmm_validate(d, &why);
+  if (rc) return fail(rc, "bmm: %s", why);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(DFX_ERR_NO_DEVICE, "bmm_create: no HIP device (this library has no CPU path)");
+  dfx_bmm *h = new (std::nothrow) dfx_bmm();
+  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
+  h->d = d;
+  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
+    delete h;
+    return fail(DFX_ERR_HIP, "bmm_create: cannot query the device");
+  }
+  const int cus = std::max(1, prop.multiProcessorCount);
+  // AUTO RULE (include/dfx.h DFX_BMM_AUTO_NOTE)
+  h->path = bmm_path(d);
+  const long long cap = grid_cap();
+  h->grid[h->path] = bmm_grid(d, h->path, cus, cap);
+  h->grid[DFX_BMM_GENERIC] = bmm_grid(d, DFX_BMM_GENERIC, cus, cap);
+  h->n_pad = (int)(((long long)d.n + 31) / 32 * 32);  // (n <= 2^31 - 32: bmm_validate)
+  const hipError_t e = hipMalloc((void **)&h->d_scale, (size_t)h->n_pad * sizeof(float));
+  if (e != hipSuccess) {
+    delete h;
+    return fail(DFX_ERR_HIP, "bmm_create: scales: %s", hipGetErrorString(e));
+  }
+  BmmArgs &a = h->args;
+  a.scale = h->d_scale;
+  a.a_s0 = d.a_s0; a.a_s1 = d.a_s1; a.lda = d.lda;
+  a.b_s0 = d.b_s0; a.b_s1 = d.b_s1; a.ldb = d.ldb;
+  a.c_s0 = d.c_s0; a.c_s1 = d.c_s1; a.ldc = d.ldc;
+  a.batch0 = d.batch0; a.batch1 = d.batch1; a.m = d.m; a.n = d.n; a.k = d.k;
+  a.trans_b = d.trans_b; a.a_u8 = d.a_dt == DFX_U8; a.dst_dt = d.dst_dt;
+  a.relu = (d.relu || d.dst_dt == DFX_U8) ? 1 : 0; a.rm = d.round_mode;
+  a.mt = (int)bmm_mtiles(d); a.nt = (int)bmm_ntiles(d);
+  a.tiles = bmm_tiles(d); a.units = bmm_units(d);
+  a.items = bmm_items(d);
+  set_name(h);
+  *out = h;
+  return DFX_OK;
+}
+
+int dfx_bmm_set_scales(dfx_bmm_t *h, const float *scales) {
+  if (!h || !scales) return fail(DFX_ERR_INVALID, "bmm_set_scales: null argument");
+  const dfx_bmm_desc &d = h->d;
+  std::vector<float> img((size_t)h->n_pad, 0.0f);  // (the entries n .. n_pad - 1 stay 0)
+  for (int i = 0; i < d.n; ++i) img[i] = scales[d.nscales == 1 ? 0 : i];
+  const bool fast = h->path == DFX_BMM_MFMA && bmm_fast_ok(d, scales) && fast_allowed();
+  DeviceGuard dg(h->device);
+  HIP_TRY(hipMemcpy(h->d_scale, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+  h->route = fast ? 1 : 0;
+  h->scales_set.store(1);
+  set_name(h);
+  return DFX_OK;
+}
+
+int dfx_bmm_submit(dfx_bmm_t *h, const void *a_dev, const void *b_dev, void *c_dev, dfx_stream_t s) {
+  if (!h || !a_dev || !b_dev || !c_dev) return fail(DFX_ERR_INVALID, "bmm_submit: null argument");
+  if (!h->scales_set.load()) return fail(DFX_ERR_STATE, "bmm_submit: dfx_bmm_set_scales not called");
+  const dfx_bmm_desc &d = h->d;
+  const unsigned esz = (unsigned)bmm_dt_size(d.dst_dt);
+  const uintptr_t pa = (uintptr_t)a_dev, pb = (uintptr_t)b_dev, pc = (uintptr_t)c_dev;
+  if (pc % esz) return fail(DFX_ERR_INVALID, "bmm_submit: c is not aligned to its element");
+  const unsigned long long abytes = bmm_a_elems(d), bbytes = bmm_b_elems(d), cbytes = bmm_c_elems(d) * esz;
+  if (bmm_overlap(pc, cbytes, pa, abytes) || bmm_overlap(pc, cbytes, pb, bbytes))
+    return fail(DFX_ERR_INVALID, "bmm_submit: c overlaps a or b");
+  DeviceGuard dg(h->device);
+  // 16-byte loads need aligned operands: others take the generic kernel for this submit, as resize and head do
+  const int path = (pa | pb) % 16 == 0 ? h->path : DFX_BMM_GENERIC;
+  BmmArgs a = h->args;  // per launch: concurrent submits on several streams are independent
+  a.a = (const unsigned char *)a_dev;
+  a.b = (const signed char *)b_dev;
+  a.c = (unsigned char *)c_dev;
+  a.c_vec = pc % (4 * esz) == 0 && d.ldc % 4 == 0 && d.c_s0 % 4 == 0 && d.c_s1 % 4 == 0;
+  const int rc = path == DFX_BMM_MFMA ? launch_bmm_mfma(a, h->grid[path], (hipStream_t)s, h->route != 0)
+                                      : launch_bmm_generic(a, h->grid[path], (hipStream_t)s);
+  if (rc != 0) return fail(DFX_ERR_UNSUPPORTED, "bmm_submit: no kernel instance for this op");
+  HIP_TRY(hipGetLastError());
+  g_launches[path].fetch_add(1, std::memory_order_relaxed);
+  return DFX_OK;
+}
+
+// test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
+int dfx_debug_bmm_launches(int64_t out[2]) {
+  if (!out) return fail(DFX_ERR_INVALID, "debug_bmm_launches: null argument");
+  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
+  return DFX_OK;
+}
+
+// test hook: the requant route the last dfx_bmm_set_scales proved (numbering of dfx_debug_conv_requant)
+int dfx_debug_bmm_requant(const dfx_bmm_t *h, int32_t out[1]) {
+  if (!h || !out) return fail(DFX_ERR_INVALID, "bmm_requant: null argument");
+  if (!h->scales_set.load()) return fail(DFX_ERR_STATE, "bmm_requant: dfx_bmm_set_scales not called");
+  out[0] = h->route;
+  return DFX_OK;
+}
+
+int dfx_bmm_query(const dfx_bmm_t *h, dfx_bmm_info *info) {
+  if (!h || !info) return fail(DFX_ERR_INVALID, "bmm_query: null argument");
+  memset(info, 0, sizeof(*info));
+  info->path = h->path;
+  info->grid = h->grid[h->path];
+  info->block = BMM_THREADS;
+  info->lds_bytes = bmm_lds_bytes(h->d, h->path);
+  info->device = h->device;
+  info->algorithmic_ops = bmm_algorithmic_ops(h->d);
+  info->algorithmic_bytes = bmm_algorithmic_bytes(h->d);
+  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
+  return DFX_OK;
+}
+
+int dfx_bmm_destroy(dfx_bmm_t *h) {
+  if (!h) return DFX_OK;
+  DeviceGuard dg(h->device);
+  (void)hipFree(h->d_scale);
+  delete h;
+  return DFX_OK;
+}
+
+}  // extern "C"

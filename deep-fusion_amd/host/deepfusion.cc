@@ -2908,6 +2908,74 @@ private:
   detail::op_state st_;
 };
 
+// ---- batched int8 matrix product (dfx_bmm_*): C[g] = requant(A[g] . B[g](^T)) over matrices that lie in three tensors at the
+// strides of matmul_shape.  a and b are registered as reads, c as a write (op_state).  One handle on one device:
+// DEEPFUSION_DEVICES does not shard this op (a head-sliced operand is not batch-major). ----
+class op_matmul : public op {
+public:
+  op_matmul(memory *a, memory *b, memory *c, const matmul_shape &sh, const std::vector<float> &scales, bool relu, round_mode rm)
+      : a_(a), b_(b), c_(c), h_(nullptr) {
+    if (!a_ || !b_ || !c_) error_and_exit("Init MatMul op failed! (null tensor)");
+    dfx_bmm_desc d;
+    memset(&d, 0, sizeof(d));
+    d.batch0 = sh.batch0; d.batch1 = sh.batch1; d.m = sh.m; d.n = sh.n; d.k = sh.k; d.trans_b = sh.trans_b ? 1 : 0;
+    d.a_dt = to_dfx_dtype(a_->data_type()); d.b_dt = to_dfx_dtype(b_->data_type()); d.dst_dt = to_dfx_dtype(c_->data_type());
+    d.relu = relu ? 1 : 0;
+    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.nscales = (int)scales.size();
+    d.force_path = -1;
+    d.a_s0 = sh.a_s0; d.a_s1 = sh.a_s1; d.lda = sh.lda;
+    d.b_s0 = sh.b_s0; d.b_s1 = sh.b_s1; d.ldb = sh.ldb;
+    d.c_s0 = sh.c_s0; d.c_s1 = sh.c_s1; d.ldc = sh.ldc;
+    if (scales.empty()) error_and_exit("Init MatMul op failed! (scales must hold 1 or n floats)");
+    if (dfx_bmm_create(&d, &h_) != DFX_OK) error_and_exit("Init MatMul op failed! (%s)", dfx_last_error());
+    // every matrix within its tensor: the last row of a and of b up to its valid columns rounded up to 16, which is what
+    // the library may read (the create above has found the sizes positive and the strides non-negative)
+    const long long brows = sh.trans_b ? sh.n : sh.k, bcols = sh.trans_b ? sh.k : sh.n;
+    const long long a_row = std::min<long long>(sh.lda, ((long long)sh.k + 15) / 16 * 16), b_row = std::min<long long>(sh.ldb, (bcols + 15) / 16 * 16);
+    const long long a_end = (sh.batch0 - 1) * sh.a_s0 + (sh.batch1 - 1) * sh.a_s1 + (long long)(sh.m - 1) * sh.lda + a_row;
+    const long long b_end = (sh.batch0 - 1) * sh.b_s0 + (sh.batch1 - 1) * sh.b_s1 + (brows - 1) * sh.ldb + b_row;
+    const long long c_end = (sh.batch0 - 1) * sh.c_s0 + (sh.batch1 - 1) * sh.c_s1 + (long long)(sh.m - 1) * sh.ldc + sh.n;
+    if (a_end > (long long)a_->size() || b_end > (long long)b_->size() || c_end > (long long)c_->size())
+      error_and_exit("Init MatMul op failed! (a matrix reaches beyond its tensor)");
+    if (dfx_bmm_set_scales(h_, scales.data()) != DFX_OK) error_and_exit("Init MatMul op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_matmul() override {
+    st_.retire(*c_);
+    dfx_bmm_destroy(h_);
+  }
+
+  void submit() override {
+    run(true);
+    st_.fetch_out(*c_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*c_);
+  }
+  void submit_async() override { run(false); }
+  void wait() override {
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*c_);
+  }
+
+protected:
+  void infer() override { run(true); }
+  void run(bool sync_host) {
+    const void *a = st_.sync_in(*a_, sync_host);
+    const void *b = st_.sync_in(*b_, sync_host);
+    void *c = st_.device_out(*c_);
+    st_.profile_begin();
+    check_dfx(dfx_bmm_submit(h_, a, b, c, st_.stream), "bmm submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "matmul"; }
+
+private:
+  memory *a_, *b_, *c_;
+  dfx_bmm_t *h_;
+  detail::op_state st_;
+};
+
 // ---- squeeze-and-excitation (dfx_se_*) and, with no weights, the global average pooling it starts with.  The two weight
 // tensors are plain oihw {cr, c, 1, 1} and {c, cr, 1, 1}; dst may be src.  Weight hashing and batch sharding are
 // op_depthwise_conv's: the op is per image, so shards are independent. ----
@@ -3358,6 +3426,17 @@ std::unique_ptr<op> top_k(const std::unique_ptr<memory> &src, std::unique_ptr<me
 std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &dst,
                             float out_scale, int c_valid) {
   return std::unique_ptr<op>(new op_head(src, dst, nullptr, DFX_HEAD_SOFTMAX, 0, c_valid, &table, out_scale));
+}
+
+std::array<long long, 3> attention_strides(int bs, int heads, int t, int d, long long ld) {
+  if (ld == 0) ld = (long long)heads * d;
+  if (bs < 1 || heads < 1 || t < 1 || d < 1 || ld < (long long)heads * d) error_and_exit("attention_strides: bad shape");
+  return std::array<long long, 3>{{(long long)t * ld, (long long)d, ld}};
+}
+
+std::unique_ptr<op> matmul(const std::unique_ptr<memory> &a, const std::unique_ptr<memory> &b, std::unique_ptr<memory> &c,
+                           const matmul_shape &shape, const std::vector<float> &scales, bool relu, round_mode rm) {
+  return std::unique_ptr<op>(new op_matmul(a.get(), b.get(), c.get(), shape, scales, relu, rm));
 }
 
 std::unique_ptr<op> select_top_k(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, memory *dst_val,

@@ -591,4 +591,34 @@ int dfx_roialign_submit(dfx_roialign_t *hv, const dfx_roialign_io *io, dfx_strea
 }
 int dfx_roialign_destroy(dfx_roialign_t *h) { return destroy_handle(h); }
 
+// ---- batched matrix product: reads A (`src[0]`) and B (`src[1]`), writes C (`dst`); byte ranges from the first to behind the
+// last valid element of each operand, as dfx_bmm_submit's overlap check takes them ----
+int dfx_bmm_create(const dfx_bmm_desc *d, dfx_bmm_t **out) {
+  if (!d || !out || d->batch0 < 1 || d->batch1 < 1 || d->m < 1 || d->n < 1 || d->k < 1 || d->lda < d->k || d->ldc < d->n ||
+      d->ldb < (d->trans_b ? d->k : d->n))
+    return fail(DFX_ERR_INVALID, "bad bmm descriptor");
+  handle *h = new_handle("bmm");
+  const size_t b0 = (size_t)d->batch0 - 1, b1 = (size_t)d->batch1 - 1;
+  const size_t brows = (size_t)(d->trans_b ? d->n : d->k), bcols = (size_t)(d->trans_b ? d->k : d->n);
+  h->src.push_back(b0 * d->a_s0 + b1 * d->a_s1 + ((size_t)d->m - 1) * d->lda + d->k);
+  h->src.push_back(b0 * d->b_s0 + b1 * d->b_s1 + (brows - 1) * d->ldb + bcols);
+  h->dst = (b0 * d->c_s0 + b1 * d->c_s1 + ((size_t)d->m - 1) * d->ldc + d->n) * dt_size(d->dst_dt);
+  *out = reinterpret_cast<dfx_bmm_t *>(h);
+  return DFX_OK;
+}
+int dfx_bmm_set_scales(dfx_bmm_t *h, const float *) { return set_weights(h, "dfx_bmm_set_scales", {}); }
+int dfx_bmm_submit(dfx_bmm_t *hv, const void *a, const void *b, void *c, dfx_stream_t s) {
+  handle *h = reinterpret_cast<handle *>(hv);
+  if (!h) return fail(DFX_ERR_INVALID, "null handle");
+  if (!stream_ok(s, "dfx_bmm_submit")) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_bmm_submit", {}};
+  add_range(r, a, h->src[0], false);
+  add_range(r, b, h->src[1], false);
+  add_range(r, c, h->dst, true);
+  r.ranges.push_back({h->packed, 0, 1, false});
+  g_trace.push_back(r);
+  return DFX_OK;
+}
+int dfx_bmm_destroy(dfx_bmm_t *h) { return destroy_handle(h); }
+
 }  // extern "C"

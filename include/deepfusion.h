@@ -441,6 +441,33 @@ std::unique_ptr<op> top_k(const std::unique_ptr<memory> &src, std::unique_ptr<me
 std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array<uint32_t, 256> &table,
                             std::unique_ptr<memory> &dst, float out_scale = 255.f, int c_valid = 0);
 
+// ---- extension: batched int8 matrix product of two DEVICE tensors (dfx_bmm_* in dfx.h): the multiply whose second operand is
+// not a weight -- Q.K^T and P.V of an attention / non-local block, a correlation layer.  a (u8 / s8), b (s8) and c (u8 / s8 /
+// s32 / f32) are tensors of any dims; `shape` says where the matrices lie in them, in ELEMENTS from each tensor's first:
+// element (g = b0 * batch1 + b1, row, col) of A is at b0 * a_s0 + b1 * a_s1 + row * lda + col, likewise for B and C.
+//   trans_b: B is {n, k} (Q.K^T);  else B is {k, n} (P.V)
+//   c = store(relu?(float(sum_k a * b) * scale[n or 0]))   inner_product()'s arithmetic without a bias; scales: 1 or n floats
+// attention_strides(bs, heads, t, d) gives {s0, s1, ld} of the per-head {t, d} matrices of an nhwc {bs, heads * d, t, 1}
+// tensor, so that the heads are read, and the context is written back interleaved, without a copy.  Pad columns (k .. lda-1
+// of A, behind B's valid columns) never take part and elements n .. ldc-1 of a row of c are not written: softmax()'s dst with
+// C' = 48 for 37 tokens is `a` as it stands.  Every operand's last matrix must lie within its tensor, the last row of a and of b up to
+// its valid columns rounded up to 16; c's elements must not overlap one another, a or b.  Bit-exact and the same on every kernel
+// path.  submit / submit_async / wait are softmax()'s; the op runs on ONE device (DEEPFUSION_DEVICES does not shard it: its
+// operands need not be batch-major), and like roi_align() it sends nothing to the host but on submit().
+// ON THE HOST the elements of c that the op does not write -- n .. ldc-1 of a row, whatever lies between the matrices -- are
+// UNDEFINED after submit() / download(): the kernel leaves them alone in c's DEVICE copy, which is not refreshed from the host
+// before the op runs, and the whole tensor is copied back (softmax()'s pad channels behave the same).  Bytes that an earlier
+// op wrote into the same device copy -- other heads of an interleaved context -- are kept. ----
+struct matmul_shape {
+  int batch0, batch1, m, n, k;
+  bool trans_b;
+  long long a_s0, a_s1, lda, b_s0, b_s1, ldb, c_s0, c_s1, ldc;
+};
+std::array<long long, 3> attention_strides(int bs, int heads, int t, int d, long long ld = 0 /* heads * d */);
+std::unique_ptr<op> matmul(const std::unique_ptr<memory> &a, const std::unique_ptr<memory> &b, std::unique_ptr<memory> &c,
+                           const matmul_shape &shape, const std::vector<float> &scales, bool relu = false,
+                           round_mode rm = round_mode::nearest);
+
 // ---- extension: image-wide top-K with peak filter (dfx_select_* in dfx.h): what a detector does behind its last conv,
 // without leaving the device.  src: an nhwc score tensor {bs, C, h, w} of u8 / s8 (a conv()'s heat map); the first c_valid
 // channels of a pixel take part (0: all).  Per image, the k (1 .. 4096) best elements that are >= min_val and, with peak3,

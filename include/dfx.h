@@ -1043,6 +1043,83 @@ typedef struct dfx_roialign_info {
 } dfx_roialign_info;
 typedef struct dfx_roialign dfx_roialign_t;
 
+/* ---- batched int8 matrix product over two DEVICE tensors: the one multiply whose second operand is not a weight the host
+ *      packs -- Q.K^T and P.V of a non-local / self-attention block (ResNet / Mask R-CNN non-local, DANet / OCRNet / CCNet
+ *      context modules, DETR and ViT-hybrid / MobileViT / Swin encoders) and correlation (cost-volume) layers.  With
+ *      dfx_head's table softmax between two of them an int8 attention block runs on the device:
+ *      s8 x s8 -> s8 logits, softmax -> u8, u8 x s8 -> s8.
+ *        g = b0 * batch1 + b1,   0 <= b0 < batch0, 0 <= b1 < batch1
+ *        acc[g,m,n] = sum over k of A[g,m,k] * B[g,n,k]      (trans_b = 1, B is {N,K}, k contiguous:  Q.K^T)
+ *                   = sum over k of A[g,m,k] * B[g,k,n]      (trans_b = 0, B is {K,N}, n contiguous:  P.V)
+ *        f = float(acc);  f = f * scale[n or 0];  ReLU (asked for, or dst is u8): f = (0 > f) ? 0 : f
+ *        C[g,m,n] = store(f, dst_dt, round_mode)
+ *      OPERANDS.  A u8 or s8; B s8 (u8 B: DFX_ERR_UNSUPPORTED, not built); C u8 / s8 / s32 / f32.
+ *      ADDRESSING, in elements, per operand: element (g, row, col) of A is at a + b0*a_s0 + b1*a_s1 + row*lda + col; B uses
+ *      b_s0, b_s1, ldb and C uses c_s0, c_s1, ldc in the same way.  The heads of a {bs, T, heads*d} NHWC tensor are read
+ *      without a copy with s0 = T*heads*d, s1 = d, ld = heads*d, and the context is written back interleaved in that shape.
+ *      A batch stride of 0 on A or B broadcasts that operand; on C it is never allowed (see the overlap rule below).
+ *      PAD COLUMNS.  Columns beyond the valid extent of a row NEVER take part, whatever they hold: K .. lda-1 of A,
+ *      K .. ldb-1 of B (trans_b = 1), N .. ldb-1 of B (trans_b = 0); elements N .. ldc-1 of a C row are NOT written
+ *      (dfx_head's rule: a softmax output with dst_ld = 208 for 197 tokens is A as it stands).  Every row of A and B is
+ *      readable up to its valid columns rounded up to 16, which the leading dimension admits on the MFMA path (that kernel
+ *      reads whole 16-byte pieces and masks them).
+ *      ARITHMETIC.  dfx_fc's, word for word, without a bias: exact s32 accumulation (1 <= K <= 65025), requant() /
+ *      gc_quarter with bias +0.0f (the identity: float(int) is never -0), a separately rounded multiply, the x86
+ *      conversion and saturations of dfx_device.cuh.
+ *      REQUANT ROUTE.  The op never sees its operands on the host, so dfx_bmm_set_scales proves the route from the shape
+ *      alone: "fast" when the round mode is nearest, DFX_NO_FAST is not set, every scale is finite and
+ *      bound * |scale| <= 2^30 with bound = 255*128*K (u8 A) or 128*128*K (s8 A); otherwise "exact".  The generic kernel is
+ *      always exact.  Both routes give the same bits wherever "fast" is allowed.
+ *      Not built: u8 B, an additive mask / relative-position bias on the logits, softmax fused between the two products
+ *      (flash-style, one launch), split-K for tiny G*M*N, a bias, K > 65025, s32 / f32 operands.
+ *      Parity unpinned: the reference has no such op. ---- */
+typedef struct dfx_bmm_desc {
+  int32_t batch0, batch1;      /* >= 1; G = batch0 * batch1 matrices */
+  int32_t m, n, k;             /* >= 1; m, n <= 2^31 - 32; k <= 65025 */
+  int32_t trans_b;             /* 1: B is {N,K} (Q.K^T);  0: B is {K,N} (P.V) */
+  int32_t a_dt;                /* DFX_U8 | DFX_S8 */
+  int32_t b_dt;                /* DFX_S8 (DFX_U8: DFX_ERR_UNSUPPORTED) */
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t relu, round_mode;
+  int32_t nscales;             /* 1 or n */
+  int32_t force_path;          /* -1 auto, else DFX_BMM_* (testing) */
+  int64_t a_s0, a_s1, lda;     /* elements; batch strides >= 0 (0 broadcasts), lda >= k */
+  int64_t b_s0, b_s1, ldb;     /* ldb >= k (trans_b = 1) or >= n (trans_b = 0) */
+  int64_t c_s0, c_s1, ldc;     /* ldc >= n; no two elements of C may share an address */
+} dfx_bmm_desc;
+enum {  /* dfx_bmm_info.path */
+  DFX_BMM_MFMA = 0,            /* bmm_mfma_kernel (bmm.cuh): v_mfma_i32_32x32x32_i8, one launch, requant in the epilogue.
+                                  Class: lda, ldb and the batch strides of A and B multiples of 16 elements; a and b 16-byte
+                                  aligned (checked per submit: others take the generic kernel for that submit).  Any M, N, K.
+                                  AUTO RULE: see DFX_BMM_AUTO_NOTE below. */
+  DFX_BMM_GENERIC = 1          /* one thread per C element, grid-stride, any strides and alignment, exact requant.  It
+                                  defines the bits. */
+};
+/* DFX_BMM_AUTO_NOTE: auto takes DFX_BMM_MFMA in its class for M >= 49, N >= 32, K >= 32, G * M * N * K >= 192 * 49 * 49 * 32 and
+ * at least 384 tiles of 32 x 32 (G * ceil(M / 32) * ceil(N / 32)), the smallest of each at which it was measured and won, and
+ * DFX_BMM_GENERIC everywhere else.  On the 12 points of profiles/bmm/bench_bmm.txt (MI355X, buffers in rotation beyond the
+ * Infinity Cache, forced legs alternating, windows of at least 3 ms, median of 5 rounds whose extremes lie within 5 % of it but
+ * for one outlying round at each Swin point; both products of an attention block over head-sliced tensors, s8 out): the MFMA
+ * kernel beats the generic one on all 12 -- ViT-B (heads 12, T 197, d 64) at bs 8 in 10.3 / 11.0 us (Q.K^T / P.V) against 435 / 200
+ * and at bs 64 in 54 / 33 us against 3536 / 1232; a Swin stage (192 windows, T 49, d 32) in 4.9 / 5.6 us against 17.8 / 17.3; a
+ * DETR encoder (bs 2, heads 8, T 850, d 32) in 16.0 / 27.7 us against 643 / 275; a non-local block (T 4096, d 256) at bs 1 in
+ * 42 / 116 us against 5388 / 2083 and at bs 4 in 160 / 123 us against 23898 / 8848: 3.1x to 150x.  Nothing smaller was timed
+ * (M = 1, K < 32, a handful of matrices, a few tiles under a deep K), so those stay on the generic kernel; DFX_BMM_MFMA is
+ * reachable there with force_path and gives the same bits.  Against what a caller had before (profiles/bmm/): 1.27x faster
+ * than dfx_fc on the one batch-1 NT point, 1.8x to 4.3x faster than torch.matmul on f16 copies at the ViT-B, Swin and DETR
+ * Q.K^T points, and SLOWER than torch at DETR P.V (0.97x) and at every non-local point (0.23x to 0.49x of f16 matmul, 0.16x to
+ * 0.70x of torch._int_mm).  What bounds it: DESIGN.md section 4.21 (at best 6 % of the int8 matrix peak and 19 % of the HBM
+ * peak: one 32 x 32 tile per wave re-reads its operands). */
+typedef struct dfx_bmm_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2 * G * M * N * K */
+  uint64_t algorithmic_bytes;  /* the distinct bytes of A, B and C: a broadcast operand counts once */
+  char kernel_name[96];        /* "bmm_mfma<nt,u8,s8> fast": form (nt | nn), A type, dst type, route (after set_scales) */
+} dfx_bmm_info;
+typedef struct dfx_bmm dfx_bmm_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -1523,6 +1600,25 @@ int dfx_roialign_submit(dfx_roialign_t *h, const dfx_roialign_io *io, dfx_stream
 int dfx_roialign_query(const dfx_roialign_t *h, dfx_roialign_info *info);
 int dfx_roialign_destroy(dfx_roialign_t *h);
 
+/* ---- batched int8 matrix product (dfx_bmm_desc above).  The descriptor is validated before anything touches a device, in
+ *      this order: DFX_ERR_INVALID for a non-positive size, m or n above 2^31 - 32, K > 65025, a bad trans_b / dtype / round mode / nscales (1 or n) /
+ *      force_path, lda < K, ldb < (trans_b ? K : N), ldc < N, a negative stride, a C whose elements could overlap -- take the
+ *      (extent, stride) pairs (N,1), (M,ldc), (batch1,c_s1), (batch0,c_s0), drop extents of 1, sort by stride: the first
+ *      stride must be >= 1, each further one >= the previous stride x the previous extent (this accepts the interleaved-heads layout) -- and any
+ *      operand whose index range reaches 2^40 elements; then DFX_ERR_UNSUPPORTED only for a u8 B and for force_path =
+ *      DFX_BMM_MFMA outside that class.  "No HIP device" is reported only for a valid descriptor.
+ *      set_scales: 1 or n host floats, copied; may be called again (not while a submit of the handle is in flight); it
+ *      chooses the requant route (above).  submit: asynchronous on `s`; DFX_ERR_INVALID, with nothing launched, for a null
+ *      pointer, a 4-byte C that is not 4-byte aligned, and a C byte range that overlaps A's or B's; DFX_ERR_STATE before
+ *      set_scales.  ONE launch with its own arguments and no scratch: submits are independent, a handle may be submitted
+ *      from several host threads and on several streams at once (dfx_pool's contract, not dfx_fc's).
+ *      Tuning switch: DFX_BMM_GRID=n caps the grid of either kernel.  No CPU fallback. ---- */
+int dfx_bmm_create(const dfx_bmm_desc *desc, dfx_bmm_t **out);
+int dfx_bmm_set_scales(dfx_bmm_t *h, const float *scales);
+int dfx_bmm_submit(dfx_bmm_t *h, const void *a_dev, const void *b_dev, void *c_dev, dfx_stream_t s);
+int dfx_bmm_query(const dfx_bmm_t *h, dfx_bmm_info *info);
+int dfx_bmm_destroy(dfx_bmm_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -1624,6 +1720,11 @@ int dfx_debug_select_launches(int64_t out[2]);
 int dfx_debug_nms_launches(int64_t out[2]);
 /* the same for dfx_roialign_submit: out[DFX_ROIALIGN_TILE], out[DFX_ROIALIGN_GENERIC] */
 int dfx_debug_roialign_launches(int64_t out[2]);
+/* the same for dfx_bmm_submit: out[DFX_BMM_MFMA], out[DFX_BMM_GENERIC] */
+int dfx_debug_bmm_launches(int64_t out[2]);
+/* the matrix product's one stage as the last dfx_bmm_set_scales proved it, same numbering (0 exact, 1 fast; the generic
+ * path is always exact).  DFX_ERR_STATE before set_scales. */
+int dfx_debug_bmm_requant(const dfx_bmm_t *h, int32_t out[1]);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,7 @@ from .capi import (  # noqa: F401
     ROI_BATCHED, ROI_LIST, ROIALIGN_AUTO, ROIALIGN_TILE, ROIALIGN_GENERIC, RoiAlignDesc, RoiAlignIo, RoiAlignInfo, RoiAlign,
     roialign_launches, roi_level_thresholds,
     BMM_AUTO, BMM_MFMA, BMM_GENERIC, BmmDesc, BmmInfo, MatMul, bmm_launches, attention_strides,
+    ATTN_AUTO, ATTN_FUSED, ATTN_CHAIN, AttnDesc, AttnInfo, Attention, attn_launches,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

@@ -42,6 +42,7 @@ NMS_MAX_N = 4096
 ROI_BATCHED, ROI_LIST = 0, 1
 ROIALIGN_AUTO, ROIALIGN_TILE, ROIALIGN_GENERIC = -1, 0, 1
 BMM_AUTO, BMM_MFMA, BMM_GENERIC = -1, 0, 1
+ATTN_AUTO, ATTN_FUSED, ATTN_CHAIN = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -275,6 +276,19 @@ class BmmInfo(ctypes.Structure):
                 ("kernel_name", ctypes.c_char * 96)]
 
 
+class AttnDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("batch0", "batch1", "tq", "tk", "d", "dv", "q_dt", "k_dt", "v_dt", "dst_dt", "relu",
+                                              "round_mode", "nscales", "force_path")] + \
+               [("prob_scale", ctypes.c_float), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_int64) for n in ("q_s0", "q_s1", "ldq", "k_s0", "k_s1", "ldk", "v_s0", "v_s1", "ldv", "o_s0", "o_s1", "ldo")]
+
+
+class AttnInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device", "route_logits", "route_context")] + \
+               [("scratch_bytes", ctypes.c_uint64), ("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
 class DwPwDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t", "pad_l",
                                              "oc", "dst_dt", "bia0_dt", "bia1_dt", "relu", "round_mode0", "round_mode1",
@@ -488,6 +502,13 @@ def lib():
         "dfx_bmm_destroy": (i32, [vp]),
         "dfx_debug_bmm_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
         "dfx_debug_bmm_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_attn_create": (i32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(vp)]),
+        "dfx_attn_set_table": (i32, [vp, vp]),
+        "dfx_attn_set_scales": (i32, [vp, ctypes.c_float, vp]),
+        "dfx_attn_submit": (i32, [vp, vp, vp, vp, vp, vp]),
+        "dfx_attn_query": (i32, [vp, ctypes.POINTER(AttnInfo)]),
+        "dfx_attn_destroy": (i32, [vp]),
+        "dfx_debug_attn_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -553,6 +574,13 @@ def bmm_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_bmm_launches(v))
     return v[BMM_MFMA], v[BMM_GENERIC]
+
+
+def attn_launches():
+    """(fused, chain): dfx_attn_submit calls of this process that ran on each path (dfx_debug_attn_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_attn_launches(v))
+    return v[ATTN_FUSED], v[ATTN_CHAIN]
 
 
 def attention_strides(bs, heads, t, d, ld=None):
@@ -1312,6 +1340,62 @@ class MatMul(_Handle):
     def submit(self, a_dev, b_dev, c_dev, stream=None):
         """asynchronous; torch CUDA tensors (or raw pointers)"""
         _check(lib().dfx_bmm_submit(self._h, _dev_ptr(a_dev), _dev_ptr(b_dev), _dev_ptr(c_dev), _stream_ptr(stream)))
+
+
+class Attention(_Handle):
+    """dfx_attn_* handle: int8 attention over batch = (batch0, batch1) matrices (include/dfx.h): O[g] = requant(softmax(
+    requant(Q[g] . K[g]^T)) . V[g]), defined as MatMul -> Softmax (u8) -> MatMul and bit-identical to that chain; on the fused
+    path it is one launch with the logits and the probabilities kept on chip.  q_strides / k_strides / v_strides / o_strides
+    are (s0, s1, ld) in elements (None: densely packed; attention_strides() for head-sliced tensors).  Q u8 or s8, K and V s8,
+    O any of the four dtypes.  set_table() and set_scales() first; submit(q, k, v, o)."""
+
+    _OP, _INFO = "dfx_attn", AttnInfo
+
+    def __init__(self, batch, tq, tk, d, dv, q_dtype=np.int8, dst_dtype=np.int8, q_strides=None, k_strides=None, v_strides=None,
+                 o_strides=None, relu=False, rm=ROUND_NEAREST, nscales=1, prob_scale=255.0, k_dtype=np.int8, v_dtype=np.int8,
+                 force_path=ATTN_AUTO, table=None, logit_scale=None, out_scales=None):
+        code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
+        batch0, batch1 = (1, batch) if isinstance(batch, int) else batch
+
+        def dense(rows, cols):
+            return batch1 * rows * cols, rows * cols, cols
+
+        dsc = AttnDesc()
+        dsc.batch0, dsc.batch1, dsc.tq, dsc.tk, dsc.d, dsc.dv = batch0, batch1, tq, tk, d, dv
+        dsc.q_dt, dsc.k_dt, dsc.v_dt, dsc.dst_dt = code(q_dtype), code(k_dtype), code(v_dtype), code(dst_dtype)
+        dsc.relu, dsc.round_mode, dsc.nscales, dsc.force_path = int(relu), rm, nscales, force_path
+        dsc.prob_scale = prob_scale
+        dsc.q_s0, dsc.q_s1, dsc.ldq = dense(tq, d) if q_strides is None else q_strides
+        dsc.k_s0, dsc.k_s1, dsc.ldk = dense(tk, d) if k_strides is None else k_strides
+        dsc.v_s0, dsc.v_s1, dsc.ldv = dense(tk, dv) if v_strides is None else v_strides
+        dsc.o_s0, dsc.o_s1, dsc.ldo = dense(tq, dv) if o_strides is None else o_strides
+        self.desc = dsc
+        self._create(dsc)
+        if table is not None:
+            self.set_table(table)
+        if logit_scale is not None and out_scales is not None:
+            self.set_scales(logit_scale, out_scales)
+
+    def set_table(self, table):
+        """256 uint32 entries (softmax_table(step, tk)); may be called again"""
+        t = np.ascontiguousarray(table, dtype=np.uint32).reshape(-1)
+        assert t.size == 256, t.size
+        _check(lib().dfx_attn_set_table(self._h, _p(t)))
+
+    def set_scales(self, logit_scale, out_scales):
+        """the logits' scale and 1 or dv out scales (the descriptor's nscales); may be called again"""
+        s = np.ascontiguousarray(out_scales, dtype=np.float32).reshape(-1)
+        assert s.size == self.desc.nscales, (s.size, self.desc.nscales)
+        _check(lib().dfx_attn_set_scales(self._h, ctypes.c_float(float(np.float32(logit_scale))), _p(s)))
+
+    def requant(self):
+        """(logits route, context route) as the last set_scales proved them; (-1, -1) before it"""
+        i = self.info()
+        return i.route_logits, i.route_context
+
+    def submit(self, q_dev, k_dev, v_dev, o_dev, stream=None):
+        """asynchronous; torch CUDA tensors (or raw pointers)"""
+        _check(lib().dfx_attn_submit(self._h, _dev_ptr(q_dev), _dev_ptr(k_dev), _dev_ptr(v_dev), _dev_ptr(o_dev), _stream_ptr(stream)))
 
 
 class DwPwConv(_Handle):

@@ -1,0 +1,304 @@
+// attn_api.hip -- host side of the fused int8 attention (dfx_attn_* of include/dfx.h): descriptor validation, the path, the
+// LDS plan and the grid (all planned in attn_plan.h), the chain of the three existing ops over scratch the handle owns (made
+// at create where it is the plan, at the first fallback submit on a fused handle) and the order of its submits, the device copies of the table and the out scales with both requant routes proved from the
+// shape, the overlap check and the choice of the path per submit, launches.  The kernel is in attn.cuh / attn.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "dfx_internal.h"
+#include "attn.cuh"
+#include "attn_plan.h"
+#include "requant_host.h"
+
+namespace dfx {
+int launch_attn_fused(const AttnArgs &a, int grid, int lds, hipStream_t s, int mode, bool fast_logits, bool fast_context);
+}
+using namespace dfx;
+
+struct dfx_attn {
+  dfx_attn_desc d;
+  int device = 0;
+  int path = DFX_ATTN_CHAIN;
+  bool fused_ok = false;       // the descriptor is in the fused kernel's class and the instances admit its LDS
+  int grid = 0, lds = 0;       // of the fused kernel
+  AttnArgs args = {};          // everything but q / k / v / o; copied per launch
+  unsigned int *d_table = nullptr;
+  float *d_oscale = nullptr;   // [dv rounded up to 32]
+  int dv_pad = 0;
+  std::atomic<int> table_set{0}, scales_set{0};
+  int route_l = 0, route_o = 0;  // 0 exact, 1 fast
+  // the chain: the three ops the attention is defined by, L and P in one allocation.  Made at create where the chain is the
+  // plan; on a fused handle at the first submit that falls back (ensure_chain, under order.mu), from the host copies below
+  dfx_bmm_t *bmm_l = nullptr, *bmm_o = nullptr;
+  dfx_head_t *head = nullptr;
+  unsigned char *scratch = nullptr;
+  std::atomic<int> chain_ready{0};
+  uint32_t table[256] = {};
+  float logit_scale = 0.0f;
+  std::vector<float> out_scales;
+  TwoLaunchOrder order;
+  char kernel_name[96] = "";
+};
+
+namespace {
+
+// submits since the library was loaded, by the path that ran; process-wide (dfx_debug_attn_launches)
+std::atomic<long long> g_launches[2];
+
+long long grid_cap() {
+  const char *e = tuning_value("DFX_ATTN_GRID");  // testing aid
+  return e ? std::max(1ll, atoll(e)) : 0;
+}
+
+void set_name(dfx_attn *h) {
+  const dfx_attn_desc &d = h->d;
+  const char *which = h->path == DFX_ATTN_FUSED ? "attn_fused" : "attn_chain";
+  if (!h->scales_set.load())
+    snprintf(h->kernel_name, sizeof(h->kernel_name), "%s<%s,%s> (no scales)", which, dt_name(d.q_dt), dt_name(d.dst_dt));
+  else
+    snprintf(h->kernel_name, sizeof(h->kernel_name), "%s<%s,%s> %s/%s", which, dt_name(d.q_dt), dt_name(d.dst_dt),
+             h->route_l ? "fast" : "exact", h->route_o ? "fast" : "exact");
+}
+
+void drop_chain(dfx_attn *h) {
+  (void)dfx_bmm_destroy(h->bmm_l);
+  (void)dfx_bmm_destroy(h->bmm_o);
+  (void)dfx_head_destroy(h->head);
+  (void)hipFree(h->scratch);
+  h->bmm_l = h->bmm_o = nullptr;
+  h->head = nullptr;
+  h->scratch = nullptr;
+}
+
+// the three ops and the scratch for L and P, with the table and the scales the handle has been given so far.  At create, or
+// with order.mu held.  (attn_validate has found the three descriptors valid: tools/attn_plan_check holds it to that.)
+int ensure_chain(dfx_attn *h) {
+  if (h->chain_ready.load()) return DFX_OK;
+  const dfx_attn_desc &d = h->d;
+  const dfx_bmm_desc bl = attn_bmm_logits(d), bo = attn_bmm_context(d);
+  const dfx_head_desc hd = attn_head_softmax(d);
+  int rc;
+  if ((rc = dfx_bmm_create(&bl, &h->bmm_l)) != DFX_OK || (rc = dfx_head_create(&hd, &h->head)) != DFX_OK ||
+      (rc = dfx_bmm_create(&bo, &h->bmm_o)) != DFX_OK) {
+    drop_chain(h);
+    return rc;  // (the op that failed has recorded why)
+  }
+  const hipError_t e = hipMalloc((void **)&h->scratch, (size_t)attn_scratch_bytes(d));
+  if (e != hipSuccess) {
+    drop_chain(h);
+    return fail(DFX_ERR_HIP, "attn: scratch for the logits and the probabilities: %s", hipGetErrorString(e));
+  }
+  if (h->table_set.load()) rc = dfx_head_set_table(h->head, h->table);
+  if (rc == DFX_OK && h->scales_set.load()) rc = dfx_bmm_set_scales(h->bmm_l, &h->logit_scale);
+  if (rc == DFX_OK && h->scales_set.load()) rc = dfx_bmm_set_scales(h->bmm_o, h->out_scales.data());
+  if (rc != DFX_OK) {
+    drop_chain(h);
+    return rc;
+  }
+  h->chain_ready.store(1);
+  return DFX_OK;
+}
+
+void release(dfx_attn *h) {
+  drop_chain(h);
+  (void)hipFree(h->d_table);
+  (void)hipFree(h->d_oscale);
+  h->order.destroy();
+  delete h;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dfx_attn_create(const dfx_attn_desc *desc, dfx_attn_t **out) {
+  if (!desc || !out) return fail(DFX_ERR_INVALID, "attn_create: null argument");
+  *out = nullptr;
+  const dfx_attn_desc &d = *desc;
+  const char *why = "";
+  int rc = attn_validate(d, &why);
+  if (rc) return fail(rc, "attn: %s", why);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(DFX_ERR_NO_DEVICE, "attn_create: no HIP device (this library has no CPU path)");
+  dfx_attn *h = new (std::nothrow) dfx_attn();
+  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
+  h->d = d;
+  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
+    release(h);
+    return fail(DFX_ERR_HIP, "attn_create: cannot query the device");
+  }
+  const int cus = std::max(1, prop.multiProcessorCount);
+  // AUTO RULE (include/dfx.h DFX_ATTN_AUTO_NOTE)
+  h->path = attn_path(d);
+  h->fused_ok = attn_fused_class(d);
+  h->grid = attn_grid(d, cus, grid_cap());
+  h->lds = (int)std::min<long long>(attn_lds_bytes(d), ATTN_LDS_MAX);
+  h->dv_pad = (int)(((long long)d.dv + 31) / 32 * 32);
+  // the chain where it is the plan; a fused handle makes it at the first submit that falls back (a misaligned q, k or v),
+  // so that the fused path has no scratch in HBM at all
+  if (h->path == DFX_ATTN_CHAIN && (rc = ensure_chain(h)) != DFX_OK) {
+    release(h);
+    return rc;
+  }
+  hipError_t e = hipMalloc((void **)&h->d_table, HEAD_TABLE_BYTES);
+  if (e == hipSuccess) e = hipMalloc((void **)&h->d_oscale, (size_t)h->dv_pad * sizeof(float));
+  if (e == hipSuccess) e = h->order.create();
+  if (e != hipSuccess) {
+    release(h);
+    return fail(DFX_ERR_HIP, "attn_create: table, scales: %s", hipGetErrorString(e));
+  }
+  AttnArgs &a = h->args;
+  a.table = h->d_table;
+  a.oscale = h->d_oscale;
+  a.prob_scale = d.prob_scale;
+  a.q_s0 = d.q_s0; a.q_s1 = d.q_s1; a.ldq = d.ldq;
+  a.k_s0 = d.k_s0; a.k_s1 = d.k_s1; a.ldk = d.ldk;
+  a.v_s0 = d.v_s0; a.v_s1 = d.v_s1; a.ldv = d.ldv;
+  a.o_s0 = d.o_s0; a.o_s1 = d.o_s1; a.ldo = d.ldo;
+  a.batch1 = d.batch1; a.tq = d.tq; a.tk = d.tk; a.d = d.d; a.dv = d.dv;
+  a.q_u8 = d.q_dt == DFX_U8; a.dst_dt = d.dst_dt;
+  a.relu = (d.relu || d.dst_dt == DFX_U8) ? 1 : 0; a.rm = d.round_mode;
+  a.mt = (int)(((long long)d.tq + ATTN_STRIP - 1) / ATTN_STRIP);
+  a.strips = attn_strips(d);
+  a.pitch = (int)attn_pitch(d);
+  a.vtiles = (int)attn_vtiles(d);  // (dv <= 2^31 - 32)
+  a.kparts = attn_kparts(d);
+  if (h->fused_ok) {  // more than 64 KiB of LDS is dynamic and has to be admitted per instance
+    for (int r = 0; r < 4; ++r) {
+      const int rc2 = launch_attn_fused(a, 0, h->lds, nullptr, 1, (r & 1) != 0, (r & 2) != 0);
+      if (rc2 != 0) {
+        (void)hipGetLastError();
+        release(h);
+        return fail(DFX_ERR_HIP, "attn_create: the fused kernel does not admit %d bytes of LDS", h->lds);
+      }
+    }
+  }
+  set_name(h);
+  *out = h;
+  return DFX_OK;
+}
+
+int dfx_attn_set_table(dfx_attn_t *h, const uint32_t *table256) {
+  if (!h || !table256) return fail(DFX_ERR_INVALID, "attn_set_table: null argument");
+  const char *why = "";
+  const int rc = head_table_ok(table256, h->d.tk, &why);
+  if (rc) return fail(rc, "attn_set_table: %s", why);
+  std::lock_guard<std::mutex> lk(h->order.mu);
+  if (h->chain_ready.load()) {
+    const int rc2 = dfx_head_set_table(h->head, table256);
+    if (rc2) return rc2;
+  }
+  DeviceGuard dg(h->device);
+  HIP_TRY(hipMemcpy(h->d_table, table256, HEAD_TABLE_BYTES, hipMemcpyHostToDevice));
+  memcpy(h->table, table256, sizeof(h->table));
+  h->table_set.store(1);
+  return DFX_OK;
+}
+
+int dfx_attn_set_scales(dfx_attn_t *h, float logit_scale, const float *out_scales) {
+  if (!h || !out_scales) return fail(DFX_ERR_INVALID, "attn_set_scales: null argument");
+  const dfx_attn_desc &d = h->d;
+  std::lock_guard<std::mutex> lk(h->order.mu);
+  if (h->chain_ready.load()) {
+    int rc = dfx_bmm_set_scales(h->bmm_l, &logit_scale);
+    if (rc == DFX_OK) rc = dfx_bmm_set_scales(h->bmm_o, out_scales);
+    if (rc) return rc;
+  }
+  std::vector<float> img((size_t)h->dv_pad, 0.0f);  // (the entries dv .. dv_pad - 1 stay 0)
+  for (int i = 0; i < d.dv; ++i) img[i] = out_scales[d.nscales == 1 ? 0 : i];
+  DeviceGuard dg(h->device);
+  HIP_TRY(hipMemcpy(h->d_oscale, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+  h->args.logit_scale = logit_scale;
+  h->logit_scale = logit_scale;
+  h->out_scales.assign(out_scales, out_scales + d.nscales);
+  h->route_l = attn_fast_logits(d, logit_scale) && fast_allowed() ? 1 : 0;
+  h->route_o = attn_fast_context(d, out_scales) && fast_allowed() ? 1 : 0;
+  h->scales_set.store(1);
+  set_name(h);
+  return DFX_OK;
+}
+
+int dfx_attn_submit(dfx_attn_t *h, const void *q_dev, const void *k_dev, const void *v_dev, void *o_dev, dfx_stream_t s) {
+  if (!h || !q_dev || !k_dev || !v_dev || !o_dev) return fail(DFX_ERR_INVALID, "attn_submit: null argument");
+  if (!h->table_set.load()) return fail(DFX_ERR_STATE, "attn_submit: dfx_attn_set_table not called");
+  if (!h->scales_set.load()) return fail(DFX_ERR_STATE, "attn_submit: dfx_attn_set_scales not called");
+  const dfx_attn_desc &d = h->d;
+  const unsigned esz = (unsigned)bmm_dt_size(d.dst_dt);
+  const uintptr_t pq = (uintptr_t)q_dev, pk = (uintptr_t)k_dev, pv = (uintptr_t)v_dev, po = (uintptr_t)o_dev;
+  if (po % esz) return fail(DFX_ERR_INVALID, "attn_submit: o is not aligned to its element");
+  const dfx_bmm_desc bl = attn_bmm_logits(d), bo = attn_bmm_context(d);
+  const unsigned long long qbytes = bmm_a_elems(bl), kbytes = bmm_b_elems(bl), vbytes = bmm_b_elems(bo), obytes = bmm_c_elems(bo) * esz;
+  if (bmm_overlap(po, obytes, pq, qbytes) || bmm_overlap(po, obytes, pk, kbytes) || bmm_overlap(po, obytes, pv, vbytes))
+    return fail(DFX_ERR_INVALID, "attn_submit: o overlaps q, k or v");
+  DeviceGuard dg(h->device);
+  // 16-byte loads need aligned operands: others take the chain for this submit
+  const int path = h->path == DFX_ATTN_FUSED && h->fused_ok && (pq | pk | pv) % 16 == 0 ? DFX_ATTN_FUSED : DFX_ATTN_CHAIN;
+  if (path == DFX_ATTN_FUSED) {
+    AttnArgs a = h->args;  // per launch: concurrent submits on several streams are independent
+    a.q = (const unsigned char *)q_dev;
+    a.k = (const signed char *)k_dev;
+    a.v = (const signed char *)v_dev;
+    a.o = (unsigned char *)o_dev;
+    a.o_vec = po % (4 * esz) == 0 && d.ldo % 4 == 0 && d.o_s0 % 4 == 0 && d.o_s1 % 4 == 0;
+    if (launch_attn_fused(a, h->grid, h->lds, (hipStream_t)s, 0, h->route_l != 0, h->route_o != 0) != 0)
+      return fail(DFX_ERR_UNSUPPORTED, "attn_submit: no kernel instance for this op");
+    HIP_TRY(hipGetLastError());
+  } else {
+    // L and P are the handle's: chain submits take turns, on the host (mu) and on the device (TwoLaunchOrder)
+    std::lock_guard<std::mutex> lk(h->order.mu);
+    int rc = ensure_chain(h);
+    if (rc) return rc;
+    unsigned char *const l_dev = h->scratch, *const p_dev = h->scratch + attn_scratch_bytes(d) / 2;
+    rc = h->order.enter((hipStream_t)s);
+    if (rc == DFX_OK) rc = dfx_bmm_submit(h->bmm_l, q_dev, k_dev, l_dev, s);
+    if (rc == DFX_OK) rc = dfx_head_submit(h->head, l_dev, p_dev, nullptr, s);
+    if (rc == DFX_OK) rc = dfx_bmm_submit(h->bmm_o, p_dev, v_dev, o_dev, s);
+    if (rc == DFX_OK) rc = h->order.leave((hipStream_t)s);
+    if (rc) return rc;
+  }
+  g_launches[path].fetch_add(1, std::memory_order_relaxed);
+  return DFX_OK;
+}
+
+// test hook: how many submits have run on each path so far (shows the per-submit fallback, which query cannot)
+int dfx_debug_attn_launches(int64_t out[2]) {
+  if (!out) return fail(DFX_ERR_INVALID, "debug_attn_launches: null argument");
+  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
+  return DFX_OK;
+}
+
+int dfx_attn_query(const dfx_attn_t *h, dfx_attn_info *info) {
+  if (!h || !info) return fail(DFX_ERR_INVALID, "attn_query: null argument");
+  memset(info, 0, sizeof(*info));
+  const bool fused = h->path == DFX_ATTN_FUSED;
+  info->path = h->path;
+  info->grid = fused ? h->grid : 0;
+  info->block = fused ? ATTN_THREADS : 0;
+  info->lds_bytes = fused ? h->lds : 0;
+  info->device = h->device;
+  info->route_logits = h->scales_set.load() ? h->route_l : -1;
+  info->route_context = h->scales_set.load() ? h->route_o : -1;
+  info->scratch_bytes = h->chain_ready.load() ? attn_scratch_bytes(h->d) : 0;
+  info->algorithmic_ops = attn_algorithmic_ops(h->d);
+  info->algorithmic_bytes = attn_algorithmic_bytes(h->d);
+  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
+  return DFX_OK;
+}
+
+int dfx_attn_destroy(dfx_attn_t *h) {
+  if (!h) return DFX_OK;
+  DeviceGuard dg(h->device);
+  release(h);
+  return DFX_OK;
+}
+
+}  // extern "C"

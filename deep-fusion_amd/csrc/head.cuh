@@ -59,6 +59,48 @@ __device__ __forceinline__ int head_cvt_u8(float p, float out_scale) {
   return (int)r;
 }
 
+// ---- shared with attn.cuh (the fused attention's softmax in LDS): byte access and the wave reductions -----------------------
+__device__ __forceinline__ unsigned head_byte(const v4i &raw, int e) { return ((unsigned)raw[e >> 2] >> (8 * (e & 3))) & 0xffu; }
+
+__device__ __forceinline__ unsigned long long head_wave_max(unsigned long long x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned long long o = __shfl_xor(x, m);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+__device__ __forceinline__ unsigned head_wave_max(unsigned x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned o = (unsigned)__shfl_xor((int)x, m);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+__device__ __forceinline__ unsigned head_wave_sum(unsigned x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x += (unsigned)__shfl_xor((int)x, m);
+  return x;
+}
+
+// the same over aligned groups of W consecutive lanes (W a power of two <= 64): every lane of a group gets the group's result
+template <int W>
+__device__ __forceinline__ unsigned head_lanes_max(unsigned x) {
+#pragma unroll
+  for (int m = W / 2; m >= 1; m >>= 1) {
+    const unsigned o = (unsigned)__shfl_xor((int)x, m);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+template <int W>
+__device__ __forceinline__ unsigned head_lanes_sum(unsigned x) {
+#pragma unroll
+  for (int m = W / 2; m >= 1; m >>= 1) x += (unsigned)__shfl_xor((int)x, m);
+  return x;
+}
+
 #ifdef DFX_HEAD_KERNELS
 
 // the K best pairs seen so far, best first
@@ -140,7 +182,6 @@ __global__ __launch_bounds__(256) void head_generic_softmax_kernel(HeadArgs a) {
 }
 
 // ---- shared by the row and the pixel kernels -----------------------------------------------------------------------------
-__device__ __forceinline__ unsigned head_byte(const v4i &raw, int e) { return ((unsigned)raw[e >> 2] >> (8 * (e & 3))) & 0xffu; }
 
 // the probabilities of the 16-byte group `g` of a row whose maximum key is m, stored behind `dst_row` (bytes); only the
 // `nvalid` leading channels of the group exist
@@ -181,28 +222,6 @@ __device__ __forceinline__ void head_store_group(const HeadArgs &a, const unsign
         if (e < nvalid) q[e] = (unsigned char)by[e];
     }
   }
-}
-
-__device__ __forceinline__ unsigned long long head_wave_max(unsigned long long x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long o = __shfl_xor(x, m);
-    x = o > x ? o : x;
-  }
-  return x;
-}
-__device__ __forceinline__ unsigned head_wave_max(unsigned x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)x, m);
-    x = o > x ? o : x;
-  }
-  return x;
-}
-__device__ __forceinline__ unsigned head_wave_sum(unsigned x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x += (unsigned)__shfl_xor((int)x, m);
-  return x;
 }
 
 // ---- row: a wave per row ---------------------------------------------------------------------------------------------------

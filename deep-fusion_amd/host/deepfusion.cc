@@ -2976,6 +2976,80 @@ private:
   detail::op_state st_;
 };
 
+// ---- fused int8 attention (dfx_attn_*): o[g] = requant(softmax(requant(q[g] . k[g]^T)) . v[g]) over matrices that lie in four
+// tensors at the strides of attention_shape.  q, k and v are registered as reads, o as a write (op_state).  One handle on one
+// device, like op_matmul. ----
+class op_attention : public op {
+public:
+  op_attention(memory *q, memory *k, memory *v, const std::array<uint32_t, 256> &table, memory *o, const attention_shape &sh, float logit_scale,
+               const std::vector<float> &out_scales, float prob_scale, bool relu, round_mode rm)
+      : q_(q), k_(k), v_(v), o_(o), h_(nullptr) {
+    if (!q_ || !k_ || !v_ || !o_) error_and_exit("Init Attention op failed! (null tensor)");
+    dfx_attn_desc d;
+    memset(&d, 0, sizeof(d));
+    d.batch0 = sh.batch0; d.batch1 = sh.batch1; d.tq = sh.tq; d.tk = sh.tk; d.d = sh.d; d.dv = sh.dv;
+    d.q_dt = to_dfx_dtype(q_->data_type()); d.k_dt = to_dfx_dtype(k_->data_type()); d.v_dt = to_dfx_dtype(v_->data_type());
+    d.dst_dt = to_dfx_dtype(o_->data_type());
+    d.relu = relu ? 1 : 0;
+    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.nscales = (int)out_scales.size();
+    d.force_path = -1;
+    d.prob_scale = prob_scale;
+    d.q_s0 = sh.q_s0; d.q_s1 = sh.q_s1; d.ldq = sh.ldq;
+    d.k_s0 = sh.k_s0; d.k_s1 = sh.k_s1; d.ldk = sh.ldk;
+    d.v_s0 = sh.v_s0; d.v_s1 = sh.v_s1; d.ldv = sh.ldv;
+    d.o_s0 = sh.o_s0; d.o_s1 = sh.o_s1; d.ldo = sh.ldo;
+    if (out_scales.empty()) error_and_exit("Init Attention op failed! (out_scales must hold 1 or dv floats)");
+    if (dfx_attn_create(&d, &h_) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
+    // every matrix within its tensor: the last row of q, k and v up to its valid columns rounded up to 16, which is what the
+    // library may read (the create above has found the sizes positive and the strides non-negative)
+    auto end = [&](long long s0, long long s1, long long ld, long long rows, long long cols, bool read) {
+      const long long row = read ? std::min<long long>(ld, (cols + 15) / 16 * 16) : cols;
+      return (sh.batch0 - 1) * s0 + (sh.batch1 - 1) * s1 + (rows - 1) * ld + row;
+    };
+    if (end(sh.q_s0, sh.q_s1, sh.ldq, sh.tq, sh.d, true) > (long long)q_->size() || end(sh.k_s0, sh.k_s1, sh.ldk, sh.tk, sh.d, true) > (long long)k_->size() ||
+        end(sh.v_s0, sh.v_s1, sh.ldv, sh.tk, sh.dv, true) > (long long)v_->size() || end(sh.o_s0, sh.o_s1, sh.ldo, sh.tq, sh.dv, false) > (long long)o_->size())
+      error_and_exit("Init Attention op failed! (a matrix reaches beyond its tensor)");
+    if (dfx_attn_set_table(h_, table.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
+    if (dfx_attn_set_scales(h_, logit_scale, out_scales.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_attention() override {
+    st_.retire(*o_);
+    dfx_attn_destroy(h_);
+  }
+
+  void submit() override {
+    run(true);
+    st_.fetch_out(*o_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*o_);
+  }
+  void submit_async() override { run(false); }
+  void wait() override {
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*o_);
+  }
+
+protected:
+  void infer() override { run(true); }
+  void run(bool sync_host) {
+    const void *q = st_.sync_in(*q_, sync_host);
+    const void *k = st_.sync_in(*k_, sync_host);
+    const void *v = st_.sync_in(*v_, sync_host);
+    void *o = st_.device_out(*o_);
+    st_.profile_begin();
+    check_dfx(dfx_attn_submit(h_, q, k, v, o, st_.stream), "attn submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "attention"; }
+
+private:
+  memory *q_, *k_, *v_, *o_;
+  dfx_attn_t *h_;
+  detail::op_state st_;
+};
+
 // ---- squeeze-and-excitation (dfx_se_*) and, with no weights, the global average pooling it starts with.  The two weight
 // tensors are plain oihw {cr, c, 1, 1} and {c, cr, 1, 1}; dst may be src.  Weight hashing and batch sharding are
 // op_depthwise_conv's: the op is per image, so shards are independent. ----
@@ -3437,6 +3511,12 @@ std::array<long long, 3> attention_strides(int bs, int heads, int t, int d, long
 std::unique_ptr<op> matmul(const std::unique_ptr<memory> &a, const std::unique_ptr<memory> &b, std::unique_ptr<memory> &c,
                            const matmul_shape &shape, const std::vector<float> &scales, bool relu, round_mode rm) {
   return std::unique_ptr<op>(new op_matmul(a.get(), b.get(), c.get(), shape, scales, relu, rm));
+}
+
+std::unique_ptr<op> attention(const std::unique_ptr<memory> &q, const std::unique_ptr<memory> &k, const std::unique_ptr<memory> &v,
+                              const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &o, const attention_shape &shape,
+                              float logit_scale, const std::vector<float> &out_scales, float prob_scale, bool relu, round_mode rm) {
+  return std::unique_ptr<op>(new op_attention(q.get(), k.get(), v.get(), table, o.get(), shape, logit_scale, out_scales, prob_scale, relu, rm));
 }
 
 std::unique_ptr<op> select_top_k(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, memory *dst_val,

@@ -621,4 +621,36 @@ int dfx_bmm_submit(dfx_bmm_t *hv, const void *a, const void *b, void *c, dfx_str
 }
 int dfx_bmm_destroy(dfx_bmm_t *h) { return destroy_handle(h); }
 
+// ---- fused attention: reads Q (`src[0]`), K (`src[1]`) and V (`src[2]`), writes O (`dst`); byte ranges from the first to
+// behind the last valid element of each operand, as dfx_attn_submit's overlap check takes them ----
+int dfx_attn_create(const dfx_attn_desc *d, dfx_attn_t **out) {
+  if (!d || !out || d->batch0 < 1 || d->batch1 < 1 || d->tq < 1 || d->tk < 1 || d->d < 1 || d->dv < 1 || d->ldq < d->d || d->ldk < d->d ||
+      d->ldv < d->dv || d->ldo < d->dv)
+    return fail(DFX_ERR_INVALID, "bad attn descriptor");
+  handle *h = new_handle("attn");
+  const size_t b0 = (size_t)d->batch0 - 1, b1 = (size_t)d->batch1 - 1;
+  h->src.push_back(b0 * d->q_s0 + b1 * d->q_s1 + ((size_t)d->tq - 1) * d->ldq + d->d);
+  h->src.push_back(b0 * d->k_s0 + b1 * d->k_s1 + ((size_t)d->tk - 1) * d->ldk + d->d);
+  h->src.push_back(b0 * d->v_s0 + b1 * d->v_s1 + ((size_t)d->tk - 1) * d->ldv + d->dv);
+  h->dst = (b0 * d->o_s0 + b1 * d->o_s1 + ((size_t)d->tq - 1) * d->ldo + d->dv) * dt_size(d->dst_dt);
+  *out = reinterpret_cast<dfx_attn_t *>(h);
+  return DFX_OK;
+}
+int dfx_attn_set_table(dfx_attn_t *h, const uint32_t *) { return set_weights(h, "dfx_attn_set_table", {}); }
+int dfx_attn_set_scales(dfx_attn_t *h, float, const float *) { return set_weights(h, "dfx_attn_set_scales", {}); }
+int dfx_attn_submit(dfx_attn_t *hv, const void *q, const void *k, const void *v, void *o, dfx_stream_t s) {
+  handle *h = reinterpret_cast<handle *>(hv);
+  if (!h) return fail(DFX_ERR_INVALID, "null handle");
+  if (!stream_ok(s, "dfx_attn_submit")) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_attn_submit", {}};
+  add_range(r, q, h->src[0], false);
+  add_range(r, k, h->src[1], false);
+  add_range(r, v, h->src[2], false);
+  add_range(r, o, h->dst, true);
+  r.ranges.push_back({h->packed, 0, 1, false});
+  g_trace.push_back(r);
+  return DFX_OK;
+}
+int dfx_attn_destroy(dfx_attn_t *h) { return destroy_handle(h); }
+
 }  // extern "C"

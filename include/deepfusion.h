@@ -468,6 +468,23 @@ std::unique_ptr<op> matmul(const std::unique_ptr<memory> &a, const std::unique_p
                            const matmul_shape &shape, const std::vector<float> &scales, bool relu = false,
                            round_mode rm = round_mode::nearest);
 
+// ---- extension: fused int8 attention (dfx_attn_* in dfx.h): o[g] = requant(softmax(requant(q[g] . k[g]^T)) . v[g]) over
+// batch0 * batch1 matrices that lie anywhere in four tensors, DEFINED as matmul() (s8 logits, scale logit_scale) -> softmax()
+// (u8, table, prob_scale) -> matmul() (out_scales: 1 or dv floats, relu) and bit-identical to that chain; the library keeps the
+// logits and the probabilities on chip where its fused kernel serves the shape (dfx.h, DFX_ATTN_AUTO_NOTE) and runs the three
+// ops behind the one handle elsewhere.  q u8 or s8, k and v s8, o any of the four dtypes.  Strides are in ELEMENTS with
+// matmul_shape's meaning; attention_strides() gives them for head-sliced nhwc tensors.  What holds for matmul()'s pad
+// columns, for the bytes of o that the op does not write and for the extent of every operand within its tensor holds here.
+// Runs on ONE device (DEEPFUSION_DEVICES does not shard it), like matmul(). ----
+struct attention_shape {
+  int batch0, batch1, tq, tk, d, dv;
+  long long q_s0, q_s1, ldq, k_s0, k_s1, ldk, v_s0, v_s1, ldv, o_s0, o_s1, ldo;
+};
+std::unique_ptr<op> attention(const std::unique_ptr<memory> &q, const std::unique_ptr<memory> &k, const std::unique_ptr<memory> &v,
+                              const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &o, const attention_shape &shape,
+                              float logit_scale, const std::vector<float> &out_scales, float prob_scale = 255.f, bool relu = false,
+                              round_mode rm = round_mode::nearest);
+
 // ---- extension: image-wide top-K with peak filter (dfx_select_* in dfx.h): what a detector does behind its last conv,
 // without leaving the device.  src: an nhwc score tensor {bs, C, h, w} of u8 / s8 (a conv()'s heat map); the first c_valid
 // channels of a pixel take part (0: all).  Per image, the k (1 .. 4096) best elements that are >= min_val and, with peak3,

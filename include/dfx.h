@@ -1070,8 +1070,8 @@ typedef struct dfx_roialign dfx_roialign_t;
  *      alone: "fast" when the round mode is nearest, DFX_NO_FAST is not set, every scale is finite and
  *      bound * |scale| <= 2^30 with bound = 255*128*K (u8 A) or 128*128*K (s8 A); otherwise "exact".  The generic kernel is
  *      always exact.  Both routes give the same bits wherever "fast" is allowed.
- *      Not built: u8 B, an additive mask / relative-position bias on the logits, softmax fused between the two products
- *      (flash-style, one launch), split-K for tiny G*M*N, a bias, K > 65025, s32 / f32 operands.
+ *      Not built: u8 B, an additive mask / relative-position bias on the logits, split-K for tiny G*M*N, a bias,
+ *      K > 65025, s32 / f32 operands.  (The softmax fused between the two products, one launch, is dfx_attn below.)
  *      Parity unpinned: the reference has no such op. ---- */
 typedef struct dfx_bmm_desc {
   int32_t batch0, batch1;      /* >= 1; G = batch0 * batch1 matrices */
@@ -1119,6 +1119,85 @@ typedef struct dfx_bmm_info {
   char kernel_name[96];        /* "bmm_mfma<nt,u8,s8> fast": form (nt | nn), A type, dst type, route (after set_scales) */
 } dfx_bmm_info;
 typedef struct dfx_bmm dfx_bmm_t;
+
+/* ---- fused int8 attention: Q.K^T, the table softmax and P.V behind ONE handle and, on the fused path, in ONE launch with
+ *      the logits and the probabilities kept on chip.  It is DEFINED as the chain of the three existing ops, by reference
+ *      (their arithmetic is not restated here), for every matrix g = b0 * batch1 + b1:
+ *        L[m,n] = dfx_bmm (trans_b = 1, a_dt = q_dt, dst s8, nscales 1, no ReLU, scale = logit_scale) of Q[g] {tq,d} and
+ *                 K[g] {tk,d}:  m < tq, n < tk, contraction over d
+ *        P[m,:] = dfx_head DFX_HEAD_SOFTMAX (src s8, dst u8, c = tk, table E, out_scale = prob_scale) of L[m,:]
+ *        O[m,j] = dfx_bmm (trans_b = 0, a_dt u8, scales = out_scales[1 or dv], relu, dst_dt) of P[g] {tq,tk} and V[g] {tk,dv}:
+ *                 j < dv, contraction over tk
+ *      round_mode applies to both requants; the softmax's u8 conversion is dfx_head's (rint to even).  Because the softmax
+ *      is a table lookup on max - x, S an exact u32 sum and the division one correctly rounded f32 division, nothing has to
+ *      be rescaled online: the fused kernel is bit-identical to the chain.
+ *      OPERANDS.  Q u8 or s8; K and V s8 (u8: DFX_ERR_UNSUPPORTED, not built); O u8 / s8 / s32 / f32.
+ *      ADDRESSING.  Each of Q, K, V, O has two batch strides and a leading dimension in elements with dfx_bmm's meaning:
+ *      a batch stride of 0 broadcasts Q, K or V and is never allowed on O (dfx_bmm's C-overlap rule holds for O).  Heads of
+ *      a {bs, T, heads*d} tensor are read in place and the context is written back interleaved.  Pad columns never take
+ *      part (d .. ldq-1 of Q, d .. ldk-1 of K, dv .. ldv-1 of V); elements dv .. ldo-1 of an O row are NOT written.  Every row
+ *      of Q, K and V is readable up to its valid columns rounded up to 16 (dfx_bmm's rule: the MFMA kernels read whole pieces).
+ *      LIMITS.  1 <= d <= 65025 (dfx_bmm's K), 1 <= tk <= 65025 (the context's K; dfx_head's c would admit 65535), tq and dv <= 2^31 - 32, every
+ *      operand's index range and the logits' G * tq * up16(tk) below 2^40.
+ *      REQUANT ROUTES.  Proved from the shape as dfx_bmm_set_scales does: bound 128*128*d (s8 Q) or 255*128*d (u8 Q) against
+ *      logit_scale for the logits, 255*128*tk against out_scales for the context.
+ *      Not built: a mask or relative-position bias on the logits, causal attention, u8 K / V, P or L as an output, f32
+ *      probabilities between the products, multi-device sharding.  Parity unpinned: the reference has no such op. ---- */
+typedef struct dfx_attn_desc {
+  int32_t batch0, batch1;      /* >= 1; G = batch0 * batch1 matrices */
+  int32_t tq, tk, d, dv;       /* >= 1; tq, dv <= 2^31 - 32; tk <= 65025; d <= 65025 */
+  int32_t q_dt;                /* DFX_U8 | DFX_S8 */
+  int32_t k_dt, v_dt;          /* DFX_S8 (DFX_U8: DFX_ERR_UNSUPPORTED) */
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t relu, round_mode;
+  int32_t nscales;             /* out scales: 1 or dv */
+  int32_t force_path;          /* -1 auto, else DFX_ATTN_* */
+  float prob_scale;            /* finite; dfx_head's out_scale (255.0f for full range) */
+  int32_t reserved;            /* ignored */
+  int64_t q_s0, q_s1, ldq;     /* elements; batch strides >= 0 (0 broadcasts), ldq >= d */
+  int64_t k_s0, k_s1, ldk;     /* ldk >= d */
+  int64_t v_s0, v_s1, ldv;     /* ldv >= dv */
+  int64_t o_s0, o_s1, ldo;     /* ldo >= dv; no two elements of O may share an address */
+} dfx_attn_desc;
+enum {  /* dfx_attn_info.path */
+  DFX_ATTN_FUSED = 0,          /* attn_fused_kernel (attn.cuh): one launch, no scratch in HBM.  A workgroup of four waves owns
+                                  a strip of 32 query rows of one g: logits by v_mfma_i32_32x32x32_i8 into an LDS strip, the
+                                  softmax in place in LDS, the context by the same MFMA with P read from LDS.
+                                  Class: ldq, ldk, ldv and the batch strides of Q, K, V multiples of 16 elements; d <= 256
+                                  (the strip's Q fragments stay in 32 VGPRs); tk <= 4096 (the strip, the table and the V images:
+                                  1024 + 32 * (up16(tk) + 16) + 12288 bytes of LDS, 141.5 KiB at tk 4096); q, k, v 16-byte
+                                  aligned (checked per submit: others take the chain for that submit).
+                                  AUTO RULE: see DFX_ATTN_AUTO_NOTE below. */
+  DFX_ATTN_CHAIN = 1           /* the three existing ops on the caller's stream, each on its own auto path, with L and P
+                                  ({G, tq, up16(tk)} bytes each) in scratch the handle owns.  It accepts everything the
+                                  descriptor accepts and, with those ops' generic kernels, defines the bits. */
+};
+/* DFX_ATTN_AUTO_NOTE: auto takes DFX_ATTN_FUSED in its class for tq >= 49, 49 <= tk <= 850, 32 <= d <= 64, 32 <= dv <= 64 and at
+ * least 384 strips of 32 query rows (G * ceil(tq / 32), the fused kernel's workgroups), and DFX_ATTN_CHAIN everywhere else.  The
+ * lower bounds are the smallest of each at which it was timed against the chain and won, the upper bounds the largest: beyond them
+ * lies a point where it LOSES.  On the 6 points of profiles/attn/bench_attn.txt (MI355X, s8 Q / K / V / O head-sliced in place, forced
+ * legs alternating in one process, buffers in rotation beyond the Infinity Cache, windows of at least 3 ms, median of 5 rounds whose
+ * extremes lie within 3.6 % of it): ViT-B (heads 12, T 197, d 64) at bs 8 in 22.6 us against the chain's 46.7 (0.48x) and at bs 64 in
+ * 134 us against 259 (0.52x); a Swin stage (192 windows of 49, d 32: two strips per window, the second with 17 of its 32 rows) in
+ * 12.5 us against 21.8 (0.57x); a DETR encoder (bs 2, heads 8, T 850, d 32) in 41.6 us against 63.8 (0.65x); and a non-local block
+ * (T 4096, d = dv = 256) at bs 1 in 389 us against 186 (2.09x SLOWER: 128 workgroups on 256 CUs) and at bs 4 in 780 us against 358
+ * (2.18x SLOWER): there a strip holds 141.5 KiB of LDS, so a CU runs ONE workgroup of four waves, and every strip re-reads all of K
+ * and V (2 MiB) through L2 with nothing to hide the latency.  The floor (Q, K, V and O once at 8 TB/s) is 0.6 / 4.8 / 0.15 / 0.22 /
+ * 0.5 / 2.1 us: the fused kernel is 37x to 750x above it.  Nothing between the box and the non-local point (tk 851 .. 4095, d or dv
+ * 65 .. 255), nothing smaller and nothing with fewer strips was timed: all of it stays on the chain; DFX_ATTN_FUSED is reachable
+ * there with force_path and gives the same bits. */
+typedef struct dfx_attn_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back to the chain without changing it) */
+  int32_t grid, block, lds_bytes; /* of the fused kernel; 0 on the chain (see the three ops' own queries) */
+  int32_t device;
+  int32_t route_logits, route_context; /* 0 exact, 1 fast, as the last set_scales proved them; -1 before it */
+  uint64_t scratch_bytes;      /* L and P together, as the handle holds them now: 0 on a fused handle until a submit has fallen
+                                  back to the chain */
+  uint64_t algorithmic_ops;    /* 2 * G * tq * tk * (d + dv) */
+  uint64_t algorithmic_bytes;  /* the distinct bytes of Q, K, V and O: a broadcast operand counts once (the floor) */
+  char kernel_name[96];        /* "attn_fused<s8,s8> fast/exact": Q type, dst type, logits / context route; "attn_chain<...>" */
+} dfx_attn_info;
+typedef struct dfx_attn dfx_attn_t;
 
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
@@ -1619,6 +1698,32 @@ int dfx_bmm_submit(dfx_bmm_t *h, const void *a_dev, const void *b_dev, void *c_d
 int dfx_bmm_query(const dfx_bmm_t *h, dfx_bmm_info *info);
 int dfx_bmm_destroy(dfx_bmm_t *h);
 
+/* ---- fused int8 attention (dfx_attn_desc above).  The descriptor is validated before anything touches a device, in this
+ *      order: DFX_ERR_INVALID for a non-positive size, tq or dv above 2^31 - 32, d > 65025, tk > 65025, a bad q / k / v / dst
+ *      dtype / round mode / nscales (1 or dv) / force_path, a prob_scale that is not finite, ldq < d, ldk < d, ldv < dv,
+ *      ldo < dv, a negative stride, an O whose elements could overlap (dfx_bmm's rule with (dv,1), (tq,ldo), (batch1,o_s1),
+ *      (batch0,o_s0)), any operand whose index range reaches 2^40 elements, and logits whose G * tq * up16(tk) reach 2^40;
+ *      then DFX_ERR_UNSUPPORTED only for a u8 K or V and for force_path = DFX_ATTN_FUSED outside that class.  "No HIP
+ *      device" is reported only for a valid descriptor.
+ *      set_table: dfx_head_set_table's checks with c = tk.  set_scales: one logit scale and 1 or dv out scales, host values,
+ *      copied; it chooses both requant routes (above).  Both may be called again (not while a submit is in flight).
+ *      submit: asynchronous on `s`; DFX_ERR_INVALID, with nothing launched, for a null pointer, a 4-byte O that is not 4-byte
+ *      aligned and an O byte range that overlaps Q's, K's or V's; DFX_ERR_STATE before set_table and set_scales.
+ *      A handle may be submitted from several host threads and on several streams at once.  Fused path: one launch with its
+ *      own arguments, submits are independent.  Chain (planned, or taken for one submit because q, k or v is not 16-byte
+ *      aligned): the handle owns ONE scratch for L and P -- allocated at create where the chain is the plan, at the first such
+ *      submit on a fused handle (DFX_ERR_HIP from that submit if the device has no room) -- so those submits are
+ *      SERIALISED as dfx_dwpw's two-launch path is: ordered by the stream on one stream; once a second stream has been seen,
+ *      every chain submit records an event and a submit on a stream other than the previous one's first waits for it on
+ *      the device.  The host never blocks.
+ *      Tuning switch: DFX_ATTN_GRID=n caps the fused kernel's grid.  No CPU fallback. ---- */
+int dfx_attn_create(const dfx_attn_desc *desc, dfx_attn_t **out);
+int dfx_attn_set_table(dfx_attn_t *h, const uint32_t *table256);
+int dfx_attn_set_scales(dfx_attn_t *h, float logit_scale, const float *out_scales);
+int dfx_attn_submit(dfx_attn_t *h, const void *q_dev, const void *k_dev, const void *v_dev, void *o_dev, dfx_stream_t s);
+int dfx_attn_query(const dfx_attn_t *h, dfx_attn_info *info);
+int dfx_attn_destroy(dfx_attn_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -1725,6 +1830,8 @@ int dfx_debug_bmm_launches(int64_t out[2]);
 /* the matrix product's one stage as the last dfx_bmm_set_scales proved it, same numbering (0 exact, 1 fast; the generic
  * path is always exact).  DFX_ERR_STATE before set_scales. */
 int dfx_debug_bmm_requant(const dfx_bmm_t *h, int32_t out[1]);
+/* the same for dfx_attn_submit: out[DFX_ATTN_FUSED], out[DFX_ATTN_CHAIN] (a chain submit counts once) */
+int dfx_debug_attn_launches(int64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,8 @@ from .capi import (  # noqa: F401
     roialign_launches, roi_level_thresholds,
     BMM_AUTO, BMM_MFMA, BMM_GENERIC, BmmDesc, BmmInfo, MatMul, bmm_launches, attention_strides,
     ATTN_AUTO, ATTN_FUSED, ATTN_CHAIN, AttnDesc, AttnInfo, Attention, attn_launches,
+    LNORM_LAYER, LNORM_RMS, LNORM_AUTO, LNORM_ROW, LNORM_GENERIC, LNORM_MAX_C, LNORM_MAX_SHIFT, LnormDesc, LnormInfo, LayerNorm,
+    lnorm_launches, lnorm_params,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

@@ -43,6 +43,9 @@ ROI_BATCHED, ROI_LIST = 0, 1
 ROIALIGN_AUTO, ROIALIGN_TILE, ROIALIGN_GENERIC = -1, 0, 1
 BMM_AUTO, BMM_MFMA, BMM_GENERIC = -1, 0, 1
 ATTN_AUTO, ATTN_FUSED, ATTN_CHAIN = -1, 0, 1
+LNORM_LAYER, LNORM_RMS = 0, 1
+LNORM_AUTO, LNORM_ROW, LNORM_GENERIC = -1, 0, 1
+LNORM_MAX_C, LNORM_MAX_SHIFT = 16384, 7
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -289,6 +292,17 @@ class AttnInfo(ctypes.Structure):
                 ("kernel_name", ctypes.c_char * 96)]
 
 
+class LnormDesc(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("mode", "src_dt", "dst_dt", "c", "src_ld", "dst_ld")] + \
+               [("eps", ctypes.c_float), ("force_path", ctypes.c_int32)]
+
+
+class LnormInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
+
+
 class DwPwDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t", "pad_l",
                                              "oc", "dst_dt", "bia0_dt", "bia1_dt", "relu", "round_mode0", "round_mode1",
@@ -509,6 +523,12 @@ def lib():
         "dfx_attn_query": (i32, [vp, ctypes.POINTER(AttnInfo)]),
         "dfx_attn_destroy": (i32, [vp]),
         "dfx_debug_attn_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_lnorm_create": (i32, [ctypes.POINTER(LnormDesc), ctypes.POINTER(vp)]),
+        "dfx_lnorm_set_params": (i32, [vp, vp, vp, vp]),
+        "dfx_lnorm_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_lnorm_query": (i32, [vp, ctypes.POINTER(LnormInfo)]),
+        "dfx_lnorm_destroy": (i32, [vp]),
+        "dfx_debug_lnorm_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -581,6 +601,26 @@ def attn_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_attn_launches(v))
     return v[ATTN_FUSED], v[ATTN_CHAIN]
+
+
+def lnorm_launches():
+    """(row, generic): dfx_lnorm_submit calls of this process that launched each kernel (dfx_debug_lnorm_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_lnorm_launches(v))
+    return v[LNORM_ROW], v[LNORM_GENERIC]
+
+
+def lnorm_params(gamma, beta, in_scale, out_scale, eps):
+    """(gamma', beta', eps_q) for dfa.LayerNorm from a float layer norm's parameters: the input is x = in_scale * code, the
+    output code is y / out_scale (out_scale None: an f32 dst, which takes gamma and beta as they are).  eps_q = eps /
+    in_scale^2 is eps in units of the integer domain.  Computed in float64 and rounded once.  beta None stays None."""
+    g = np.asarray(gamma, dtype=np.float64).reshape(-1)
+    b = None if beta is None else np.asarray(beta, dtype=np.float64).reshape(-1)
+    if out_scale is not None:
+        g = g / float(out_scale)
+        b = None if b is None else b / float(out_scale)
+    eps_q = np.float32(float(eps) / (float(in_scale) * float(in_scale)))
+    return g.astype(np.float32), None if b is None else b.astype(np.float32), eps_q
 
 
 def attention_strides(bs, heads, t, d, ld=None):
@@ -1191,6 +1231,33 @@ class Head(_Handle):
         """asynchronous; torch CUDA tensors (or raw pointers); out_dev: idx (TOPK) or dst (SOFTMAX)"""
         _check(lib().dfx_head_submit(self._h, _dev_ptr(src_dev), _dev_ptr(out_dev),
                                      None if val_dev is None else _dev_ptr(val_dev), _stream_ptr(stream)))
+
+
+class LayerNorm(_Handle):
+    """dfx_lnorm_* handle: int8 layer norm (mode LNORM_LAYER) or RMS norm (LNORM_RMS) over a row matrix: `rows` rows of `c`
+    valid channels (include/dfx.h).  src uint8 / int8, dst uint8 / int8 / float32; eps in units of the integer domain
+    (lnorm_params()).  set_params(gamma, beta=None, shift=None) first; submit(src, dst)."""
+
+    _OP, _INFO = "dfx_lnorm", LnormInfo
+
+    def __init__(self, rows, c, src_dtype, dst_dtype, eps, mode=LNORM_LAYER, src_ld=None, dst_ld=None, force_path=LNORM_AUTO):
+        code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
+        d = LnormDesc()
+        d.rows, d.mode, d.src_dt, d.dst_dt, d.c = rows, mode, code(src_dtype), code(dst_dtype), c
+        d.src_ld = c if src_ld is None else src_ld
+        d.dst_ld = c if dst_ld is None else dst_ld
+        d.eps, d.force_path = eps, force_path
+        self.desc = d
+        self._create(d)
+
+    def set_params(self, gamma, beta=None, shift=None):
+        """gamma, beta: c floats (beta None: zeros); shift: c bytes of 0 .. 7 or None"""
+        c = self.desc.c
+        g = np.ascontiguousarray(gamma, dtype=np.float32).reshape(-1)
+        b = None if beta is None else np.ascontiguousarray(beta, dtype=np.float32).reshape(-1)
+        s = None if shift is None else np.ascontiguousarray(shift, dtype=np.uint8).reshape(-1)
+        assert g.size == c and (b is None or b.size == c) and (s is None or s.size == c)
+        _check(lib().dfx_lnorm_set_params(self._h, _p(g), _p(b), _p(s)))
 
 
 class TopK(Head):

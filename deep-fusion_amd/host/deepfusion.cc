@@ -2621,6 +2621,145 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- int8 layer norm / RMS norm (dfx_lnorm_*) over the rows of an nhwc tensor (rows = bs * h * w, src_ld = C, c_valid <= C);
+// dst {bs, C', h, w} with C' >= c_valid, whose pad channels the kernel leaves alone (undefined on the host afterwards, as
+// op_head's softmax).  gamma / beta / shifts are copied at construction.  src is registered as a read, dst as a write
+// (op_state).  Batch sharding is op_head's: both tensors are batch-major. ----
+class op_layer_norm : public op {
+public:
+  op_layer_norm(const std::unique_ptr<memory> &src, const std::vector<float> &gamma, const std::vector<float> &beta,
+                std::unique_ptr<memory> &dst, float eps, norm_mode mode, const std::vector<u8> &shifts, int c_valid)
+      : src_(src.get()), dst_(dst.get()), h_(nullptr) {
+    using fmt = memory::format;
+    if (!src_ || !dst_) error_and_exit("Init LayerNorm op failed! (null tensor)");
+    if (src_ == dst_) error_and_exit("Init LayerNorm op failed! (in place is not built)");
+    if (src_->dim_format() != fmt::nhwc || dst_->dim_format() != fmt::nhwc) error_and_exit("Init LayerNorm op failed! (format)");
+    auto i = src_->std_dims(), o = dst_->std_dims();
+    if (i[0] != o[0] || i[2] != o[2] || i[3] != o[3]) error_and_exit("Init LayerNorm op failed! (batch size / height / width do not equal)");
+    dfx_lnorm_desc d;
+    memset(&d, 0, sizeof(d));
+    const long long px = (long long)i[2] * i[3];
+    d.rows = (long long)i[0] * px;
+    d.mode = mode == norm_mode::rms ? DFX_LNORM_RMS : DFX_LNORM_LAYER;
+    d.src_dt = to_dfx_dtype(src_->data_type());
+    d.dst_dt = to_dfx_dtype(dst_->data_type());
+    d.c = c_valid > 0 ? c_valid : i[1];
+    d.src_ld = i[1];
+    d.dst_ld = o[1];
+    d.eps = eps;
+    d.force_path = -1;
+    if ((long long)gamma.size() != d.c) error_and_exit("Init LayerNorm op failed! (gamma must have c_valid values)");
+    if (!beta.empty() && (long long)beta.size() != d.c) error_and_exit("Init LayerNorm op failed! (beta must be empty or have c_valid values)");
+    if (!shifts.empty() && (long long)shifts.size() != d.c) error_and_exit("Init LayerNorm op failed! (shifts must be empty or have c_valid values)");
+    const float *b = beta.empty() ? nullptr : beta.data();
+    const u8 *s = shifts.empty() ? nullptr : shifts.data();
+    src_img_ = (size_t)px * i[1] * dtype_size(src_->data_type());
+    dst_img_ = (size_t)px * o[1] * dtype_size(dst_->data_type());
+    for (const detail::shard_range &r : detail::plan_shards(i[0])) {
+      shard sh;
+      sh.r = r;
+      dfx_lnorm_desc ds = d;
+      ds.rows = (long long)r.n * px;
+      check_dfx(dfx_set_device(r.device), "set device");
+      if (dfx_lnorm_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init LayerNorm op failed! (%s)", dfx_last_error());
+      if (dfx_lnorm_set_params(sh.h, gamma.data(), b, s) != DFX_OK) error_and_exit("Init LayerNorm op failed! (%s)", dfx_last_error());
+      check_dfx(dfx_stream_create(&sh.stream), "stream create");
+      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
+      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
+      shards_.push_back(sh);
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    if (dfx_lnorm_create(&d, &h_) != DFX_OK) error_and_exit("Init LayerNorm op failed! (%s)", dfx_last_error());
+    if (dfx_lnorm_set_params(h_, gamma.data(), b, s) != DFX_OK) error_and_exit("Init LayerNorm op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_layer_norm() override {
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      dfx_lnorm_destroy(sh.h);
+      dfx_stream_destroy(sh.stream);
+      dfx_mem_free_device(sh.src);
+      dfx_mem_free_device(sh.dst);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire(*dst_);
+    dfx_lnorm_destroy(h_);
+  }
+
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  void submit_async() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(false);
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled(*dst_);
+    }
+  }
+
+protected:
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
+    const char *hs = static_cast<const char *>(src_->host_data());
+    char *ho = static_cast<char *>(const_cast<void *>(dst_->host_data()));
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
+      check_dfx(dfx_lnorm_submit(sh.h, sh.src, sh.dst, sh.stream), "lnorm submit");
+      check_dfx(dfx_memcpy_d2h(ho + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    detail::op_state::host_is_current(*dst_);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  void run(bool sync_host) {
+    const void *in = st_.sync_in(*src_, sync_host);
+    void *o = st_.device_out(*dst_);
+    st_.profile_begin();
+    check_dfx(dfx_lnorm_submit(h_, in, o, st_.stream), "lnorm submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "layer_norm"; }
+
+private:
+  struct shard {
+    detail::shard_range r;
+    dfx_lnorm_t *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    void *src = nullptr, *dst = nullptr;
+  };
+  memory *src_, *dst_;
+  dfx_lnorm_t *h_;
+  size_t src_img_, dst_img_;  // bytes per image
+  detail::op_state st_;
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
+};
+
 // ---- image-wide top-K with peak filter (dfx_select_*): the k best elements of every image of an nhwc score tensor,
 // optionally only 3x3 local maxima and only elements >= min_val, with whole pixel rows of further nhwc tensors gathered
 // behind it.  src and the gather sources are registered as reads, idx, count, val and the gather destinations as writes
@@ -3500,6 +3639,11 @@ std::unique_ptr<op> top_k(const std::unique_ptr<memory> &src, std::unique_ptr<me
 std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &dst,
                             float out_scale, int c_valid) {
   return std::unique_ptr<op>(new op_head(src, dst, nullptr, DFX_HEAD_SOFTMAX, 0, c_valid, &table, out_scale));
+}
+
+std::unique_ptr<op> layer_norm(const std::unique_ptr<memory> &src, const std::vector<float> &gamma, const std::vector<float> &beta,
+                               std::unique_ptr<memory> &dst, float eps, norm_mode mode, const std::vector<u8> &shifts, int c_valid) {
+  return std::unique_ptr<op>(new op_layer_norm(src, gamma, beta, dst, eps, mode, shifts, c_valid));
 }
 
 std::array<long long, 3> attention_strides(int bs, int heads, int t, int d, long long ld) {

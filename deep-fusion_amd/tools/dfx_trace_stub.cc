@@ -484,6 +484,30 @@ int dfx_head_submit(dfx_head_t *hv, const void *src, void *idx_or_dst, void *val
 }
 int dfx_head_destroy(dfx_head_t *h) { return destroy_handle(h); }
 
+// ---- layer norm / RMS norm: one read (src), one write (dst) ----
+int dfx_lnorm_create(const dfx_lnorm_desc *d, dfx_lnorm_t **out) {
+  if (!d || !out || d->rows < 1 || d->c < 1 || d->src_ld < d->c || d->dst_ld < d->c) return fail(DFX_ERR_INVALID, "bad lnorm descriptor");
+  handle *h = new_handle("lnorm");
+  const size_t rows = (size_t)d->rows;
+  h->src.push_back(((rows - 1) * d->src_ld + d->c) * dt_size(d->src_dt));
+  h->dst = ((rows - 1) * d->dst_ld + d->c) * dt_size(d->dst_dt);
+  *out = reinterpret_cast<dfx_lnorm_t *>(h);
+  return DFX_OK;
+}
+int dfx_lnorm_set_params(dfx_lnorm_t *h, const float *, const float *, const uint8_t *) { return set_weights(h, "dfx_lnorm_set_params", {}); }
+int dfx_lnorm_submit(dfx_lnorm_t *hv, const void *src, void *dst, dfx_stream_t s) {
+  handle *h = reinterpret_cast<handle *>(hv);
+  if (!h) return fail(DFX_ERR_INVALID, "null handle");
+  if (!stream_ok(s, "dfx_lnorm_submit")) return DFX_ERR_INVALID;
+  dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_lnorm_submit", {}};
+  add_range(r, src, h->src[0], false);
+  add_range(r, dst, h->dst, true);
+  r.ranges.push_back({h->packed, 0, 1, false});
+  g_trace.push_back(r);
+  return DFX_OK;
+}
+int dfx_lnorm_destroy(dfx_lnorm_t *h) { return destroy_handle(h); }
+
 // ---- image-wide top-K: reads src and the gather sources (`src`); writes idx (`dst`), val when given (`lat`), count and the
 // gather destinations (this op borrows no host tensors: `wei` holds the bytes of count and of each gather destination) ----
 int dfx_select_create(const dfx_select_desc *d, dfx_select_t **out) {

@@ -441,6 +441,24 @@ std::unique_ptr<op> top_k(const std::unique_ptr<memory> &src, std::unique_ptr<me
 std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array<uint32_t, 256> &table,
                             std::unique_ptr<memory> &dst, float out_scale = 255.f, int c_valid = 0);
 
+// ---- extension: int8 layer norm / RMS norm (dfx_lnorm_* in dfx.h): the normalisation in front of every attention and every
+// MLP of a transformer block, so that inner_product() -> attention() -> scaled_sum() chains never leave the device.  src: an
+// nhwc tensor {bs, C, h, w} of u8 / s8; every pixel (token) is a row of C channels of which the first c_valid take part
+// (c_valid = 0: all), c_valid <= 16384.  dst {bs, C', h, w} of u8 / s8 / f32, C' >= c_valid.  Per row, with t_k = x_k <<
+// shifts[k] (shifts: empty, or c_valid values of 0 .. 7, FQ-ViT's power-of-two factors), the sums S = sum t_k and Q = sum t_k^2
+// are exact integers and everything behind them is one separately rounded f32 operation per step (dfx.h states the
+// sequence):  layer: y_k = (c t_k - S) * a * gamma[k] + beta[k] with a = 1 / sqrt((c Q - S^2) / c^2 + eps) / c;
+// rms: y_k = t_k * a * gamma[k] + beta[k] with a = 1 / sqrt(Q / c + eps).  u8 / s8 dst: reorder()'s conversion of y_k.
+// eps is in units of the integer domain (eps_real / in_scale^2) and the output scale is folded into gamma and beta by the
+// caller.  beta may be empty (zeros).  dst must not be src.  Bit-exact and the same on every kernel path.  c_valid, the
+// pad channels of dst (UNDEFINED on the host afterwards), submit / submit_async / wait and DEEPFUSION_DEVICES sharding over
+// the batch are softmax()'s.  Not built: s32 / f32 sources, in place, a fused residual add, group / instance norm, mean /
+// rstd as outputs. ----
+enum class norm_mode { layer = 0, rms = 1 };
+std::unique_ptr<op> layer_norm(const std::unique_ptr<memory> &src, const std::vector<float> &gamma,
+                               const std::vector<float> &beta, std::unique_ptr<memory> &dst, float eps,
+                               norm_mode mode = norm_mode::layer, const std::vector<u8> &shifts = {}, int c_valid = 0);
+
 // ---- extension: batched int8 matrix product of two DEVICE tensors (dfx_bmm_* in dfx.h): the multiply whose second operand is
 // not a weight -- Q.K^T and P.V of an attention / non-local block, a correlation layer.  a (u8 / s8), b (s8) and c (u8 / s8 /
 // s32 / f32) are tensors of any dims; `shape` says where the matrices lie in them, in ELEMENTS from each tensor's first:

@@ -1199,6 +1199,76 @@ typedef struct dfx_attn_info {
 } dfx_attn_info;
 typedef struct dfx_attn dfx_attn_t;
 
+/* ---- int8 layer norm / RMS norm over a ROW MATRIX: the normalisation in front of every attention and every MLP of a
+ *      transformer block (ViT, Swin, DETR encoders, MobileViT), so that inner_product -> attention -> scaled_sum chains
+ *      stay on the device.  No MFMA, HBM-bound.
+ *
+ *      Inputs.  src is a row matrix as in dfx_head: `rows` rows of `c` valid channels, src_ld >= c elements apart, dtype u8
+ *      or s8.  Channels c .. src_ld-1 never take part, whatever they hold.  dst is rows dst_ld >= c elements apart, dtype
+ *      u8, s8 or f32.  Elements c .. dst_ld-1 are NOT written.  1 <= c <= DFX_LNORM_MAX_C = 16384.  The other parameters:
+ *        gamma[c], beta[c]  f32 per channel, any bit patterns.  beta == NULL means zeros, and the add is still performed.
+ *        shift[c]           optional, a u8 per channel with values 0 .. 7.  NULL means all 0.  This is FQ-ViT's power-of-two
+ *                           factor and makes an 8-bit layer-norm input realistic.
+ *        eps                f32, finite and > 0, in units of the integer domain.  The caller passes eps_real / in_scale^2.
+ *
+ *      Per row, with x_k the element as an integer:
+ *
+ *        t_k = x_k * 2^shift[k]                      |t_k| <= 32640
+ *        S   = sum t_k                                exact, |S| <= 32640*c < 2^30
+ *        Q   = sum t_k^2                              exact, < 2^44 (u64)
+ *
+ *        DFX_LNORM_LAYER:
+ *          D   = c*Q - S^2                            exact u64, 0 <= D < 2^58   (c^2 x the biased variance)
+ *          v   = fdiv(u64->f32(D), f32(c*c))          each conversion rounds once to nearest even; ONE correctly rounded division
+ *          u_k = c*t_k - S                            exact s32, |u_k| < 2^31
+ *          a   = fdiv(fdiv(1.0f, sqrt(fadd(v, eps))), f32(c))     f32(c) is exact
+ *        DFX_LNORM_RMS:
+ *          v   = fdiv(u64->f32(Q), f32(c))
+ *          u_k = t_k
+ *          a   = fdiv(1.0f, sqrt(fadd(v, eps)))
+ *
+ *        y_k = fadd(fmul(fmul(s32->f32(u_k), a), gamma[k]), beta[k])      every operation rounded separately, no FMA
+ *        f32 dst: store y_k.   u8 / s8 dst: the reorder's conversion (rint to even, NaN -> 0, clamp to the dtype's range).
+ *
+ *      The bounds above are what makes 16384 the limit; static assertions in csrc/lnorm_plan.h restate them.  The output
+ *      scale is folded into gamma and beta by the caller (Python: dfa.lnorm_params).  S, Q and D are exact integers, so the
+ *      order in which lanes add them does not matter; everything behind them is a fixed sequence of single-rounded f32
+ *      operations (sqrt is the correctly rounded one), so a sequential scan and any tree give the same bits: both kernels
+ *      agree bit for bit.  A constant row has D = 0 and u_k = 0, so y_k = beta[k] exactly.
+ *      Not built: s32 / f32 sources (their sums are not order-free), in-place operation, a fused residual add, group /
+ *      instance norm, mean / rstd as outputs, c > 16384.  Parity unpinned: the reference has no such op. ---- */
+enum { DFX_LNORM_LAYER = 0, DFX_LNORM_RMS = 1 };
+enum { DFX_LNORM_MAX_C = 16384, DFX_LNORM_MAX_SHIFT = 7 };
+typedef struct dfx_lnorm_desc {
+  int64_t rows;                /* >= 1; rows * max(src_ld, dst_ld) <= 2^40 */
+  int32_t mode, src_dt /* U8|S8 */, dst_dt /* U8|S8|F32 */, c, src_ld, dst_ld;
+  float   eps;                 /* finite, > 0 */
+  int32_t force_path;          /* -1 auto | DFX_LNORM_ROW | DFX_LNORM_GENERIC */
+} dfx_lnorm_desc;
+enum {  /* dfx_lnorm_info.path */
+  DFX_LNORM_ROW = 0,           /* lnorm_row_kernel<W> (lnorm.cuh): W in {4, 8, 16, 32, 64} consecutive lanes own a row, W the
+                                  smallest of these >= ceil(c / 16), capped at 64; a 256-lane workgroup handles 256 / W rows
+                                  per trip, grid-stride.  Class: src_ld % 16 == 0, dst_ld * element size % 16 == 0; pointers
+                                  16-byte aligned (checked per submit: others take the generic kernel for that submit).
+                                  16-byte loads and stores, the last group masked by c; a lane keeps its first four groups
+                                  in registers over both passes; gamma / beta staged in LDS where 8 * c bytes <= 64 KiB. */
+  DFX_LNORM_GENERIC = 1        /* one thread per row, sequential, any alignment and leading dimension, grid-stride.  It
+                                  defines the bits. */
+};
+/* DFX_LNORM_AUTO_NOTE: UNMEASURED.  The row kernel has not been timed on an MI355X yet (tools/bench_lnorm is the
+ * instrument; profiles/lnorm/README.md), so auto takes DFX_LNORM_GENERIC everywhere and DFX_LNORM_ROW runs only where
+ * force_path asks for it -- dfx_dwpw's precedent: no path is on auto before a measurement puts it there. */
+typedef struct dfx_lnorm_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_bytes;  /* what one submit must read and write: rows * c src bytes + rows * c dst elements + gamma,
+                                  beta (8 * c) and, when given, shift (c) */
+  char kernel_name[96];        /* mode, dtypes, lanes per row, shifts: "lnorm_row<layer,s8->s8,w16,shift>",
+                                  "lnorm_generic<rms,u8->f32>" */
+} dfx_lnorm_info;
+typedef struct dfx_lnorm dfx_lnorm_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -1724,6 +1794,26 @@ int dfx_attn_submit(dfx_attn_t *h, const void *q_dev, const void *k_dev, const v
 int dfx_attn_query(const dfx_attn_t *h, dfx_attn_info *info);
 int dfx_attn_destroy(dfx_attn_t *h);
 
+/* ---- int8 layer norm / RMS norm (dfx_lnorm_desc above).  The descriptor is validated before anything touches a device,
+ *      in this order: DFX_ERR_INVALID for a bad mode, rows < 1, c outside 1 .. 16384, a src dtype other than u8 / s8, a dst
+ *      dtype other than u8 / s8 / f32, src_ld < c, dst_ld < c, an eps that is not finite and > 0, a bad force_path, more
+ *      than 2^40 elements; then DFX_ERR_UNSUPPORTED only for force_path = DFX_LNORM_ROW outside that class.  "No HIP
+ *      device" is reported only for a valid descriptor.
+ *      set_params: host pointers, copied to the device; gamma is c floats, beta c floats or NULL (zeros), shift c bytes or
+ *      NULL (all 0); a shift above 7 is DFX_ERR_INVALID and leaves the handle as it was.  It may be called again (not
+ *      while a submit of the handle is in flight).
+ *      submit: asynchronous on `s`; ONE launch with its own arguments; it never writes to the handle: one handle serves
+ *      several streams and host threads at once.  DFX_ERR_STATE before set_params.  DFX_ERR_INVALID, with nothing launched,
+ *      for a null pointer, an f32 dst that is not 4-byte aligned and a dst that overlaps src (in place is not built: rows
+ *      longer than the register budget are re-read).  Pointers that are not 16-byte aligned take the generic kernel for
+ *      that submit.
+ *      Tuning switch: DFX_LNORM_GRID=n caps the grid of either kernel.  No CPU fallback.  Auto: DFX_LNORM_AUTO_NOTE. ---- */
+int dfx_lnorm_create(const dfx_lnorm_desc *desc, dfx_lnorm_t **out);
+int dfx_lnorm_set_params(dfx_lnorm_t *h, const float *gamma, const float *beta_or_null, const uint8_t *shift_or_null);
+int dfx_lnorm_submit(dfx_lnorm_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_lnorm_query(const dfx_lnorm_t *h, dfx_lnorm_info *info);
+int dfx_lnorm_destroy(dfx_lnorm_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -1832,6 +1922,8 @@ int dfx_debug_bmm_launches(int64_t out[2]);
 int dfx_debug_bmm_requant(const dfx_bmm_t *h, int32_t out[1]);
 /* the same for dfx_attn_submit: out[DFX_ATTN_FUSED], out[DFX_ATTN_CHAIN] (a chain submit counts once) */
 int dfx_debug_attn_launches(int64_t out[2]);
+/* the same for dfx_lnorm_submit: out[DFX_LNORM_ROW], out[DFX_LNORM_GENERIC] */
+int dfx_debug_lnorm_launches(int64_t out[2]);
 
 #ifdef __cplusplus
 }

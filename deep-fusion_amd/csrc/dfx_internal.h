@@ -1,6 +1,5 @@
-// dfx_internal.h -- the few host-side helpers the translation units behind include/dfx.h share
-// (dfx_api.hip, reorder_api.hip, catconv_api.hip, dwconv_api.hip, dwpw_api.hip, gconv_api.hip, fc_api.hip, imgconv_api.hip, deconv_api.hip, dilconv_api.hip, resize_api.hip, se_api.hip, wsum_api.hip, head_api.hip, select_api.hip).  Not installed, not
-// part of the C ABI.  What needs no HIP is in requant_host.h.
+// dfx_internal.h -- the few host-side helpers the translation units behind include/dfx.h share (every *_api.hip includes
+// it, directly or through weighted_op.h).  Not installed, not part of the C ABI.  What needs no HIP is in requant_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

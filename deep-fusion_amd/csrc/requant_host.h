@@ -1,8 +1,7 @@
 // requant_host.h -- host-only: the per-channel requantisation constants (compensation, bias as f32, scale) of the ops
-// whose activations are stored as u8 - 128, and the proof of their fast requant route, written once for
-// dwconv_api.hip, gconv_api.hip, fc_api.hip, imgconv_api.hip, deconv_api.hip, dilconv_api.hip and dwpw_api.hip's stage 1 (dfx_api.hip takes the small helpers only: its proof is
-// another one).  No HIP in here, so that it can be built and run on its own (tools/requant_host_check.cc, under the
-// host sanitizers).
+// whose activations are stored as u8 - 128, and the proof of their fast requant route, written once for every op that
+// calls requant_consts() (dfx_api.hip takes the small helpers only: its proof is another one).  No HIP in here, so that
+// it can be built and run on its own (tools/requant_host_check.cc, under the host sanitizers).
 #pragma once
 
 #include <stddef.h>

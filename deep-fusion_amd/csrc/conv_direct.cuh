@@ -82,50 +82,11 @@
 namespace dfx {
 
 constexpr int DK_M = 128;    // pixel slots per unit at most (NPB = 4 blocks of 32)
-constexpr int DK_POS = 80;   // LDS bytes per halo-tile position and plane (64 + 16 pad)
 constexpr int DK_TQ = 6;     // tile granules a thread holds in registers at once (4 waves: 24 KB of tile, 8 waves: 48 KB)
 constexpr int DK_RD = 9;     // conv0 weight ring: k-blocks in flight per wave (multiple of 3)
-constexpr int DK_STAGE = 32 * 144;  // per wave: 1-byte store staging (aliases the dead tile)
 #ifndef DK_QM_TRANSPOSE
 #define DK_QM_TRANSPOSE 0           // 1: the conversion-free routes store through the LDS transpose too (A/B aid)
 #endif
-
-struct DirectGeom {
-  int ni, thv, twv;     // unit = ni whole images (ni > 1 only if thv == oh && twv == ow) x thv x twv px
-  int uy, ux, total_units;
-  int lh, lw, npos;     // halo tile rows / cols per image; positions = ni * lh * lw
-  int icb;              // 32-channel input blocks
-  int n_planes;         // 64-channel planes of the tile = (icb + 1) / 2
-  int plane_bytes;      // ni * img_pitch
-  // byte pitches of the tile: position (img, ly, lx) of a plane sits at img * img_pitch + ly * row_pitch + lx *
-  // DK_POS.  row_pitch = lw * DK_POS + 16 c, img_pitch = lh * row_pitch + 16 c': the host picks c, c' (0..15) so
-  // that the 16 lanes of every ds_read_b128 lane group of a pixel fragment fall into 16 different 16-byte bank
-  // columns.  (With the plain pitches consecutive slots of one output row are conflict-free -- DK_POS is 5 x 16 --
-  // but a 32-slot block wraps over 2-5 output rows and the row gap broke the pattern: 47 % of the LDS cycles at
-  // res4 were bank conflicts, profiles/r03/final pmc.)
-  int row_pitch, img_pitch;
-  // unfused != 0: no 1x1 stage (oc1x1 == 0).  conv0's requantised result IS the output: 4-byte outputs are stored
-  // straight from the accumulators (a lane holds 4 consecutive channels of its pixel per q: one 16-byte store),
-  // 1-byte outputs are collected in `mid` in natural channel order and leave as whole pixel rows (16-byte stores).
-  int unfused;
-  int ocb;              // conv0 output blocks, padded to a multiple of WO
-  int n_g1;             // conv1 groups of G column blocks
-  int mid_stride;       // 32 * ocb + 16
-  int off_pxoff, off_mid, off_cst;  // LDS byte offsets (tile and the aliased staging at 0)
-  int fast;             // 1: fast requant path valid (host proof)
-  int m0, m1;           // host-proven requant without conversions: m0 = 1 stage-0 "fma"; m1 = 2 / 3 stage-1 "magic" / "fma"
-  int npb;              // 32-pixel blocks per unit (1, 2 or 4)
-#ifdef DFX_STAMPS
-  unsigned long long *prof;  // diagnostic build only: [workgroup][wave][16] cycle sums
-#endif
-#ifdef DK_DEBUG
-  // bounds-checking diagnostic build: every global access is checked against these sizes; the
-  // first violation per tag is recorded in dbg[2 tag] (offset) / dbg[2 tag + 1] (size) and the
-  // access is redirected to offset 0
-  long long src_bytes, dst_bytes, wei_bytes, wei1_bytes, cst_bytes;
-  long long *dbg;
-#endif
-};
 
 #define DKF() __builtin_amdgcn_sched_barrier(0)
 #ifdef DK_DEBUG

@@ -15,11 +15,10 @@
 // Consecutive threads own consecutive channels, so weight loads are 64-B
 // contiguous per 16 lanes and dst stores are fully coalesced.
 #include "dfx_device.cuh"
+#include "conv_geom.h"
 
 namespace dfx {
 
-constexpr int GEN_TP = 32;       // pixels per workgroup
-constexpr int GEN_THREADS = 256;
 
 template <typename T>
 __device__ __forceinline__ void store_typed(T *dst, size_t idx, float f, int rm);

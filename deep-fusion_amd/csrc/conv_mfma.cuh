@@ -99,19 +99,11 @@
 #include <type_traits>
 
 #include "dfx_device.cuh"
+#include "conv_geom.h"
 
 namespace dfx {
 
-constexpr int MFMA_THREADS = 1024;  // 16 waves: 14 compute + 2 loaders (waves 7 and 15)
-constexpr int MFMA_TEAMS = 2;       // loader waves = unit streams per CU
 constexpr int MFMA_CW = 7;          // compute waves per loader
-constexpr int MFMA_NB = 4;          // input-tile ring slots in LDS (2 per loader)
-#ifndef DFX_STAMPS
-constexpr int MFMA_CTRL_BYTES = 128; // LDS control block, see CTL_* below
-#else
-constexpr int MFMA_CTRL_BYTES = 128 + 16 * 8 * 4; // + the stamps build's per-wave cycle sums ([16 waves][8] ints)
-#endif
-constexpr int MFMA_LC = 22;         // 16-byte chunks the loader wave holds per lane (88 VGPRs)
 constexpr int MFMA_SPIN_LIMIT = 1 << 24;  // bound of every flag wait (~seconds): a protocol error ends the launch
                                           // with wrong output (the parity tests catch it) instead of hanging the GPU
 
@@ -121,15 +113,6 @@ constexpr float MAGIC0_F = 12582912.0f;
 constexpr int MAGIC1_BITS = 0x3E22F983;   // 1/(2*pi), an inline constant: ulp 2^-26, mantissa 0x22F983
 constexpr int MAGIC1_LO = -0x22F983;      // most negative / positive integer it can absorb
 constexpr int MAGIC1_HI = 0x7FFFFF - 0x22F983;
-
-// Constant area (floats): per conv0 channel A0 | B0 | C0, per 1x1 channel A1 | B1 | C1 (see emit_pair).
-// The B and C of the STORING stage (stage 1 of a fused op, stage 0 of an unfused one) are kept as
-// PAIRS {k, k}: v_pk_add_f32 / v_pk_mul_f32 then take them as plain 64-bit operands.  Broadcasting
-// one 32-bit constant with op_sel instead is not safe on this hardware: the form that takes the HIGH
-// half of a source pair for the low lane (op_sel:[0,1]) returned wrong low results in the last 16
-// lanes of a wave about once per 1e4 epilogue executions (tools/probe/probe_pk_opsel.hip reproduces it
-// in isolation; the form op_sel_hi:[1,0] and scalar arithmetic never did).
-__host__ __device__ constexpr int mfma_cst_floats(int oc, int oc1) { return oc1 ? 3 * oc + 5 * oc1 : 5 * oc; }
 
 // control block in LDS (ints)
 constexpr int CTL_NEXT = 0;   // 64 x the next tile claim of this CU (every lane of a claiming wave adds 1)
@@ -151,47 +134,6 @@ __device__ __forceinline__ int chunk_swizzle(int X) {
   if (CP == 4) return (X >> 2) & 3;
   return (X >> 1) & 7;  // CP == 8 (other kernels)
 }
-
-struct MfmaGeom {  // unit decomposition chosen by the host (dfx_api.hip)
-  int th, tw;      // unit size in output rows / columns
-  int uy, ux;      // units per image along y / x
-  int linear;      // 1: tw == ow, pixels of a unit are numbered linearly across rows
-                   // 0: tw % 32 == 0, every 32-pixel tile lies inside one row
-  int total_units;
-  int row_chunks;   // (tw + 2) * (ic / 16)
-  int tile_chunks;  // (th + 2) * row_chunks
-  unsigned row_magic;  // ceil(2^32 / row_chunks): q / row_chunks == umulhi(q, row_magic)
-  unsigned tw_magic;   // ceil(2^32 / tw)
-  unsigned upi_magic, ux_magic;  // ceil(2^32 / (uy * ux)), ceil(2^32 / ux); 0 where the divisor is 1
-  int ntu;             // tile claims per unit = tiles of a full unit
-  unsigned ntu_magic;  // ceil(2^32 / ntu) (unused when ntu == 1)
-  int claim_limit;     // ntu * (total_units + 4): no CU can legitimately claim more tiles
-  int mode0, mode1;    // requant mode of stage 0 / stage 1: 0 exact, 1 fast, 2 magic (see header)
-  int s0_uniform;      // fused op with ONE conv0 scale (count 1, op_conv.cc:311-313): s0_value, no per-channel reads
-  float s0_value;
-  int tile_stride;     // bytes between the MFMA_NB input-tile slots in LDS
-  int static_rounds;   // units a loader owns statically before it turns to the queue
-  int pool;            // unfused ops only: 1 = 2x2 stride-2 max pooling fused into the store stage.  Units are
-                       // full-width row groups (th even); a tile is 2 rows x 16 columns, so that a pooling
-                       // window is accumulator registers e, e+1, e+8, e+9 of one lane; dst has oh/2 x ow/2 pixels
-  int lazy_queue;      // 1: a loader draws its next unit only when the slot for it is free (store-bound ops)
-  int half_from;       // unit ids >= half_from denote HALF units (th / 2 rows): id half_from + 2 i + j is half j of unit
-                       // half_from + i; total_units counts them.  INT_MAX: none.  The tail of a store-bound op: the
-                       // queue's granule is what a workgroup still holds when the queue runs dry (dfx_api.hip)
-  int upx;             // > 0: PIXEL-RUN units (conv_mfma.cuh only; store-bound ops whose row units end in a partial tile).
-                       // Unit u of an image is its pixels [u * upx, min((u + 1) * upx, oh * ow)) in row-major order, upx a
-                       // multiple of 32: every tile is full except the last of an image.  linear == 1, tw == ow, ux == 1,
-                       // uy = units per image, ntu = upx / 32, no half units; th = the most output rows a run touches,
-                       // ceil((ow - 1 + upx) / ow): the halo tile is always th + 2 full-width rows from the run's first row
-                       // and the run's start column travels in the unit record.  0: row / column units as above
-  int *queue;          // [0] next unit, [1] finished loaders; both 0 between launches
-#ifdef DFX_STAMPS
-  unsigned long long *prof;  // diagnostic build only: [workgroup][wave][16] cycle sums
-#endif
-#ifdef DFX_TRACE
-  int *trace;  // diagnostic build only (make trace): host-visible [workgroup][wave][4] progress words
-#endif
-};
 
 #ifdef DFX_TRACE
 // progress word of this wave in host-pinned memory: readable by the host while the kernel runs

@@ -81,7 +81,6 @@ constexpr int RL_B = RL_NB;                          // conv1 + store waves
 constexpr int RL_C = RL_A + RL_B;                    // waves that stage the weights
 constexpr int RL_WAVES = RL_C + MFMA_TEAMS;          // + 2 loaders
 constexpr int RL_THREADS = 64 * RL_WAVES;            // 768
-constexpr int RL_CTRL_BYTES = 512;                   // control block: the words of conv_mfma.cuh + the mid ring's
 constexpr int MAGIC3_BITS = 0x4B000000;              // 2^23: stage-0 accumulator start of the "fma" mode
 constexpr int RL_SPIN_LIMIT = 1 << 19;               // bound of the s_sleep(4) waits (~0.1 s): a protocol error ends the launch with
                                                      // wrong output (the parity tests catch it) instead of hanging the GPU

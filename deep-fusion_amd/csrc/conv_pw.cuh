@@ -26,18 +26,7 @@
 
 namespace dfx {
 
-constexpr int PW_THREADS = 256;
 constexpr int PW_CH = 4;  // k-blocks per chunk (a lane's 4 x 16 bytes at offsets 0, 32, 64, 96 of a 128-byte line)
-
-struct PwGeom {
-  int icb, ocb;      // 32-channel blocks
-  int px_total;      // bs * oh * ow (< 2^31 / ic: byte offsets of pixel rows stay in 32 bits per lane pair ... see host)
-  int n_blocks;      // ceil(px_total / 32)
-  int off_cst;       // LDS byte offset of the constants (behind the weights)
-  int off_stage;     // ... of the waves' store staging (behind the constants), stage_bytes per wave
-  int stage_bytes;
-  int fast, m0;      // host proofs: fast requant route valid; stage-0 "fma" route (u8 dst)
-};
 
 // one quarter block (4 consecutive channels of the lane's pixel) after requant: the packed dword (1-byte outputs) or the
 // four 4-byte values' bit patterns.  The arithmetic is store_group's / pack_group's (conv_mfma.cuh), value for value.

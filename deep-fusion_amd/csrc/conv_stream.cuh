@@ -48,35 +48,7 @@
 
 namespace dfx {
 
-constexpr int ST_THREADS = 256;
-constexpr int ST_M = 128;  // pixel slots per unit and PXB
 constexpr int ST_TQ = 4;   // tile granules (16 B) a thread stages with precomputed addresses
-constexpr int ST_POS = 64;  // LDS bytes per halo-tile position (16-byte chunks XOR-swizzled by position)
-constexpr int ST_STAGE = 32 * 144;  // per wave: 32 pixels x 128 output bytes (+16 pad), 1-byte outputs;
-                                   // the four staging areas alias the input tile (dead during the 1x1 stage)
-
-struct StreamGeom {
-  int ni, thv, twv;     // unit = ni whole images (ni > 1 only if thv == oh && twv == ow) x thv x twv px
-  int uy, ux;           // units per image (group) along y / x
-  int total_units;
-  int lh, lw, npos;     // halo tile rows / cols per image; LDS positions = ni * lh * lw
-  int n_icc;            // 64-channel input chunks
-  int icb;              // 32-channel input blocks (ic rounded up)
-  int n_occ;            // conv0 output chunks of OCC blocks
-  int ocb;              // = n_occ * OCC: padded conv0 output blocks
-  int n_g1, ks2;        // conv1: groups of G column blocks; k-steps (pairs of oc blocks)
-  int s0_steps;         // conv0 steps per unit
-  int mid_stride;       // bytes per slot of the intermediate (32 * ocb + 16)
-  int off_tile, off_pxoff, off_mid, off_cst, off_stage;  // LDS byte offsets (weight buffers at 0)
-  int fast;             // 1: the fast requant path is valid (host proof, see conv_mfma.cuh store_group)
-  int planes;           // 1: one 64-channel input chunk in LDS at a time; n_icc: all chunks resident (staged once per item)
-  unsigned mg_g4, mg_lhw, mg_lw;  // ceil(2^32 / x) for x = 4 * planes, lh * lw, lw (resident-chunk staging)
-  int occ_par;          // unfused only: 1 = a work item is (unit, output chunk) instead of a whole unit
-#ifdef DFX_STAMPS
-  unsigned long long *prof;  // diagnostic build only: [workgroup][wave][16] cycle sums
-#endif
-};
-
 // The two fragment sets alternate per k-block; sched_barrier keeps hipcc from hoisting every
 // fragment load of a stage to its top (register pressure) and from re-mixing the groups.
 // (Round 1 read this fence as a workaround for a hardware write-after-read hazard on MFMA A/B

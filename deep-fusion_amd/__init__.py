@@ -33,7 +33,7 @@ from .capi import (  # noqa: F401
     NMS_BOXES, NMS_DECODE, NMS_AUTO, NMS_MASK, NMS_GENERIC, NMS_MAX_N, NmsDesc, NmsIo, NmsInfo, BoxNms, nms_launches, box_tables,
     ROI_BATCHED, ROI_LIST, ROIALIGN_AUTO, ROIALIGN_TILE, ROIALIGN_GENERIC, RoiAlignDesc, RoiAlignIo, RoiAlignInfo, RoiAlign,
     roialign_launches, roi_level_thresholds,
-    BMM_AUTO, BMM_MFMA, BMM_GENERIC, BmmDesc, BmmInfo, MatMul, bmm_launches, attention_strides,
+    BMM_AUTO, BMM_MFMA, BMM_GENERIC, BmmDesc, BmmInfo, MatMul, bmm_launches, attention_strides, LogitBiasDesc, attention_bias,
     ATTN_AUTO, ATTN_FUSED, ATTN_CHAIN, AttnDesc, AttnInfo, Attention, attn_launches,
     LNORM_LAYER, LNORM_RMS, LNORM_AUTO, LNORM_ROW, LNORM_GENERIC, LNORM_MAX_C, LNORM_MAX_SHIFT, LnormDesc, LnormInfo, LayerNorm,
     lnorm_launches, lnorm_params,

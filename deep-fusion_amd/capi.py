@@ -279,6 +279,11 @@ class BmmInfo(ctypes.Structure):
                 ("kernel_name", ctypes.c_char * 96)]
 
 
+class LogitBiasDesc(ctypes.Structure):
+    _fields_ = [("period0", ctypes.c_int32), ("period1", ctypes.c_int32), ("s0", ctypes.c_int64), ("s1", ctypes.c_int64),
+                ("ld", ctypes.c_int64)]
+
+
 class AttnDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("batch0", "batch1", "tq", "tk", "d", "dv", "q_dt", "k_dt", "v_dt", "dst_dt", "relu",
                                               "round_mode", "nscales", "force_path")] + \
@@ -511,6 +516,7 @@ def lib():
         "dfx_debug_roialign_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
         "dfx_bmm_create": (i32, [ctypes.POINTER(BmmDesc), ctypes.POINTER(vp)]),
         "dfx_bmm_set_scales": (i32, [vp, vp]),
+        "dfx_bmm_set_bias": (i32, [vp, ctypes.POINTER(LogitBiasDesc), vp]),
         "dfx_bmm_submit": (i32, [vp, vp, vp, vp, vp]),
         "dfx_bmm_query": (i32, [vp, ctypes.POINTER(BmmInfo)]),
         "dfx_bmm_destroy": (i32, [vp]),
@@ -519,6 +525,7 @@ def lib():
         "dfx_attn_create": (i32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(vp)]),
         "dfx_attn_set_table": (i32, [vp, vp]),
         "dfx_attn_set_scales": (i32, [vp, ctypes.c_float, vp]),
+        "dfx_attn_set_bias": (i32, [vp, ctypes.POINTER(LogitBiasDesc), vp]),
         "dfx_attn_submit": (i32, [vp, vp, vp, vp, vp, vp]),
         "dfx_attn_query": (i32, [vp, ctypes.POINTER(AttnInfo)]),
         "dfx_attn_destroy": (i32, [vp]),
@@ -631,6 +638,85 @@ def attention_strides(bs, heads, t, d, ld=None):
     if min(bs, heads, t, d) < 1 or ld < heads * d:
         raise ValueError("bs, heads, t, d must be positive and ld at least heads * d")
     return t * ld, d, ld
+
+
+def _logit_bias_args(table, periods, strides, m, n):
+    """(LogitBiasDesc, contiguous f32 array) of a logit bias for an {m, n} product.  strides None: `table` is densely packed,
+    {period0, period1, m, n}, or {period0, period1, n} for one row broadcast over m (told apart by its size)."""
+    t = np.ascontiguousarray(table, dtype=np.float32).reshape(-1)
+    p0, p1 = (int(v) for v in periods)
+    b = LogitBiasDesc()
+    b.period0, b.period1 = p0, p1
+    if strides is None:
+        if t.size == p0 * p1 * m * n and (m > 1 or np.ndim(table) != 3):
+            b.s0, b.s1, b.ld = p1 * m * n, m * n, n
+        elif t.size == p0 * p1 * n:
+            b.s0, b.s1, b.ld = p1 * n, n, 0
+        else:
+            raise ValueError("a dense table holds period0 * period1 * m * n or period0 * period1 * n values, not %d" % t.size)
+    else:
+        b.s0, b.s1, b.ld = (int(v) for v in strides)
+        if min(p0, p1) >= 1 and min(b.s0, b.s1, b.ld) >= 0:          # (the library refuses the rest)
+            need = (p0 - 1) * b.s0 + (p1 - 1) * b.s1 + ((m - 1) * b.ld if b.ld else 0) + n
+            if t.size < need:
+                raise ValueError("the table holds %d values, its layout addresses %d" % (t.size, need))
+    return b, t
+
+
+def attention_bias(rel_bias=None, mask=None, key_padding=None, *, logit_step, logit_scale, acc_bound, mask_value=None):
+    """-> (table, periods): the accumulator-unit logit bias of dfa.Attention.set_bias / dfa.MatMul.set_bias (include/dfx.h)
+    for an attention over batch = (batch0, batch1) from what a float model holds:
+      rel_bias     {heads, tq, tk} real-valued (Swin's relative-position bias per head)        -> period1 = heads
+      mask         {nW, tq, tk}: real-valued additive, -inf = masked; or boolean, True = masked  -> period0 = nW
+      key_padding  {bs, tk} boolean, True = a padded key                                      -> period0 = bs
+    (mask and key_padding both set period0 and must agree on it.)  A real value r becomes r / (logit_step * logit_scale):
+    logit_step is the s8 logits' quantisation step, logit_scale the op's scale on the accumulator.  A masked entry becomes
+    the FINITE value -(acc_bound + ceil(129 / |logit_scale|)), with logit_scale's sign, rounded away from zero to f32: with
+    any accumulator within acc_bound (128 * 128 * d for s8 Q, 255 * 128 * d for u8 Q) the logit saturates to -128, and the
+    fast requant route stays provable.  mask_value=-inf keeps -inf (always the exact route).  The table is
+    {period0, period1, tq, tk}, or {period0, 1, tk} when only key_padding is given (one row broadcast over the queries)."""
+    unit = float(logit_step) * float(logit_scale)
+    if not np.isfinite(unit) or unit == 0.0:
+        raise ValueError("logit_step * logit_scale must be finite and non-zero")
+    if mask_value is None:
+        mag = float(acc_bound) + float(np.ceil(129.0 / abs(float(logit_scale))))
+        mv = np.float32(mag)
+        if float(mv) < mag:
+            mv = np.nextafter(mv, np.float32(np.inf))
+        mask_value = -mv if logit_scale > 0 else mv
+    mask_value = np.float32(mask_value)
+    parts, masked = [], []
+    if rel_bias is not None:
+        r = np.asarray(rel_bias, dtype=np.float64)
+        assert r.ndim == 3, "rel_bias is {heads, tq, tk}"
+        parts.append(r[None])
+    if mask is not None:
+        mk = np.asarray(mask)
+        assert mk.ndim == 3, "mask is {nW, tq, tk}"
+        if mk.dtype == np.bool_:
+            masked.append(mk[:, None])
+        else:
+            mk = mk.astype(np.float64)
+            if np.isnan(mk).any() or np.isposinf(mk).any():
+                raise ValueError("mask holds NaN or +inf")
+            masked.append(np.isneginf(mk)[:, None])
+            parts.append(np.where(np.isneginf(mk), 0.0, mk)[:, None])
+    if key_padding is not None:
+        kp = np.asarray(key_padding, dtype=np.bool_)
+        assert kp.ndim == 2, "key_padding is {bs, tk}"
+        masked.append(kp[:, None, None, :])
+    if not parts and not masked:
+        raise ValueError("nothing to build a bias from")
+    total = np.zeros((1, 1, 1, 1), dtype=np.float64)
+    for x in parts:
+        total = total + x
+    table = (total / unit).astype(np.float32)
+    for x in masked:
+        table = np.where(x, mask_value, np.broadcast_to(table, np.broadcast_shapes(table.shape, x.shape))).astype(np.float32)
+    p0, p1, rows, cols = table.shape
+    if rows == 1:                                      # key padding alone: one row per table
+        return np.ascontiguousarray(table.reshape(p0, p1, cols)), (p0, p1)
+    return np.ascontiguousarray(table), (p0, p1)
 
 
 def roi_level_thresholds(k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6):
@@ -1378,7 +1464,7 @@ class MatMul(_Handle):
     _OP, _INFO, _ROUTES = "dfx_bmm", BmmInfo, 1
 
     def __init__(self, batch, m, n, k, a_dtype=np.uint8, dst_dtype=np.int8, trans_b=True, a_strides=None, b_strides=None,
-                 c_strides=None, relu=False, rm=ROUND_NEAREST, nscales=1, b_dtype=np.int8, force_path=BMM_AUTO, scales=None):
+                 c_strides=None, relu=False, rm=ROUND_NEAREST, nscales=1, b_dtype=np.int8, force_path=BMM_AUTO, scales=None, bias=None):
         code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
         batch0, batch1 = (1, batch) if isinstance(batch, int) else batch
         brows, bcols = (n, k) if trans_b else (k, n)
@@ -1397,12 +1483,25 @@ class MatMul(_Handle):
         self._create(d)
         if scales is not None:
             self.set_scales(scales)
+        if bias is not None:
+            self.set_bias(*bias) if isinstance(bias, tuple) else self.set_bias(bias)
 
     def set_scales(self, scales):
         """1 or n floats (the descriptor's nscales); may be called again"""
         s = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
         assert s.size == self.desc.nscales, (s.size, self.desc.nscales)
         _check(lib().dfx_bmm_set_scales(self._h, _p(s)))
+
+    def set_bias(self, table, periods=(1, 1), strides=None):
+        """the logit bias (include/dfx.h, dfx_logit_bias_desc): f32 values in ACCUMULATOR units added before the scale, finite
+        or -inf; matrix (b0, b1) uses table (b0 % periods[0], b1 % periods[1]).  strides None: a dense {p0, p1, m, n} table,
+        or {p0, p1, n} for one row broadcast over m; else (s0, s1, ld) in floats over the flat table (ld 0: one row).  The
+        values are copied; may be called again; table None clears the bias.  Not while a submit is in flight."""
+        if table is None:
+            _check(lib().dfx_bmm_set_bias(self._h, None, None))
+            return
+        b, t = _logit_bias_args(table, periods, strides, self.desc.m, self.desc.n)
+        _check(lib().dfx_bmm_set_bias(self._h, ctypes.byref(b), _p(t)))
 
     def submit(self, a_dev, b_dev, c_dev, stream=None):
         """asynchronous; torch CUDA tensors (or raw pointers)"""
@@ -1420,7 +1519,7 @@ class Attention(_Handle):
 
     def __init__(self, batch, tq, tk, d, dv, q_dtype=np.int8, dst_dtype=np.int8, q_strides=None, k_strides=None, v_strides=None,
                  o_strides=None, relu=False, rm=ROUND_NEAREST, nscales=1, prob_scale=255.0, k_dtype=np.int8, v_dtype=np.int8,
-                 force_path=ATTN_AUTO, table=None, logit_scale=None, out_scales=None):
+                 force_path=ATTN_AUTO, table=None, logit_scale=None, out_scales=None, bias=None):
         code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
         batch0, batch1 = (1, batch) if isinstance(batch, int) else batch
 
@@ -1442,6 +1541,8 @@ class Attention(_Handle):
             self.set_table(table)
         if logit_scale is not None and out_scales is not None:
             self.set_scales(logit_scale, out_scales)
+        if bias is not None:
+            self.set_bias(*bias) if isinstance(bias, tuple) else self.set_bias(bias)
 
     def set_table(self, table):
         """256 uint32 entries (softmax_table(step, tk)); may be called again"""
@@ -1455,8 +1556,17 @@ class Attention(_Handle):
         assert s.size == self.desc.nscales, (s.size, self.desc.nscales)
         _check(lib().dfx_attn_set_scales(self._h, ctypes.c_float(float(np.float32(logit_scale))), _p(s)))
 
+    def set_bias(self, table, periods=(1, 1), strides=None):
+        """the logit bias of Q . K^T (include/dfx.h): MatMul.set_bias with m = tq, n = tk; attention_bias() builds the table
+        from a relative-position bias, a window mask and a key-padding mask.  table None clears it."""
+        if table is None:
+            _check(lib().dfx_attn_set_bias(self._h, None, None))
+            return
+        b, t = _logit_bias_args(table, periods, strides, self.desc.tq, self.desc.tk)
+        _check(lib().dfx_attn_set_bias(self._h, ctypes.byref(b), _p(t)))
+
     def requant(self):
-        """(logits route, context route) as the last set_scales proved them; (-1, -1) before it"""
+        """(logits route, context route) as the last set_scales / set_bias proved them; (-1, -1) before set_scales"""
         i = self.info()
         return i.route_logits, i.route_context
 

@@ -43,10 +43,21 @@ struct AttnArgs {
   int pitch;                   // bytes per strip row
   int vtiles, kparts;          // context: column tiles of 32, key parts (attn_plan.h)
   int o_vec;                   // 4 adjacent j leave as one store (o, ldo and O's batch strides allow it)
+  // the logit bias (bias_plan.h): the handle's device image {bias_p0 * bias_p1, bias_rows, bias_cols} f32, or nullptr
+  const float *bias;
+  int bias_p0, bias_p1;        // periods over batch0 / batch1
+  int bias_rows, bias_cols;    // tq, or 1 (one row broadcast over tq); tk rounded up to 32
 };
 
-template <int DST, bool FL, bool FO>
-__global__ __launch_bounds__(ATTN_THREADS) void attn_fused_kernel(AttnArgs a) {
+// BIAS: the logits' requant adds the logit bias's entry (a.bias is set), as dfx_bmm's epilogue does; the instances without
+// it are the kernel as it was before the bias existed.
+// amdgpu_waves_per_eu: the unbiased instances take 164 or 168 VGPRs (AGPRs included), three waves per SIMD; the 16 VGPRs of the
+// tile's bias quads took the biased ones to 184 - 200, TWO waves per SIMD, i.e. two workgroups per CU instead of three, and every
+// point with more than 512 strips paid for it (ViT-B bs 8: 672 strips, 1.50x the unbiased time; bs 64: 1.28x).  Asked for three
+// waves the compiler fits the biased instances into 157 - 161 VGPRs without scratch.  The argument depends on BIAS so that
+// the unbiased instances stay as they were (1 is the default's lower bound: profiles/attn/bias_codegen.txt).
+template <int DST, bool FL, bool FO, bool BIAS>
+__global__ __launch_bounds__(ATTN_THREADS) __attribute__((amdgpu_waves_per_eu(BIAS ? 3 : 1))) void attn_fused_kernel(AttnArgs a) {
   constexpr int ESZ = (DST == DFX_F32 || DST == DFX_S32) ? 4 : 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char attn_lds[];
   unsigned *const tab = reinterpret_cast<unsigned *>(attn_lds);
@@ -89,9 +100,19 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_fused_kernel(AttnArgs a) {
       qf[s] = zero4;
       if (s < nds && 32 * s + 16 * h < a.d) qf[s] = *reinterpret_cast<const v4i *>(qrow + 32 * s) ^ qx80;
     }
+    // this lane's row of the bias: the strip's clamped query row, as Q's is
+    const float *biasrow = nullptr;
+    if constexpr (BIAS) biasrow = bmm_bias_row(a.bias, a.bias_p0, a.bias_p1, a.bias_rows, a.bias_cols, b0, b1, min(m0 + l31, a.tq - 1)) + 4 * h;
     for (int kt = wave; kt < nkt; kt += ATTN_WAVES) {
       const int n0 = 32 * kt;
       const signed char *const krow = kg + (size_t)min(n0 + l31, a.tk - 1) * (size_t)a.ldk + 16 * h;
+      // the tile's four quads of bias, n0 + 8 q + 4 h .. + 3, issued ahead of the MFMA loop (n0 + 31 < up32(tk) = bias_cols:
+      // inside the padded image row, 16-byte aligned)
+      v4f bq[4];
+      if constexpr (BIAS) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const v4f *>(biasrow + n0 + 8 * q);
+      }
       v16i acc;
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[i] = 0;
@@ -117,7 +138,9 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_fused_kernel(AttnArgs a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int a4[4] = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-        const v4i out = gc_quarter<DFX_S8, FL>(a4, v4f{0.0f, 0.0f, 0.0f, 0.0f}, ls4, false, a.rm);
+        v4f bias4 = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (BIAS) bias4 = bq[q];
+        const v4i out = gc_quarter<DFX_S8, FL>(a4, bias4, ls4, false, a.rm);
         // (n0 + 31 < up32(tk) <= pitch: inside the row)
         *reinterpret_cast<int *>(strip + l31 * a.pitch + n0 + 8 * q + 4 * h) = out[0];
       }

@@ -14,10 +14,11 @@
 #include "dfx_internal.h"
 #include "attn.cuh"
 #include "attn_plan.h"
+#include "bias_plan.h"
 #include "requant_host.h"
 
 namespace dfx {
-int launch_attn_fused(const AttnArgs &a, int grid, int lds, hipStream_t s, int mode, bool fast_logits, bool fast_context);
+int launch_attn_fused(const AttnArgs &a, int grid, int lds, hipStream_t s, int mode, bool fast_logits, bool fast_context, bool bias);
 }
 using namespace dfx;
 
@@ -42,6 +43,14 @@ struct dfx_attn {
   uint32_t table[256] = {};
   float logit_scale = 0.0f;
   std::vector<float> out_scales;
+  // the logit bias (of the logits' product, bias_plan.h): the fused kernel's device image, on handles whose plan is the fused
+  // kernel only (the chain's bmm_l owns its own), and, only until the chain exists, the host copy of the caller's table in
+  // its own layout, from which ensure_chain gives it to the chain
+  float *d_bias = nullptr;
+  bool bias_set = false;
+  dfx_logit_bias_desc bias = {};
+  BiasScan bias_scan;
+  std::vector<float> bias_host;
   TwoLaunchOrder order;
   char kernel_name[96] = "";
 };
@@ -56,14 +65,27 @@ long long grid_cap() {
   return e ? std::max(1ll, atoll(e)) : 0;
 }
 
+// (AUTO RULE with a logit bias -- include/dfx.h DFX_ATTN_AUTO_NOTE, DESIGN.md section 4.22, profiles/attn/bench_attn_bias.txt: the
+// biased fused kernel beat the biased chain at every point of the unbiased rule's box and lost where the unbiased one loses,
+// so the box is the same and a bias does not change the handle's plan, h->path.)
 void set_name(dfx_attn *h) {
   const dfx_attn_desc &d = h->d;
   const char *which = h->path == DFX_ATTN_FUSED ? "attn_fused" : "attn_chain";
+  const char *bias = h->bias_set ? " +bias" : "";
   if (!h->scales_set.load())
-    snprintf(h->kernel_name, sizeof(h->kernel_name), "%s<%s,%s> (no scales)", which, dt_name(d.q_dt), dt_name(d.dst_dt));
+    snprintf(h->kernel_name, sizeof(h->kernel_name), "%s<%s,%s> (no scales)%s", which, dt_name(d.q_dt), dt_name(d.dst_dt), bias);
   else
-    snprintf(h->kernel_name, sizeof(h->kernel_name), "%s<%s,%s> %s/%s", which, dt_name(d.q_dt), dt_name(d.dst_dt),
-             h->route_l ? "fast" : "exact", h->route_o ? "fast" : "exact");
+    snprintf(h->kernel_name, sizeof(h->kernel_name), "%s<%s,%s> %s/%s%s", which, dt_name(d.q_dt), dt_name(d.dst_dt),
+             h->route_l ? "fast" : "exact", h->route_o ? "fast" : "exact", bias);
+}
+
+// both routes from the shape, the scales and the bias as the handle holds them now: whichever setter came last
+void prove_routes(dfx_attn *h) {
+  if (!h->scales_set.load()) return;
+  const dfx_attn_desc &d = h->d;
+  const bool fl = h->bias_set ? bmm_fast_ok_biased(attn_bmm_logits(d), &h->logit_scale, h->bias_scan) : attn_fast_logits(d, h->logit_scale);
+  h->route_l = fl && fast_allowed() ? 1 : 0;
+  h->route_o = attn_fast_context(d, h->out_scales.data()) && fast_allowed() ? 1 : 0;
 }
 
 void drop_chain(dfx_attn *h) {
@@ -97,10 +119,12 @@ int ensure_chain(dfx_attn *h) {
   if (h->table_set.load()) rc = dfx_head_set_table(h->head, h->table);
   if (rc == DFX_OK && h->scales_set.load()) rc = dfx_bmm_set_scales(h->bmm_l, &h->logit_scale);
   if (rc == DFX_OK && h->scales_set.load()) rc = dfx_bmm_set_scales(h->bmm_o, h->out_scales.data());
+  if (rc == DFX_OK && h->bias_set) rc = dfx_bmm_set_bias(h->bmm_l, &h->bias, h->bias_host.data());
   if (rc != DFX_OK) {
     drop_chain(h);
     return rc;
   }
+  std::vector<float>().swap(h->bias_host);  // bmm_l has it now; later set_bias calls forward to it
   h->chain_ready.store(1);
   return DFX_OK;
 }
@@ -109,6 +133,7 @@ void release(dfx_attn *h) {
   drop_chain(h);
   (void)hipFree(h->d_table);
   (void)hipFree(h->d_oscale);
+  (void)hipFree(h->d_bias);
   h->order.destroy();
   delete h;
 }
@@ -173,8 +198,8 @@ int dfx_attn_create(const dfx_attn_desc *desc, dfx_attn_t **out) {
   a.vtiles = (int)attn_vtiles(d);  // (dv <= 2^31 - 32)
   a.kparts = attn_kparts(d);
   if (h->fused_ok) {  // more than 64 KiB of LDS is dynamic and has to be admitted per instance
-    for (int r = 0; r < 4; ++r) {
-      const int rc2 = launch_attn_fused(a, 0, h->lds, nullptr, 1, (r & 1) != 0, (r & 2) != 0);
+    for (int r = 0; r < 8; ++r) {
+      const int rc2 = launch_attn_fused(a, 0, h->lds, nullptr, 1, (r & 1) != 0, (r & 2) != 0, (r & 4) != 0);
       if (rc2 != 0) {
         (void)hipGetLastError();
         release(h);
@@ -220,9 +245,70 @@ int dfx_attn_set_scales(dfx_attn_t *h, float logit_scale, const float *out_scale
   h->args.logit_scale = logit_scale;
   h->logit_scale = logit_scale;
   h->out_scales.assign(out_scales, out_scales + d.nscales);
-  h->route_l = attn_fast_logits(d, logit_scale) && fast_allowed() ? 1 : 0;
-  h->route_o = attn_fast_context(d, out_scales) && fast_allowed() ? 1 : 0;
   h->scales_set.store(1);
+  prove_routes(h);
+  set_name(h);
+  return DFX_OK;
+}
+
+int dfx_attn_set_bias(dfx_attn_t *h, const dfx_logit_bias_desc *desc, const float *host_table) {
+  if (!h) return fail(DFX_ERR_INVALID, "attn_set_bias: null argument");
+  std::lock_guard<std::mutex> lk(h->order.mu);
+  DeviceGuard dg(h->device);
+  if (!desc) {  // clear: the handle gives its former bits
+    if (h->chain_ready.load()) {
+      const int rc = dfx_bmm_set_bias(h->bmm_l, nullptr, nullptr);
+      if (rc) return rc;
+    }
+    (void)hipFree(h->d_bias);
+    h->d_bias = nullptr;
+    h->bias_set = false;
+    h->args.bias = nullptr;
+    std::vector<float>().swap(h->bias_host);
+    prove_routes(h);
+    set_name(h);
+    return DFX_OK;
+  }
+  if (!host_table) return fail(DFX_ERR_INVALID, "attn_set_bias: null table");
+  const dfx_bmm_desc bl = attn_bmm_logits(h->d);
+  const char *why = "";
+  int rc = bias_validate(bl, *desc, &why);
+  if (rc) return fail(rc, "attn_set_bias: %s", why);
+  BiasScan scan;
+  if (bias_scan(bl, *desc, host_table, &scan) != DFX_OK) return fail(DFX_ERR_INVALID, "attn_set_bias: +inf or NaN in the table (finite values and -inf)");
+  const bool fused_plan = h->path == DFX_ATTN_FUSED;  // (then fused_ok: attn_validate; any other handle only ever runs the chain)
+  std::vector<float> img, host;
+  try {
+    if (!h->chain_ready.load()) host.assign(host_table, host_table + bias_host_elems(bl, *desc));
+    if (fused_plan) img.resize((size_t)bias_image_elems(bl, *desc));
+  } catch (const std::bad_alloc &) {
+    return fail(DFX_ERR_HIP, "out of host memory");
+  }
+  float *fresh = nullptr;  // the handle keeps its former bias if anything below fails
+  if (fused_plan) {         // the fused kernel's own image
+    bias_fill_image(bl, *desc, host_table, img.data());
+    hipError_t e = hipMalloc((void **)&fresh, img.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(fresh, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(fresh);
+      return fail(DFX_ERR_HIP, "attn_set_bias: the table's image: %s", hipGetErrorString(e));
+    }
+  }
+  if (h->chain_ready.load() && (rc = dfx_bmm_set_bias(h->bmm_l, desc, host_table)) != DFX_OK) {
+    (void)hipFree(fresh);
+    return rc;
+  }
+  (void)hipFree(h->d_bias);
+  h->d_bias = fresh;
+  h->bias = *desc;
+  h->bias_scan = scan;
+  h->bias_host.swap(host);
+  h->bias_set = true;
+  AttnArgs &a = h->args;
+  a.bias = h->d_bias;
+  a.bias_p0 = desc->period0; a.bias_p1 = desc->period1;
+  a.bias_rows = (int)bias_rows(bl, *desc); a.bias_cols = (int)bias_cols(bl);
+  prove_routes(h);
   set_name(h);
   return DFX_OK;
 }
@@ -249,7 +335,7 @@ int dfx_attn_submit(dfx_attn_t *h, const void *q_dev, const void *k_dev, const v
     a.v = (const signed char *)v_dev;
     a.o = (unsigned char *)o_dev;
     a.o_vec = po % (4 * esz) == 0 && d.ldo % 4 == 0 && d.o_s0 % 4 == 0 && d.o_s1 % 4 == 0;
-    if (launch_attn_fused(a, h->grid, h->lds, (hipStream_t)s, 0, h->route_l != 0, h->route_o != 0) != 0)
+    if (launch_attn_fused(a, h->grid, h->lds, (hipStream_t)s, 0, h->route_l != 0, h->route_o != 0, a.bias != nullptr) != 0)
       return fail(DFX_ERR_UNSUPPORTED, "attn_submit: no kernel instance for this op");
     HIP_TRY(hipGetLastError());
   } else {
@@ -289,7 +375,7 @@ int dfx_attn_query(const dfx_attn_t *h, dfx_attn_info *info) {
   info->route_context = h->scales_set.load() ? h->route_o : -1;
   info->scratch_bytes = h->chain_ready.load() ? attn_scratch_bytes(h->d) : 0;
   info->algorithmic_ops = attn_algorithmic_ops(h->d);
-  info->algorithmic_bytes = attn_algorithmic_bytes(h->d);
+  info->algorithmic_bytes = attn_algorithmic_bytes(h->d) + (h->bias_set ? bias_distinct_bytes(attn_bmm_logits(h->d), h->bias) : 0);
   memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }

@@ -46,6 +46,31 @@ struct BmmArgs {
   long long items;           // generic: C elements
 };
 
+// the logit bias (bias_plan.h): the handle's device image {p0 * p1, rows, cols} f32
+struct BmmBiasArgs {
+  const float *img;
+  int p0, p1;                // periods over batch0 / batch1
+  int rows, cols;            // m, or 1 (one row broadcast over m); n rounded up to 32
+};
+// The argument of the BIASED instances of both kernels.  The kernels are templates over their argument type: the unbiased
+// instances take BmmArgs itself, so their argument segment and their code are what they were before the bias existed (the
+// hidden grid size stays in the segment's third 64-byte line: one line more to fetch showed as 2.4 % at the ViT-B bs 8 P.V
+// point of tools/bench_bmm when the bias's fields sat in BmmArgs).
+struct BmmBiasedArgs : BmmArgs {
+  BmmBiasArgs bias;
+};
+template <class ARGS>
+struct bmm_biased { static constexpr bool value = false; };
+template <>
+struct bmm_biased<BmmBiasedArgs> { static constexpr bool value = true; };
+
+// bias_plan.h's image index: the row of matrix (b0, b1)'s table that C's row m uses (m < the operand's rows).  b0 < batch0 and
+// b1 < batch1 fit an int: the two remainders are 32-bit ones
+__device__ __forceinline__ const float *bmm_bias_row(const float *img, int p0, int p1, int rows, int cols, long long b0, long long b1, int m) {
+  const long long t = (long long)((unsigned)b0 % (unsigned)p0) * p1 + (long long)((unsigned)b1 % (unsigned)p1);
+  return img + (size_t)((t * rows + (rows == 1 ? 0 : m)) * cols);
+}
+
 // bytes >= nv of a 16-byte piece zeroed (0 <= nv <= 16)
 __device__ __forceinline__ v4i bmm_mask16(v4i v, int nv) {
 #pragma unroll
@@ -76,8 +101,10 @@ __device__ __forceinline__ unsigned char *bmm_nn_images() {
   }
 }
 
-template <bool NT, int DST, bool FAST>
-__global__ __launch_bounds__(BMM_THREADS) void bmm_mfma_kernel(BmmArgs a) {
+// ARGS: BmmArgs, or BmmBiasedArgs: the epilogue's requant then adds the logit bias's entry
+template <bool NT, int DST, bool FAST, class ARGS>
+__global__ __launch_bounds__(BMM_THREADS) void bmm_mfma_kernel(ARGS a) {
+  constexpr bool BIAS = bmm_biased<ARGS>::value;
   constexpr int ESZ = (DST == DFX_F32 || DST == DFX_S32) ? 4 : 1;
   unsigned char *const bmm_lds = bmm_nn_images<NT>();  // (the NT instances have no LDS at all)
   const int tid = threadIdx.x, lane = tid & 63;
@@ -125,6 +152,15 @@ __global__ __launch_bounds__(BMM_THREADS) void bmm_mfma_kernel(BmmArgs a) {
       }
     };
 
+    // the lane's four quads of bias, n0 + 8 q + 4 h .. + 3 of its row m, issued ahead of the K loop (the row clamped as A's is;
+    // n0 + 31 < up32(n) = bias_cols: inside the padded image row, 16-byte aligned)
+    v4f bq[4];
+    if constexpr (BIAS) {
+      const float *const brw = bmm_bias_row(a.bias.img, a.bias.p0, a.bias.p1, a.bias.rows, a.bias.cols, b0, b1, min(m0 + l31, a.m - 1)) + n0 + 4 * h;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const v4f *>(brw + 8 * q);
+    }
+
     v16i acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0;
@@ -170,7 +206,9 @@ __global__ __launch_bounds__(BMM_THREADS) void bmm_mfma_kernel(BmmArgs a) {
       const int a4[4] = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
       const int n = n0 + nl;
       if (!live || mrow >= a.m || n >= a.n) continue;
-      const v4i out = gc_quarter<DST, FAST>(a4, v4f{0.0f, 0.0f, 0.0f, 0.0f}, *reinterpret_cast<const v4f *>(a.scale + n), relu, a.rm);
+      v4f bias4 = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+      if constexpr (BIAS) bias4 = bq[q];
+      const v4i out = gc_quarter<DST, FAST>(a4, bias4, *reinterpret_cast<const v4f *>(a.scale + n), relu, a.rm);
       const int left = min(4, a.n - n);
       if constexpr (ESZ == 1) {
         unsigned char *const p = a.c + cbase + n;

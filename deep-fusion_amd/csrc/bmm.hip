@@ -4,7 +4,10 @@
 
 namespace dfx {
 
-__global__ __launch_bounds__(BMM_THREADS) void bmm_generic_kernel(BmmArgs a) {
+// ARGS: BmmArgs, or BmmBiasedArgs: requant's bias slot then holds the logit bias's entry
+template <class ARGS>
+__global__ __launch_bounds__(BMM_THREADS) void bmm_generic_kernel(ARGS a) {
+  constexpr bool BIAS = bmm_biased<ARGS>::value;
   const long long stride = (long long)gridDim.x * blockDim.x;
   const long long per = (long long)a.m * a.n;
   for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < a.items; id += stride) {
@@ -19,7 +22,9 @@ __global__ __launch_bounds__(BMM_THREADS) void bmm_generic_kernel(BmmArgs a) {
       for (int k = 0; k < a.k; ++k) acc += (int)ap[k] * (int)bp[(size_t)(k * bstep)];
     else
       for (int k = 0; k < a.k; ++k) acc += (int)(signed char)ap[k] * (int)bp[(size_t)(k * bstep)];
-    const float f = requant(acc, 0.0f, a.scale[n], a.relu != 0);
+    float bias = 0.0f;
+    if constexpr (BIAS) bias = bmm_bias_row(a.bias.img, a.bias.p0, a.bias.p1, a.bias.rows, a.bias.cols, b0, b1, (int)m)[n];
+    const float f = requant(acc, bias, a.scale[n], a.relu != 0);
     const size_t ci = (size_t)(b0 * a.c_s0 + b1 * a.c_s1 + m * a.ldc + n);
     switch (a.dst_dt) {
       case DFX_F32: reinterpret_cast<float *>(a.c)[ci] = f; break;
@@ -30,31 +35,45 @@ __global__ __launch_bounds__(BMM_THREADS) void bmm_generic_kernel(BmmArgs a) {
   }
 }
 
+static BmmBiasedArgs bmm_with(const BmmArgs &a, const BmmBiasArgs &bias) {
+  BmmBiasedArgs b;
+  static_cast<BmmArgs &>(b) = a;
+  b.bias = bias;
+  return b;
+}
+
 template <bool NT, int DST>
-static int bmm_one(const BmmArgs &a, int grid, hipStream_t s, bool fast) {
-  if (fast) bmm_mfma_kernel<NT, DST, true><<<grid, BMM_THREADS, 0, s>>>(a);
-  else bmm_mfma_kernel<NT, DST, false><<<grid, BMM_THREADS, 0, s>>>(a);
+static int bmm_one(const BmmArgs &a, const BmmBiasArgs *bias, int grid, hipStream_t s, bool fast) {
+  if (bias) {
+    const BmmBiasedArgs b = bmm_with(a, *bias);
+    if (fast) bmm_mfma_kernel<NT, DST, true, BmmBiasedArgs><<<grid, BMM_THREADS, 0, s>>>(b);
+    else bmm_mfma_kernel<NT, DST, false, BmmBiasedArgs><<<grid, BMM_THREADS, 0, s>>>(b);
+  } else {
+    if (fast) bmm_mfma_kernel<NT, DST, true, BmmArgs><<<grid, BMM_THREADS, 0, s>>>(a);
+    else bmm_mfma_kernel<NT, DST, false, BmmArgs><<<grid, BMM_THREADS, 0, s>>>(a);
+  }
   return 0;
 }
 
 template <bool NT>
-static int bmm_form(const BmmArgs &a, int grid, hipStream_t s, bool fast) {
+static int bmm_form(const BmmArgs &a, const BmmBiasArgs *bias, int grid, hipStream_t s, bool fast) {
   switch (a.dst_dt) {
-    case DFX_F32: return bmm_one<NT, DFX_F32>(a, grid, s, fast);
-    case DFX_S32: return bmm_one<NT, DFX_S32>(a, grid, s, fast);
-    case DFX_S8: return bmm_one<NT, DFX_S8>(a, grid, s, fast);
-    case DFX_U8: return bmm_one<NT, DFX_U8>(a, grid, s, fast);
+    case DFX_F32: return bmm_one<NT, DFX_F32>(a, bias, grid, s, fast);
+    case DFX_S32: return bmm_one<NT, DFX_S32>(a, bias, grid, s, fast);
+    case DFX_S8: return bmm_one<NT, DFX_S8>(a, bias, grid, s, fast);
+    case DFX_U8: return bmm_one<NT, DFX_U8>(a, bias, grid, s, fast);
   }
   return -1;
 }
 
-// -1: no such instance
-int launch_bmm_mfma(const BmmArgs &a, int grid, hipStream_t s, bool fast) {
-  return a.trans_b ? bmm_form<true>(a, grid, s, fast) : bmm_form<false>(a, grid, s, fast);
+// -1: no such instance.  bias: nullptr, or the logit bias of the biased kernels
+int launch_bmm_mfma(const BmmArgs &a, const BmmBiasArgs *bias, int grid, hipStream_t s, bool fast) {
+  return a.trans_b ? bmm_form<true>(a, bias, grid, s, fast) : bmm_form<false>(a, bias, grid, s, fast);
 }
 
-int launch_bmm_generic(const BmmArgs &a, int grid, hipStream_t s) {
-  bmm_generic_kernel<<<grid, BMM_THREADS, 0, s>>>(a);
+int launch_bmm_generic(const BmmArgs &a, const BmmBiasArgs *bias, int grid, hipStream_t s) {
+  if (bias) bmm_generic_kernel<BmmBiasedArgs><<<grid, BMM_THREADS, 0, s>>>(bmm_with(a, *bias));
+  else bmm_generic_kernel<BmmArgs><<<grid, BMM_THREADS, 0, s>>>(a);
   return 0;
 }
 

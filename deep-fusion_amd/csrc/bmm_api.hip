@@ -1,6 +1,7 @@
 // bmm_api.hip -- host side of the batched int8 matrix product (dfx_bmm_* of include/dfx.h): descriptor validation, the
 // path and the grids (all planned in bmm_plan.h), the device copy of the scales with the requant route proved from the
-// shape, the overlap check and the choice of the kernel per submit, launches.  The kernels are in bmm.cuh / bmm.hip.
+// shape, the logit bias's device image (planned in bias_plan.h) and the route proved again with it, the overlap check and the
+// choice of the kernel per submit, launches.  The kernels are in bmm.cuh / bmm.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,11 +14,12 @@
 #include "dfx_internal.h"
 #include "bmm.cuh"
 #include "bmm_plan.h"
+#include "bias_plan.h"
 #include "requant_host.h"
 
 namespace dfx {
-int launch_bmm_mfma(const BmmArgs &a, int grid, hipStream_t s, bool fast);
-int launch_bmm_generic(const BmmArgs &a, int grid, hipStream_t s);
+int launch_bmm_mfma(const BmmArgs &a, const BmmBiasArgs *bias, int grid, hipStream_t s, bool fast);
+int launch_bmm_generic(const BmmArgs &a, const BmmBiasArgs *bias, int grid, hipStream_t s);
 }
 using namespace dfx;
 
@@ -31,6 +33,13 @@ struct dfx_bmm {
   int n_pad = 0;
   std::atomic<int> scales_set{0};
   int route = 0;               // 0 exact, 1 fast (dfx_debug_conv_requant's numbering); MFMA path only
+  std::vector<float> scales;   // the host copy of the last set_scales: set_bias proves the route again from it
+  // the logit bias: the device image and the biased kernels' second argument, its layout and what the scan of its entries found
+  float *d_bias = nullptr;
+  BmmBiasArgs bias_args = {};
+  bool bias_set = false;
+  dfx_logit_bias_desc bias = {};
+  BiasScan bias_scan;
   char kernel_name[96] = "";
 };
 
@@ -48,11 +57,19 @@ long long grid_cap() {
 void set_name(dfx_bmm *h) {
   const dfx_bmm_desc &d = h->d;
   const char *form = d.trans_b ? "nt" : "nn";
+  const char *bias = h->bias_set ? " +bias" : "";
   if (h->path == DFX_BMM_MFMA)
-    snprintf(h->kernel_name, sizeof(h->kernel_name), "bmm_mfma<%s,%s,%s> %s", form, dt_name(d.a_dt), dt_name(d.dst_dt),
-             !h->scales_set.load() ? "(no scales)" : h->route ? "fast" : "exact");
+    snprintf(h->kernel_name, sizeof(h->kernel_name), "bmm_mfma<%s,%s,%s> %s%s", form, dt_name(d.a_dt), dt_name(d.dst_dt),
+             !h->scales_set.load() ? "(no scales)" : h->route ? "fast" : "exact", bias);
   else
-    snprintf(h->kernel_name, sizeof(h->kernel_name), "bmm_generic<%s,%s,%s> exact", form, dt_name(d.a_dt), dt_name(d.dst_dt));
+    snprintf(h->kernel_name, sizeof(h->kernel_name), "bmm_generic<%s,%s,%s> exact%s", form, dt_name(d.a_dt), dt_name(d.dst_dt), bias);
+}
+
+// the requant route from the shape, the scales and the bias as the handle holds them now: whichever setter came last
+void prove_route(dfx_bmm *h) {
+  if (!h->scales_set.load()) return;
+  const bool ok = h->bias_set ? bmm_fast_ok_biased(h->d, h->scales.data(), h->bias_scan) : bmm_fast_ok(h->d, h->scales.data());
+  h->route = h->path == DFX_BMM_MFMA && ok && fast_allowed() ? 1 : 0;
 }
 
 }  // namespace
@@ -111,11 +128,55 @@ int dfx_bmm_set_scales(dfx_bmm_t *h, const float *scales) {
   const dfx_bmm_desc &d = h->d;
   std::vector<float> img((size_t)h->n_pad, 0.0f);  // (the entries n .. n_pad - 1 stay 0)
   for (int i = 0; i < d.n; ++i) img[i] = scales[d.nscales == 1 ? 0 : i];
-  const bool fast = h->path == DFX_BMM_MFMA && bmm_fast_ok(d, scales) && fast_allowed();
   DeviceGuard dg(h->device);
   HIP_TRY(hipMemcpy(h->d_scale, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-  h->route = fast ? 1 : 0;
+  h->scales.assign(scales, scales + d.nscales);
   h->scales_set.store(1);
+  prove_route(h);
+  set_name(h);
+  return DFX_OK;
+}
+
+int dfx_bmm_set_bias(dfx_bmm_t *h, const dfx_logit_bias_desc *desc, const float *host_table) {
+  if (!h) return fail(DFX_ERR_INVALID, "bmm_set_bias: null argument");
+  DeviceGuard dg(h->device);
+  if (!desc) {  // clear: the handle gives its former bits
+    (void)hipFree(h->d_bias);
+    h->d_bias = nullptr;
+    h->bias_set = false;
+    h->bias_args = BmmBiasArgs{};
+    prove_route(h);
+    set_name(h);
+    return DFX_OK;
+  }
+  if (!host_table) return fail(DFX_ERR_INVALID, "bmm_set_bias: null table");
+  const dfx_bmm_desc &d = h->d;
+  const char *why = "";
+  const int rc = bias_validate(d, *desc, &why);
+  if (rc) return fail(rc, "bmm_set_bias: %s", why);
+  BiasScan scan;
+  if (bias_scan(d, *desc, host_table, &scan) != DFX_OK) return fail(DFX_ERR_INVALID, "bmm_set_bias: +inf or NaN in the table (finite values and -inf)");
+  std::vector<float> img;
+  try {
+    img.resize((size_t)bias_image_elems(d, *desc));
+  } catch (const std::bad_alloc &) {
+    return fail(DFX_ERR_HIP, "out of host memory");
+  }
+  bias_fill_image(d, *desc, host_table, img.data());
+  float *fresh = nullptr;  // the handle keeps its former bias if anything below fails
+  hipError_t e = hipMalloc((void **)&fresh, img.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(fresh, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(fresh);
+    return fail(DFX_ERR_HIP, "bmm_set_bias: the table's image: %s", hipGetErrorString(e));
+  }
+  (void)hipFree(h->d_bias);
+  h->d_bias = fresh;
+  h->bias = *desc;
+  h->bias_scan = scan;
+  h->bias_set = true;
+  h->bias_args = BmmBiasArgs{h->d_bias, desc->period0, desc->period1, (int)bias_rows(d, *desc), (int)bias_cols(d)};
+  prove_route(h);
   set_name(h);
   return DFX_OK;
 }
@@ -138,8 +199,10 @@ int dfx_bmm_submit(dfx_bmm_t *h, const void *a_dev, const void *b_dev, void *c_d
   a.b = (const signed char *)b_dev;
   a.c = (unsigned char *)c_dev;
   a.c_vec = pc % (4 * esz) == 0 && d.ldc % 4 == 0 && d.c_s0 % 4 == 0 && d.c_s1 % 4 == 0;
-  const int rc = path == DFX_BMM_MFMA ? launch_bmm_mfma(a, h->grid[path], (hipStream_t)s, h->route != 0)
-                                      : launch_bmm_generic(a, h->grid[path], (hipStream_t)s);
+  const BmmBiasArgs bias = h->bias_args;  // (a copy, like a)
+  const BmmBiasArgs *const bp = h->bias_set ? &bias : nullptr;
+  const int rc = path == DFX_BMM_MFMA ? launch_bmm_mfma(a, bp, h->grid[path], (hipStream_t)s, h->route != 0)
+                                      : launch_bmm_generic(a, bp, h->grid[path], (hipStream_t)s);
   if (rc != 0) return fail(DFX_ERR_UNSUPPORTED, "bmm_submit: no kernel instance for this op");
   HIP_TRY(hipGetLastError());
   g_launches[path].fetch_add(1, std::memory_order_relaxed);
@@ -170,7 +233,7 @@ int dfx_bmm_query(const dfx_bmm_t *h, dfx_bmm_info *info) {
   info->lds_bytes = bmm_lds_bytes(h->d, h->path);
   info->device = h->device;
   info->algorithmic_ops = bmm_algorithmic_ops(h->d);
-  info->algorithmic_bytes = bmm_algorithmic_bytes(h->d);
+  info->algorithmic_bytes = bmm_algorithmic_bytes(h->d) + (h->bias_set ? bias_distinct_bytes(h->d, h->bias) : 0);
   memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
@@ -179,6 +242,7 @@ int dfx_bmm_destroy(dfx_bmm_t *h) {
   if (!h) return DFX_OK;
   DeviceGuard dg(h->device);
   (void)hipFree(h->d_scale);
+  (void)hipFree(h->d_bias);
   delete h;
   return DFX_OK;
 }

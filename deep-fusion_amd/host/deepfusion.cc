@@ -3050,9 +3050,23 @@ private:
 // ---- batched int8 matrix product (dfx_bmm_*): C[g] = requant(A[g] . B[g](^T)) over matrices that lie in three tensors at the
 // strides of matmul_shape.  a and b are registered as reads, c as a write (op_state).  One handle on one device:
 // DEEPFUSION_DEVICES does not shard this op (a head-sliced operand is not batch-major). ----
+// the dfx_logit_bias_desc of a logit_bias over {rows, cols} products, its table checked against what the layout addresses
+// (the library cannot: it only sees a pointer); a layout the library refuses anyway is passed on for it to say why
+static dfx_logit_bias_desc logit_bias_desc(const logit_bias &bias, long long rows, long long cols, const char *what) {
+  dfx_logit_bias_desc b;
+  b.period0 = bias.period0; b.period1 = bias.period1; b.s0 = bias.s0; b.s1 = bias.s1; b.ld = bias.ld;
+  if (bias.period0 >= 1 && bias.period1 >= 1 && bias.s0 >= 0 && bias.s1 >= 0 && bias.ld >= 0) {
+    const unsigned __int128 need = (unsigned __int128)(bias.period0 - 1) * (unsigned __int128)bias.s0 + (unsigned __int128)(bias.period1 - 1) * (unsigned __int128)bias.s1 +
+                                   (unsigned __int128)(bias.ld == 0 ? 0 : rows - 1) * (unsigned __int128)bias.ld + (unsigned __int128)cols;
+    if (need > (unsigned __int128)bias.table.size()) error_and_exit("Init %s op failed! (the logit bias's layout reaches beyond its table)", what);
+  }
+  return b;
+}
+
 class op_matmul : public op {
 public:
-  op_matmul(memory *a, memory *b, memory *c, const matmul_shape &sh, const std::vector<float> &scales, bool relu, round_mode rm)
+  op_matmul(memory *a, memory *b, memory *c, const matmul_shape &sh, const std::vector<float> &scales, bool relu, round_mode rm,
+            const logit_bias *bias = nullptr)
       : a_(a), b_(b), c_(c), h_(nullptr) {
     if (!a_ || !b_ || !c_) error_and_exit("Init MatMul op failed! (null tensor)");
     dfx_bmm_desc d;
@@ -3078,6 +3092,10 @@ public:
     if (a_end > (long long)a_->size() || b_end > (long long)b_->size() || c_end > (long long)c_->size())
       error_and_exit("Init MatMul op failed! (a matrix reaches beyond its tensor)");
     if (dfx_bmm_set_scales(h_, scales.data()) != DFX_OK) error_and_exit("Init MatMul op failed! (%s)", dfx_last_error());
+    if (bias) {
+      const dfx_logit_bias_desc bd = logit_bias_desc(*bias, sh.m, sh.n, "MatMul");
+      if (dfx_bmm_set_bias(h_, &bd, bias->table.data()) != DFX_OK) error_and_exit("Init MatMul op failed! (%s)", dfx_last_error());
+    }
     st_.ensure_stream();
   }
   ~op_matmul() override {
@@ -3121,7 +3139,7 @@ private:
 class op_attention : public op {
 public:
   op_attention(memory *q, memory *k, memory *v, const std::array<uint32_t, 256> &table, memory *o, const attention_shape &sh, float logit_scale,
-               const std::vector<float> &out_scales, float prob_scale, bool relu, round_mode rm)
+               const std::vector<float> &out_scales, float prob_scale, bool relu, round_mode rm, const logit_bias *bias = nullptr)
       : q_(q), k_(k), v_(v), o_(o), h_(nullptr) {
     if (!q_ || !k_ || !v_ || !o_) error_and_exit("Init Attention op failed! (null tensor)");
     dfx_attn_desc d;
@@ -3151,6 +3169,10 @@ public:
       error_and_exit("Init Attention op failed! (a matrix reaches beyond its tensor)");
     if (dfx_attn_set_table(h_, table.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
     if (dfx_attn_set_scales(h_, logit_scale, out_scales.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
+    if (bias) {
+      const dfx_logit_bias_desc bd = logit_bias_desc(*bias, sh.tq, sh.tk, "Attention");
+      if (dfx_attn_set_bias(h_, &bd, bias->table.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
+    }
     st_.ensure_stream();
   }
   ~op_attention() override {
@@ -3657,10 +3679,22 @@ std::unique_ptr<op> matmul(const std::unique_ptr<memory> &a, const std::unique_p
   return std::unique_ptr<op>(new op_matmul(a.get(), b.get(), c.get(), shape, scales, relu, rm));
 }
 
+std::unique_ptr<op> matmul(const std::unique_ptr<memory> &a, const std::unique_ptr<memory> &b, std::unique_ptr<memory> &c,
+                           const matmul_shape &shape, const std::vector<float> &scales, const logit_bias &bias, bool relu, round_mode rm) {
+  return std::unique_ptr<op>(new op_matmul(a.get(), b.get(), c.get(), shape, scales, relu, rm, &bias));
+}
+
 std::unique_ptr<op> attention(const std::unique_ptr<memory> &q, const std::unique_ptr<memory> &k, const std::unique_ptr<memory> &v,
                               const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &o, const attention_shape &shape,
                               float logit_scale, const std::vector<float> &out_scales, float prob_scale, bool relu, round_mode rm) {
   return std::unique_ptr<op>(new op_attention(q.get(), k.get(), v.get(), table, o.get(), shape, logit_scale, out_scales, prob_scale, relu, rm));
+}
+
+std::unique_ptr<op> attention(const std::unique_ptr<memory> &q, const std::unique_ptr<memory> &k, const std::unique_ptr<memory> &v,
+                              const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &o, const attention_shape &shape,
+                              float logit_scale, const std::vector<float> &out_scales, const logit_bias &bias, float prob_scale, bool relu,
+                              round_mode rm) {
+  return std::unique_ptr<op>(new op_attention(q.get(), k.get(), v.get(), table, o.get(), shape, logit_scale, out_scales, prob_scale, relu, rm, &bias));
 }
 
 std::unique_ptr<op> select_top_k(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &dst_idx, memory *dst_val,

@@ -12,7 +12,16 @@
 // MiB Infinity Cache); -rotate_mb 0 times one set over and over (warm caches).  Next to each time: the floor, Q, K, V and O read
 // or written once at the 8 TB/s HBM peak, and the strips (workgroups of the fused kernel) of the point.  The results of the two
 // legs are compared byte for byte.
-//   bench_attn [-iter 20] [-burning_iter 3] [-rounds 5] [-window_us 3000] [-rotate_mb 768] [-only <substring>]
+// BIASED LEGS (dfx_attn_set_bias): every point is also timed with a logit bias on both forced paths, the four legs alternating
+// in the same rounds on the same buffers: the Swin stage with one {T, T} table per (window, head) (period0 = nW = 64, period1 =
+// heads: relative-position bias plus a shifted-window mask), every other point with a key-padding row per image (period0 =
+// bs, period1 = 1, ld = 0: the last tenth of the keys masked).  Finite entries are +-32 logit steps, masked entries the finite
+// value of dfa.attention_bias (the fast route stays proved).  The two biased legs are compared byte for byte and must differ
+// from the unbiased result.  -bias 0 times the two unbiased legs alone, as before the bias existed.  -bias_table1 1 gives the
+// points that have a key-padding row ONE whole {T, T} table instead (periods 1, 1): every lane reads its own row of a table all
+// matrices share, where the row layout has all lanes of a wave read the same 16 bytes.
+// -t <T> (with -bs, -heads, -d) times ONE point of that shape instead of the six.
+//   bench_attn [-iter 20] [-bias 1] [-bias_table1 0] [-t 0 -bs 8 -heads 12 -d 64] [-burning_iter 3] [-rounds 5] [-window_us 3000] [-rotate_mb 768] [-only <substring>]
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -32,6 +41,8 @@ int main(int argc, char **argv) {
   const double window_us = f.geti("window_us", 3000);
   const std::string only = f.gets("only", "");
   const size_t rotate = (size_t)f.geti("rotate_mb", 768) << 20;
+  const int nleg = f.geti("bias", 1) ? 4 : 2;
+  const bool table1 = f.geti("bias_table1", 0) != 0;
   const struct { const char *n; int bs, heads, t, d; } nets[] = {{"ViT-B bs8", 8, 12, 197, 64}, {"ViT-B bs64", 64, 12, 197, 64},
                                                                  {"Swin 64x3 windows", 64, 3, 49, 32}, {"DETR bs2", 2, 8, 850, 32},
                                                                  {"non-local bs1", 1, 1, 4096, 256}, {"non-local bs4", 4, 1, 4096, 256}};
@@ -41,8 +52,13 @@ int main(int argc, char **argv) {
   dfx_event_t e0, e1;
   check(dfx_event_create(&e0), "event create");
   check(dfx_event_create(&e1), "event create");
-  const char *leg_name[2] = {"fused", "chain"};
-  for (const auto &n : nets) {
+  const char *leg_name[4] = {"fused", "chain", "fused+b", "chain+b"};
+  const int custom_t = f.geti("t", 0);
+  for (auto n : nets) {
+    if (custom_t > 0) {
+      if (std::string(n.n) != nets[0].n) continue;  // (once)
+      n.n = "custom"; n.bs = f.geti("bs", 8); n.heads = f.geti("heads", 12); n.t = custom_t; n.d = f.geti("d", 64);
+    }
     const std::string name = n.n;
     if (!only.empty() && name.find(only) == std::string::npos) continue;
     const AttnShape s = attn_heads(n.bs, n.heads, n.t, n.d, DFX_S8, DFX_S8);
@@ -69,13 +85,32 @@ int main(int argc, char **argv) {
     const float logit_scale = 40.0f / (74.0f * 74.0f * std::sqrt((float)s.d)), out_scale = 1.0f / 256.0f;
     std::vector<uint32_t> table(256);
     attn_softmax_table(table.data(), 0.0625, s.tk);
-    dfx_attn_t *h[2] = {nullptr, nullptr};
-    dfx_attn_info info[2];
-    for (int k = 0; k < 2; ++k) {
-      const dfx_attn_desc d = s.desc(1, k == 0 ? DFX_ATTN_FUSED : DFX_ATTN_CHAIN);
+    // the bias of the biased legs: whole tables per (window, head) at the Swin point, a key-padding row per image elsewhere
+    const bool windows = s.tq == 49;
+    dfx_logit_bias_desc bd;
+    bd.period0 = table1 && !windows ? 1 : s.batch0; bd.period1 = windows ? s.batch1 : 1;
+    bd.ld = windows || table1 ? s.tk : 0;
+    bd.s1 = windows ? (long long)s.tq * s.tk : 0;
+    bd.s0 = windows ? bd.s1 * s.batch1 : s.tk;
+    const float masked = -(128.0f * 128.0f * (float)s.d + std::ceil(129.0f / logit_scale));
+    std::vector<float> bias((size_t)bd.period0 * bd.period1 * (bd.ld ? s.tq : 1) * s.tk);
+    {
+      unsigned lcg = 12345u;
+      for (size_t i = 0; i < bias.size(); ++i) {
+        lcg = lcg * 1664525u + 1013904223u;
+        bias[i] = ((float)(lcg >> 8) / 16777216.0f * 64.0f - 32.0f) / logit_scale;
+        const int n = (int)(i % (size_t)s.tk);
+        if (windows ? (lcg >> 4) % 10 == 0 && n != 0 : n >= s.tk - s.tk / 10) bias[i] = masked;  // (key 0 of a window row is never masked)
+      }
+    }
+    dfx_attn_t *h[4] = {nullptr, nullptr, nullptr, nullptr};
+    dfx_attn_info info[4];
+    for (int k = 0; k < nleg; ++k) {
+      const dfx_attn_desc d = s.desc(1, k % 2 == 0 ? DFX_ATTN_FUSED : DFX_ATTN_CHAIN);
       check(dfx_attn_create(&d, &h[k]), "attn create");
       check(dfx_attn_set_table(h[k], table.data()), "set_table");
       check(dfx_attn_set_scales(h[k], logit_scale, &out_scale), "set_scales");
+      if (k >= 2) check(dfx_attn_set_bias(h[k], &bd, bias.data()), "set_bias");
       check(dfx_attn_query(h[k], &info[k]), "query");
     }
     size_t turn = 0;
@@ -92,11 +127,11 @@ int main(int argc, char **argv) {
       check(dfx_event_elapsed_ms(e0, e1, &ms), "elapsed");
       return (double)ms * 1000.0 / cnt;
     };
-    std::vector<double> us[2];
-    std::vector<unsigned char> out[2];
-    int per[2] = {iters, iters};  // submits per timed window
+    std::vector<double> us[4];
+    std::vector<unsigned char> out[4];
+    int per[4] = {iters, iters, iters, iters};  // submits per timed window
     for (int r = 0; r < rounds; ++r)
-      for (int k = 0; k < 2; ++k) {
+      for (int k = 0; k < nleg; ++k) {
         if (r == 0) {
           (void)timed(k, 1);  // also the first warm-up submit
           out[k].resize(ob);
@@ -108,9 +143,9 @@ int main(int argc, char **argv) {
         for (int i = 0; i < burn; ++i) launch(k);
         us[k].push_back(timed(k, per[k]));
       }
-    double med[2] = {0, 0};
+    double med[4] = {0, 0, 0, 0};
     const double floor_us = (double)info[0].algorithmic_bytes / 8.0e6;  // 8 TB/s
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < nleg; ++k) {
       std::sort(us[k].begin(), us[k].end());
       med[k] = us[k][us[k].size() / 2];
       printf("%-20s %-6s %10.2f (%8.2f .. %8.2f) %6d %9.2f %8.2f %8.3f  %s, grid %d, lds %d\n", name.c_str(), leg_name[k], med[k], us[k].front(),
@@ -122,7 +157,14 @@ int main(int argc, char **argv) {
            "%zu buffer sets\n", "", med[0] / med[1], 100.0 * (us[0].back() - us[0].front()) / med[0], 100.0 * (us[1].back() - us[1].front()) / med[1],
            s.tq, s.tk, s.d, s.dv, s.batch0 * s.batch1, strips, nsets);
     if (out[0] != out[1]) { fprintf(stderr, "the fused kernel and the chain disagree on %s\n", name.c_str()); return 1; }
-    for (int k = 0; k < 2; ++k) dfx_attn_destroy(h[k]);
+    if (nleg == 4) {
+      printf("%-20s biased: fused time / chain time: %.3f; biased / unbiased: fused %.3f, chain %.3f; spread of the rounds: fused+b %.1f %%, chain+b %.1f %%; "
+             "%d x %d tables of %s, %.1f KiB\n", "", med[2] / med[3], med[2] / med[0], med[3] / med[1], 100.0 * (us[2].back() - us[2].front()) / med[2],
+             100.0 * (us[3].back() - us[3].front()) / med[3], bd.period0, bd.period1, bd.ld ? "{tq, tk}" : "one key-padding row", (double)bias.size() * 4 / 1024.0);
+      if (out[2] != out[3]) { fprintf(stderr, "the biased fused kernel and the biased chain disagree on %s\n", name.c_str()); return 1; }
+      if (out[2] == out[0]) { fprintf(stderr, "the bias changes nothing on %s\n", name.c_str()); return 1; }
+    }
+    for (int k = 0; k < nleg; ++k) dfx_attn_destroy(h[k]);
     dfx_mem_free_device(dq);
     dfx_mem_free_device(dk);
     dfx_mem_free_device(dv);

@@ -15,7 +15,13 @@
 // TB/s HBM peak.  The submits rotate over enough buffer sets to exceed -rotate_mb (default 768: three times the 256 MiB
 // Infinity Cache); -rotate_mb 0 times one set over and over (warm caches).  The results of the two bmm legs are compared
 // byte for byte.
-//   bench_bmm [-iter 20] [-burning_iter 3] [-rounds 5] [-window_us 3000] [-rotate_mb 768] [-skip_ms 1000] [-only <substring>]
+// BIASED LEG (dfx_bmm_set_bias): every point is also timed on the forced MFMA kernel with a logit bias, in the same rounds on
+// the same buffers: the Swin point with one {M, N} table per (window, head) (period0 = 64, period1 = 3), every other point
+// with one row per image (period0 = bs, period1 = 1, ld = 0: a key-padding row at Q.K^T, its last tenth masked).  Finite
+// entries are +-32 output steps, masked entries the finite value of dfa.attention_bias (the fast route stays proved).  Its
+// result is compared byte for byte with ONE submit of the biased generic kernel and must differ from the unbiased result.
+// -bias 0 leaves the leg out, as before the bias existed.
+//   bench_bmm [-iter 20] [-bias 1] [-burning_iter 3] [-rounds 5] [-window_us 3000] [-rotate_mb 768] [-skip_ms 1000] [-only <substring>]
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -39,6 +45,7 @@ int main(int argc, char **argv) {
   const double skip_ms = f.geti("skip_ms", 1000), window_us = f.geti("window_us", 3000);
   const std::string only = f.gets("only", "");
   const size_t rotate = (size_t)f.geti("rotate_mb", 768) << 20;
+  const bool biased = f.geti("bias", 1) != 0;
   std::vector<Point> points;
   const struct { const char *n; int bs, heads, t, d; } nets[] = {{"ViT-B bs8", 8, 12, 197, 64}, {"ViT-B bs64", 64, 12, 197, 64},
                                                                  {"Swin 64x3 windows", 64, 3, 49, 32}, {"DETR bs2", 2, 8, 850, 32},
@@ -52,7 +59,7 @@ int main(int argc, char **argv) {
   dfx_event_t e0, e1;
   check(dfx_event_create(&e0), "event create");
   check(dfx_event_create(&e1), "event create");
-  const char *leg_name[3] = {"mfma", "generic", "dfx_fc"};
+  const char *leg_name[4] = {"mfma", "generic", "dfx_fc", "mfma+b"};
   for (const Point &p : points) {
     if (!only.empty() && p.name.find(only) == std::string::npos) continue;
     const BmmShape &s = p.s;
@@ -75,12 +82,31 @@ int main(int argc, char **argv) {
     check(dfx_stream_sync(nullptr), "sync");
     // a scale that centres the s8 output (about 40 per standard deviation)
     const float scale = 40.0f / ((s.a_dt == DFX_U8 ? 147.0f : 74.0f) * 74.0f * std::sqrt((float)s.k));
-    dfx_bmm_t *h[2] = {nullptr, nullptr};
-    dfx_bmm_info info[2];
-    for (int k = 0; k < 2; ++k) {
-      const dfx_bmm_desc d = s.desc(1, k);
+    // handles: the two unbiased kernels, then (leg 3) the biased MFMA kernel and the biased generic kernel that checks it
+    dfx_bmm_t *h[4] = {nullptr, nullptr, nullptr, nullptr};
+    dfx_bmm_info info[4];
+    const bool windows = s.m == 49;
+    dfx_logit_bias_desc bd;
+    bd.period0 = s.batch0; bd.period1 = windows ? s.batch1 : 1;
+    bd.ld = windows ? s.n : 0;
+    bd.s1 = windows ? (long long)s.m * s.n : 0;
+    bd.s0 = windows ? bd.s1 * s.batch1 : s.n;
+    const float masked = -((s.a_dt == DFX_U8 ? 255.0f : 128.0f) * 128.0f * (float)s.k + std::ceil(129.0f / scale));
+    std::vector<float> bias((size_t)bd.period0 * bd.period1 * (windows ? s.m : 1) * s.n);
+    {
+      unsigned lcg = 12345u;
+      for (size_t i = 0; i < bias.size(); ++i) {
+        lcg = lcg * 1664525u + 1013904223u;
+        bias[i] = ((float)(lcg >> 8) / 16777216.0f * 64.0f - 32.0f) / scale;
+        const int n = (int)(i % (size_t)s.n);
+        if (windows ? (lcg >> 4) % 10 == 0 : n >= s.n - s.n / 10) bias[i] = masked;
+      }
+    }
+    for (int k = 0; k < (biased ? 4 : 2); ++k) {
+      const dfx_bmm_desc d = s.desc(1, k % 2);
       check(dfx_bmm_create(&d, &h[k]), "bmm create");
       check(dfx_bmm_set_scales(h[k], &scale), "set_scales");
+      if (k >= 2) check(dfx_bmm_set_bias(h[k], &bd, bias.data()), "set_bias");
       check(dfx_bmm_query(h[k], &info[k]), "query");
     }
     // leg 2: dfx_fc where the point is one NT matrix with packed rows (lda = ldb = k, ldc = n)
@@ -95,12 +121,14 @@ int main(int argc, char **argv) {
       check(dfx_fc_set_weights(fc, (const int8_t *)hb.data(), nullptr, &scale), "fc set_weights");  // outside the timed region
       check(dfx_fc_query(fc, &fc_info), "fc query");
     }
-    const int nlegs = fc ? 3 : 2;
+    std::vector<int> legs = {0, 1};
+    if (fc) legs.push_back(2);
+    if (biased) legs.push_back(3);
     size_t turn = 0;
     auto launch = [&](int k) {
       const size_t t = turn++ % nsets;
       if (k == 2) check(dfx_fc_submit(fc, (char *)da + t * step(abytes), (char *)dc + t * step(cbytes), nullptr), "fc submit");
-      else check(dfx_bmm_submit(h[k], (char *)da + t * step(abytes), (char *)db + t * step(bbytes), (char *)dc + t * step(cbytes), nullptr), "bmm submit");
+      else check(dfx_bmm_submit(h[k == 3 ? 2 : k], (char *)da + t * step(abytes), (char *)db + t * step(bbytes), (char *)dc + t * step(cbytes), nullptr), "bmm submit");
     };
     auto timed = [&](int k, int n) {
       check(dfx_event_record(e0, nullptr), "record");
@@ -110,12 +138,12 @@ int main(int argc, char **argv) {
       check(dfx_event_elapsed_ms(e0, e1, &ms), "elapsed");
       return (double)ms * 1000.0 / n;
     };
-    std::vector<double> us[3];
-    std::vector<unsigned char> out[3];
-    bool single[3] = {false, false, false};
-    int per[3] = {iters, iters, iters};  // submits per timed window
+    std::vector<double> us[4];
+    std::vector<unsigned char> out[4];
+    bool single[4] = {false, false, false, false};
+    int per[4] = {iters, iters, iters, iters};  // submits per timed window
     for (int r = 0; r < rounds; ++r)
-      for (int k = 0; k < nlegs; ++k) {
+      for (int k : legs) {
         if (single[k]) continue;
         if (r == 0) {
           const double first = timed(k, 1);  // also the first warm-up submit
@@ -133,21 +161,34 @@ int main(int argc, char **argv) {
         for (int i = 0; i < burn; ++i) launch(k);
         us[k].push_back(timed(k, per[k]));
       }
-    double med[3] = {0, 0, 0};
-    for (int k = 0; k < nlegs; ++k) {
+    double med[4] = {0, 0, 0, 0};
+    for (int k : legs) {
       std::sort(us[k].begin(), us[k].end());
       med[k] = us[k][us[k].size() / 2];
-      const uint64_t ops = k == 2 ? fc_info.algorithmic_ops : info[k].algorithmic_ops, bytes = k == 2 ? fc_info.algorithmic_bytes : info[k].algorithmic_bytes;
+      const dfx_bmm_info &bi = info[k == 3 ? 2 : k];
+      const uint64_t ops = k == 2 ? fc_info.algorithmic_ops : bi.algorithmic_ops, bytes = k == 2 ? fc_info.algorithmic_bytes : bi.algorithmic_bytes;
       const double tops = (double)ops / med[k] / 1e6, tbs = (double)bytes / med[k] / 1e6;
       printf("%-26s %-8s %10.2f (%8.2f .. %8.2f) %6d %8.2f %7.2f %8.3f %6.1f  %s, grid %d%s\n", p.name.c_str(), leg_name[k], med[k], us[k].front(),
-             us[k].back(), single[k] ? 1 : per[k], tops, 100.0 * tops / 4600.0, tbs, 100.0 * tbs / 8.0, k == 2 ? fc_info.kernel_name : info[k].kernel_name,
-             k == 2 ? fc_info.grid : info[k].grid, single[k] ? " (one submit: beyond -skip_ms)" : "");
+             us[k].back(), single[k] ? 1 : per[k], tops, 100.0 * tops / 4600.0, tbs, 100.0 * tbs / 8.0, k == 2 ? fc_info.kernel_name : bi.kernel_name,
+             k == 2 ? fc_info.grid : bi.grid, single[k] ? " (one submit: beyond -skip_ms)" : "");
     }
     printf("%-26s mfma time / generic time: %.3f", "", med[0] / med[1]);
     if (fc) printf("; mfma time / dfx_fc time: %.3f (set_weights not timed)", med[0] / med[2]);
     printf("; m %d n %d k %d, %d matrices; %zu buffer sets\n", s.m, s.n, s.k, s.batch0 * s.batch1, nsets);
     if (out[0] != out[1]) { fprintf(stderr, "the mfma and the generic kernels disagree on %s\n", p.name.c_str()); return 1; }
-    for (int k = 0; k < 2; ++k) dfx_bmm_destroy(h[k]);
+    if (biased) {
+      printf("%-26s biased mfma time / mfma time: %.3f; spread of the rounds: mfma %.1f %%, mfma+b %.1f %%; %d x %d tables of %s, %.1f KiB\n", "", med[3] / med[0],
+             100.0 * (us[0].back() - us[0].front()) / med[0], 100.0 * (us[3].back() - us[3].front()) / med[3], bd.period0, bd.period1,
+             windows ? "{m, n}" : "one row", (double)bias.size() * 4 / 1024.0);
+      // one submit of the biased generic kernel into set 0: the biased MFMA kernel's bytes must be its bytes
+      std::vector<unsigned char> ref(cbytes);
+      check(dfx_bmm_submit(h[3], da, db, dc, nullptr), "bmm submit");
+      check(dfx_memcpy_d2h(ref.data(), dc, cbytes, nullptr), "D2H");
+      check(dfx_stream_sync(nullptr), "sync");
+      if (out[3] != ref) { fprintf(stderr, "the biased mfma and the biased generic kernels disagree on %s\n", p.name.c_str()); return 1; }
+      if (out[3] == out[0]) { fprintf(stderr, "the bias changes nothing on %s\n", p.name.c_str()); return 1; }
+    }
+    for (int k = 0; k < 4; ++k) dfx_bmm_destroy(h[k]);
     dfx_fc_destroy(fc);
     dfx_mem_free_device(da);
     dfx_mem_free_device(db);

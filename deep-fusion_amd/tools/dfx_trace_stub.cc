@@ -631,6 +631,7 @@ int dfx_bmm_create(const dfx_bmm_desc *d, dfx_bmm_t **out) {
   return DFX_OK;
 }
 int dfx_bmm_set_scales(dfx_bmm_t *h, const float *) { return set_weights(h, "dfx_bmm_set_scales", {}); }
+int dfx_bmm_set_bias(dfx_bmm_t *h, const dfx_logit_bias_desc *, const float *) { return set_weights(h, "dfx_bmm_set_bias", {}); }
 int dfx_bmm_submit(dfx_bmm_t *hv, const void *a, const void *b, void *c, dfx_stream_t s) {
   handle *h = reinterpret_cast<handle *>(hv);
   if (!h) return fail(DFX_ERR_INVALID, "null handle");
@@ -662,6 +663,7 @@ int dfx_attn_create(const dfx_attn_desc *d, dfx_attn_t **out) {
 }
 int dfx_attn_set_table(dfx_attn_t *h, const uint32_t *) { return set_weights(h, "dfx_attn_set_table", {}); }
 int dfx_attn_set_scales(dfx_attn_t *h, float, const float *) { return set_weights(h, "dfx_attn_set_scales", {}); }
+int dfx_attn_set_bias(dfx_attn_t *h, const dfx_logit_bias_desc *, const float *) { return set_weights(h, "dfx_attn_set_bias", {}); }
 int dfx_attn_submit(dfx_attn_t *hv, const void *q, const void *k, const void *v, void *o, dfx_stream_t s) {
   handle *h = reinterpret_cast<handle *>(hv);
   if (!h) return fail(DFX_ERR_INVALID, "null handle");

@@ -485,6 +485,19 @@ std::array<long long, 3> attention_strides(int bs, int heads, int t, int d, long
 std::unique_ptr<op> matmul(const std::unique_ptr<memory> &a, const std::unique_ptr<memory> &b, std::unique_ptr<memory> &c,
                            const matmul_shape &shape, const std::vector<float> &scales, bool relu = false,
                            round_mode rm = round_mode::nearest);
+// A LOGIT BIAS (dfx_logit_bias_desc in dfx.h): c = store(relu?((float(sum_k a * b) + bias(g, row, col)) * scale[n or 0])), one
+// separately rounded f32 add before the multiply, so the values are in ACCUMULATOR units; finite or -inf (a mask: an s8 c stores
+// -128).  Matrix (b0, b1) uses table (b0 % period0, b1 % period1); table (p0, p1) row m col n is table[p0 * s0 + p1 * s1 + m * ld
+// + n], in floats; ld == 0: one row, broadcast over m.  `table` must hold every float the layout addresses; it is copied when
+// the op is made.  What dfx.h says about a mask behind a softmax holds: the masked logit is -128, no less.
+struct logit_bias {
+  std::vector<float> table;
+  int period0, period1;
+  long long s0, s1, ld;
+};
+std::unique_ptr<op> matmul(const std::unique_ptr<memory> &a, const std::unique_ptr<memory> &b, std::unique_ptr<memory> &c,
+                           const matmul_shape &shape, const std::vector<float> &scales, const logit_bias &bias, bool relu = false,
+                           round_mode rm = round_mode::nearest);
 
 // ---- extension: fused int8 attention (dfx_attn_* in dfx.h): o[g] = requant(softmax(requant(q[g] . k[g]^T)) . v[g]) over
 // batch0 * batch1 matrices that lie anywhere in four tensors, DEFINED as matmul() (s8 logits, scale logit_scale) -> softmax()
@@ -502,6 +515,12 @@ std::unique_ptr<op> attention(const std::unique_ptr<memory> &q, const std::uniqu
                               const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &o, const attention_shape &shape,
                               float logit_scale, const std::vector<float> &out_scales, float prob_scale = 255.f, bool relu = false,
                               round_mode rm = round_mode::nearest);
+// the same with matmul()'s logit_bias on the logits (m = tq, n = tk): a relative-position table per head, a shifted-window
+// mask, a key-padding row, a causal mask.  A fully masked row is uniform over all tk keys (dfx.h).
+std::unique_ptr<op> attention(const std::unique_ptr<memory> &q, const std::unique_ptr<memory> &k, const std::unique_ptr<memory> &v,
+                              const std::array<uint32_t, 256> &table, std::unique_ptr<memory> &o, const attention_shape &shape,
+                              float logit_scale, const std::vector<float> &out_scales, const logit_bias &bias, float prob_scale = 255.f,
+                              bool relu = false, round_mode rm = round_mode::nearest);
 
 // ---- extension: image-wide top-K with peak filter (dfx_select_* in dfx.h): what a detector does behind its last conv,
 // without leaving the device.  src: an nhwc score tensor {bs, C, h, w} of u8 / s8 (a conv()'s heat map); the first c_valid

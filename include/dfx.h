@@ -1053,6 +1053,10 @@ typedef struct dfx_roialign dfx_roialign_t;
  *                   = sum over k of A[g,m,k] * B[g,k,n]      (trans_b = 0, B is {K,N}, n contiguous:  P.V)
  *        f = float(acc);  f = f * scale[n or 0];  ReLU (asked for, or dst is u8): f = (0 > f) ? 0 : f
  *        C[g,m,n] = store(f, dst_dt, round_mode)
+ *      With a LOGIT BIAS set on the handle (dfx_bmm_set_bias, dfx_logit_bias_desc below):
+ *        f = float(acc);  f = f + bias(g,m,n);  f = f * scale[n or 0];  ReLU;  C[g,m,n] = store(f, dst_dt, round_mode)
+ *      which is requant() verbatim: one separately rounded f32 add BEFORE the multiply, never an FMA.  The bias is therefore
+ *      in ACCUMULATOR units: bias_real / (logit_step * logit_scale) for logits whose s8 step is logit_step.
  *      OPERANDS.  A u8 or s8; B s8 (u8 B: DFX_ERR_UNSUPPORTED, not built); C u8 / s8 / s32 / f32.
  *      ADDRESSING, in elements, per operand: element (g, row, col) of A is at a + b0*a_s0 + b1*a_s1 + row*lda + col; B uses
  *      b_s0, b_s1, ldb and C uses c_s0, c_s1, ldc in the same way.  The heads of a {bs, T, heads*d} NHWC tensor are read
@@ -1063,15 +1067,26 @@ typedef struct dfx_roialign dfx_roialign_t;
  *      (dfx_head's rule: a softmax output with dst_ld = 208 for 197 tokens is A as it stands).  Every row of A and B is
  *      readable up to its valid columns rounded up to 16, which the leading dimension admits on the MFMA path (that kernel
  *      reads whole 16-byte pieces and masks them).
- *      ARITHMETIC.  dfx_fc's, word for word, without a bias: exact s32 accumulation (1 <= K <= 65025), requant() /
- *      gc_quarter with bias +0.0f (the identity: float(int) is never -0), a separately rounded multiply, the x86
- *      conversion and saturations of dfx_device.cuh.
+ *      ARITHMETIC.  dfx_fc's, word for word: exact s32 accumulation (1 <= K <= 65025), requant() / gc_quarter whose bias
+ *      slot holds +0.0f (the identity: float(int) is never -0) or the logit bias's {m, n} entry, a separately rounded
+ *      multiply, the x86 conversion and saturations of dfx_device.cuh.
  *      REQUANT ROUTE.  The op never sees its operands on the host, so dfx_bmm_set_scales proves the route from the shape
  *      alone: "fast" when the round mode is nearest, DFX_NO_FAST is not set, every scale is finite and
  *      bound * |scale| <= 2^30 with bound = 255*128*K (u8 A) or 128*128*K (s8 A); otherwise "exact".  The generic kernel is
  *      always exact.  Both routes give the same bits wherever "fast" is allowed.
- *      Not built: u8 B, an additive mask / relative-position bias on the logits, split-K for tiny G*M*N, a bias,
- *      K > 65025, s32 / f32 operands.  (The softmax fused between the two products, one launch, is dfx_attn below.)
+ *      With a logit bias the proof is (bound + max |finite bias entry|) * |scale| <= 2^30 and NO non-finite entry: a -inf
+ *      anywhere takes the exact route (the fast route's conversion is not defined there).
+ *      LOGIT BIAS VALUES.  Finite f32 values and -inf; +inf or NaN anywhere in the addressed table: DFX_ERR_INVALID.  A -inf
+ *      entry follows the exact route's x86 semantics: the sum is -inf, the product -inf, +inf or NaN by the scale's sign,
+ *      vcvtps2dq gives 0x80000000 for all three, so an s8 C stores -128 whatever the sign of the scale (no ReLU).
+ *      WHAT A MASK GIVES.  The masked logit is -128, no less.  In a softmax behind it (dfx_head, dfx_attn) its probability is
+ *      E[max + 128] of the caller's table over the row sum: 0 once that table entry is 0 or the u8 rounding takes it, and not
+ *      before.  A FULLY masked row is uniform over all its keys (every logit is -128); torch gives NaN there.
+ *      Not built: u8 B, split-K for tiny G*M*N, a per-channel bias vector as dfx_fc has it, K > 65025, s32 / f32 operands;
+ *      of the logit bias: a device-resident table (per-batch masks that change every submit without a host call), f16 / s8
+ *      storage of the table, skipping fully masked key tiles (a causal speed-up), a mask input to dfx_head, two separate
+ *      bias operands (the host sums rel_bias[h] + mask[w] once).  (The softmax fused between the two products, one launch,
+ *      is dfx_attn below.)
  *      Parity unpinned: the reference has no such op. ---- */
 typedef struct dfx_bmm_desc {
   int32_t batch0, batch1;      /* >= 1; G = batch0 * batch1 matrices */
@@ -1087,6 +1102,18 @@ typedef struct dfx_bmm_desc {
   int64_t b_s0, b_s1, ldb;     /* ldb >= k (trans_b = 1) or >= n (trans_b = 0) */
   int64_t c_s0, c_s1, ldc;     /* ldc >= n; no two elements of C may share an address */
 } dfx_bmm_desc;
+/* The HOST layout of a logit bias (dfx_bmm_set_bias / dfx_attn_set_bias): period0 x period1 tables of {m, n} f32 values in
+ * accumulator units, or of one row {n} broadcast over m.  Matrix (b0, b1) uses table (b0 % period0, b1 % period1).
+ *   Swin: batch0 = images x windows, batch1 = heads, period0 = nW (the shifted-window mask repeats per image; 1 on
+ *   un-shifted blocks), period1 = heads; the host sums rel_bias[h] + mask[w] once.  DETR key padding: period0 = bs,
+ *   period1 = 1, ld = 0 (a {bs, tk} table).  Causal: periods 1 and one {T, T} table.
+ * The library copies the addressed entries into a device image {period0 * period1, m or 1, n rounded up to 32} it owns (at
+ * most 2^30 bytes: larger is DFX_ERR_UNSUPPORTED). */
+typedef struct dfx_logit_bias_desc {
+  int32_t period0, period1;    /* 1 <= period0 <= batch0, 1 <= period1 <= batch1 */
+  int64_t s0, s1, ld;          /* in floats, >= 0: table (p0,p1) row m col n at p0*s0 + p1*s1 + m*ld + n;
+                                  ld == 0: one row, broadcast over m; else ld >= n */
+} dfx_logit_bias_desc;
 enum {  /* dfx_bmm_info.path */
   DFX_BMM_MFMA = 0,            /* bmm_mfma_kernel (bmm.cuh): v_mfma_i32_32x32x32_i8, one launch, requant in the epilogue.
                                   Class: lda, ldb and the batch strides of A and B multiples of 16 elements; a and b 16-byte
@@ -1115,8 +1142,10 @@ typedef struct dfx_bmm_info {
   int32_t grid, block, lds_bytes;
   int32_t device;
   uint64_t algorithmic_ops;    /* 2 * G * M * N * K */
-  uint64_t algorithmic_bytes;  /* the distinct bytes of A, B and C: a broadcast operand counts once */
-  char kernel_name[96];        /* "bmm_mfma<nt,u8,s8> fast": form (nt | nn), A type, dst type, route (after set_scales) */
+  uint64_t algorithmic_bytes;  /* the distinct bytes of A, B and C: a broadcast operand counts once; plus, while a logit bias is
+                                  set, the distinct bytes of its tables */
+  char kernel_name[96];        /* "bmm_mfma<nt,u8,s8> fast": form (nt | nn), A type, dst type, route (after set_scales); the
+                                  suffix " +bias" while a logit bias is set */
 } dfx_bmm_info;
 typedef struct dfx_bmm dfx_bmm_t;
 
@@ -1141,8 +1170,18 @@ typedef struct dfx_bmm dfx_bmm_t;
  *      operand's index range and the logits' G * tq * up16(tk) below 2^40.
  *      REQUANT ROUTES.  Proved from the shape as dfx_bmm_set_scales does: bound 128*128*d (s8 Q) or 255*128*d (u8 Q) against
  *      logit_scale for the logits, 255*128*tk against out_scales for the context.
- *      Not built: a mask or relative-position bias on the logits, causal attention, u8 K / V, P or L as an output, f32
- *      probabilities between the products, multi-device sharding.  Parity unpinned: the reference has no such op. ---- */
+ *      LOGIT BIAS.  dfx_attn_set_bias sets dfx_bmm's logit bias (dfx_logit_bias_desc, its values and its mask semantics, all
+ *      above) on the logits' product and on nothing else: L = dfx_bmm(Q, K) WITH that bias, then dfx_head's softmax and
+ *      dfx_bmm(P, V), both unchanged.  With m = tq, n = tk, batch = (batch0, batch1): a per-head relative-position table, a
+ *      shifted-window mask, a key-padding row and a causal mask are all layouts of it.  A masked logit is -128; its
+ *      probability is E[max + 128] over the row sum (0 once the table or the u8 rounding says so); a fully masked row is
+ *      uniform over all tk keys (torch: NaN).  The logits' route is then proved with the bias (dfx_bmm's rule).  A bias does
+ *      not change the handle's plan: the biased fused kernel was timed against the biased chain at the points of
+ *      DFX_ATTN_AUTO_NOTE and won and lost where the unbiased one does (below).
+ *      Not built: u8 K / V, P or L as an output, f32 probabilities between the products, multi-device sharding; of the logit
+ *      bias: a device-resident table, f16 / s8 storage, skipping fully masked key tiles (a causal speed-up), a mask input
+ *      to dfx_head, two separate bias operands, anything for the non-local point's speed.  Parity unpinned: the reference has
+ *      no such op. ---- */
 typedef struct dfx_attn_desc {
   int32_t batch0, batch1;      /* >= 1; G = batch0 * batch1 matrices */
   int32_t tq, tk, d, dv;       /* >= 1; tq, dv <= 2^31 - 32; tk <= 65025; d <= 65025 */
@@ -1185,7 +1224,13 @@ enum {  /* dfx_attn_info.path */
  * and V (2 MiB) through L2 with nothing to hide the latency.  The floor (Q, K, V and O once at 8 TB/s) is 0.6 / 4.8 / 0.15 / 0.22 /
  * 0.5 / 2.1 us: the fused kernel is 37x to 750x above it.  Nothing between the box and the non-local point (tk 851 .. 4095, d or dv
  * 65 .. 255), nothing smaller and nothing with fewer strips was timed: all of it stays on the chain; DFX_ATTN_FUSED is reachable
- * there with force_path and gives the same bits. */
+ * there with force_path and gives the same bits.
+ * WITH A LOGIT BIAS the rule is the same box (profiles/attn/bench_attn_bias.txt, the same method, the four legs alternating; a
+ * key-padding row per image, at the Swin stage one {49, 49} table per (window, head)): the biased fused kernel beats the biased
+ * chain at ViT-B bs 8 in 22.8 us against 49.0 (0.47x) and at bs 64 in 134 us against 260 (0.51x), at the Swin stage in 13.4 us
+ * against 22.4 (0.60x), at the DETR encoder in 41.9 us against 66.5 (0.63x), every time by far more than the rounds' spread (at
+ * most 3.5 %), and loses at the non-local point as it does without a bias (2.06x / 2.15x).  What the bias costs: DESIGN.md
+ * section 4.22. */
 typedef struct dfx_attn_info {
   int32_t path;                /* the handle's plan (a misaligned submit falls back to the chain without changing it) */
   int32_t grid, block, lds_bytes; /* of the fused kernel; 0 on the chain (see the three ops' own queries) */
@@ -1194,8 +1239,10 @@ typedef struct dfx_attn_info {
   uint64_t scratch_bytes;      /* L and P together, as the handle holds them now: 0 on a fused handle until a submit has fallen
                                   back to the chain */
   uint64_t algorithmic_ops;    /* 2 * G * tq * tk * (d + dv) */
-  uint64_t algorithmic_bytes;  /* the distinct bytes of Q, K, V and O: a broadcast operand counts once (the floor) */
-  char kernel_name[96];        /* "attn_fused<s8,s8> fast/exact": Q type, dst type, logits / context route; "attn_chain<...>" */
+  uint64_t algorithmic_bytes;  /* the distinct bytes of Q, K, V and O: a broadcast operand counts once (the floor); plus, while a
+                                  logit bias is set, the distinct bytes of its tables */
+  char kernel_name[96];        /* "attn_fused<s8,s8> fast/exact": Q type, dst type, logits / context route; "attn_chain<...>";
+                                  the suffix " +bias" while a logit bias is set */
 } dfx_attn_info;
 typedef struct dfx_attn dfx_attn_t;
 
@@ -1764,6 +1811,13 @@ int dfx_roialign_destroy(dfx_roialign_t *h);
  *      Tuning switch: DFX_BMM_GRID=n caps the grid of either kernel.  No CPU fallback. ---- */
 int dfx_bmm_create(const dfx_bmm_desc *desc, dfx_bmm_t **out);
 int dfx_bmm_set_scales(dfx_bmm_t *h, const float *scales);
+/* The logit bias (dfx_logit_bias_desc above).  DFX_ERR_INVALID for a period outside 1 .. its batch extent, a negative
+ * stride, 0 < ld < n, a host extent of 2^40 floats or more, a null table and a +inf or NaN among the addressed entries;
+ * DFX_ERR_UNSUPPORTED for a device image above 2^30 bytes; the handle is unchanged by a refused call.  The addressed entries
+ * are COPIED at the call: set_scales' contract -- synchronous, not while a submit of the handle is in flight.  It may be called
+ * again with another table or layout.  desc == NULL clears the bias (host_table is ignored) and the handle gives its former
+ * bits.  Either order with set_scales: whichever setter comes last proves the requant route again. */
+int dfx_bmm_set_bias(dfx_bmm_t *h, const dfx_logit_bias_desc *desc, const float *host_table);
 int dfx_bmm_submit(dfx_bmm_t *h, const void *a_dev, const void *b_dev, void *c_dev, dfx_stream_t s);
 int dfx_bmm_query(const dfx_bmm_t *h, dfx_bmm_info *info);
 int dfx_bmm_destroy(dfx_bmm_t *h);
@@ -1790,6 +1844,9 @@ int dfx_bmm_destroy(dfx_bmm_t *h);
 int dfx_attn_create(const dfx_attn_desc *desc, dfx_attn_t **out);
 int dfx_attn_set_table(dfx_attn_t *h, const uint32_t *table256);
 int dfx_attn_set_scales(dfx_attn_t *h, float logit_scale, const float *out_scales);
+/* dfx_bmm_set_bias on the logits' product (m = tq, n = tk), with its checks, its copy and its contract; it reaches the fused
+ * kernel, the chain, and the chain a fused handle makes at its first submit that falls back.  desc == NULL clears it. */
+int dfx_attn_set_bias(dfx_attn_t *h, const dfx_logit_bias_desc *desc, const float *host_table);
 int dfx_attn_submit(dfx_attn_t *h, const void *q_dev, const void *k_dev, const void *v_dev, void *o_dev, dfx_stream_t s);
 int dfx_attn_query(const dfx_attn_t *h, dfx_attn_info *info);
 int dfx_attn_destroy(dfx_attn_t *h);

@@ -37,6 +37,7 @@ from .capi import (  # noqa: F401
     ATTN_AUTO, ATTN_FUSED, ATTN_CHAIN, AttnDesc, AttnInfo, Attention, attn_launches,
     LNORM_LAYER, LNORM_RMS, LNORM_AUTO, LNORM_ROW, LNORM_GENERIC, LNORM_MAX_C, LNORM_MAX_SHIFT, LnormDesc, LnormInfo, LayerNorm,
     lnorm_launches, lnorm_params,
+    LINEAR_AUTO, LINEAR_TILE, LINEAR_GENERIC, LinearDesc, LinearInfo, Linear, linear_launches, gelu_table,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

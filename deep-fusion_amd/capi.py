@@ -46,6 +46,7 @@ ATTN_AUTO, ATTN_FUSED, ATTN_CHAIN = -1, 0, 1
 LNORM_LAYER, LNORM_RMS = 0, 1
 LNORM_AUTO, LNORM_ROW, LNORM_GENERIC = -1, 0, 1
 LNORM_MAX_C, LNORM_MAX_SHIFT = 16384, 7
+LINEAR_AUTO, LINEAR_TILE, LINEAR_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -308,6 +309,19 @@ class LnormInfo(ctypes.Structure):
                [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
 
 
+class LinearDesc(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("k", "n", "src_dt", "dst_dt", "bia_dt", "relu", "round_mode", "nscales", "lut_in_dt",
+                                              "force_path")] + \
+               [("src_ld", ctypes.c_int64), ("dst_ld", ctypes.c_int64)]
+
+
+class LinearInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
 class DwPwDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t", "pad_l",
                                              "oc", "dst_dt", "bia0_dt", "bia1_dt", "relu", "round_mode0", "round_mode1",
@@ -536,6 +550,15 @@ def lib():
         "dfx_lnorm_query": (i32, [vp, ctypes.POINTER(LnormInfo)]),
         "dfx_lnorm_destroy": (i32, [vp]),
         "dfx_debug_lnorm_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_linear_create": (i32, [ctypes.POINTER(LinearDesc), ctypes.POINTER(vp)]),
+        "dfx_linear_set_weights": (i32, [vp, vp, vp, vp]),
+        "dfx_linear_set_table": (i32, [vp, vp]),
+        "dfx_linear_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_linear_submit_host": (i32, [vp, vp, vp]),
+        "dfx_linear_query": (i32, [vp, ctypes.POINTER(LinearInfo)]),
+        "dfx_linear_destroy": (i32, [vp]),
+        "dfx_debug_linear_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_debug_linear_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -615,6 +638,34 @@ def lnorm_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_lnorm_launches(v))
     return v[LNORM_ROW], v[LNORM_GENERIC]
+
+
+def linear_launches():
+    """(tile, generic): dfx_linear_submit calls of this process that launched each kernel (dfx_debug_linear_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_linear_launches(v))
+    return v[LINEAR_TILE], v[LINEAR_GENERIC]
+
+
+def gelu_table(in_step, out_step, in_dt=np.int8, out_dt=np.int8):
+    """The 256-byte table of dfa.Linear(table=...) for GELU behind a linear layer: entry i stands for the index-type value
+    q (i for a uint8 index type, i - 128 for int8: dfx_wsum's convention), x = q * in_step, and holds
+    clamp(rint(0.5 * x * (1 + erf(x / sqrt(2))) / out_step)) as out_dt, rint to even, computed in float64 with math.erf.
+    Returned as uint8 bytes (an int8 value as its two's complement)."""
+    import math
+    in_dt, out_dt = np.dtype(in_dt), np.dtype(out_dt)
+    if in_dt not in (np.dtype(np.uint8), np.dtype(np.int8)) or out_dt not in (np.dtype(np.uint8), np.dtype(np.int8)):
+        raise ValueError("index and output types are uint8 or int8")
+    if not (float(in_step) > 0 and float(out_step) > 0 and math.isfinite(in_step) and math.isfinite(out_step)):
+        raise ValueError("steps must be finite and positive")
+    lo, hi = (0, 255) if out_dt == np.dtype(np.uint8) else (-128, 127)
+    out = np.empty(256, dtype=np.uint8)
+    for i in range(256):
+        x = float(i if in_dt == np.dtype(np.uint8) else i - 128) * float(in_step)
+        g = 0.5 * x * (1.0 + math.erf(x / math.sqrt(2.0)))
+        v = int(min(max(round(g / float(out_step)), lo), hi))   # round(): ties to even
+        out[i] = v & 0xff
+    return out
 
 
 def lnorm_params(gamma, beta, in_scale, out_scale, eps):
@@ -1344,6 +1395,45 @@ class LayerNorm(_Handle):
         s = None if shift is None else np.ascontiguousarray(shift, dtype=np.uint8).reshape(-1)
         assert g.size == c and (b is None or b.size == c) and (s is None or s.size == c)
         _check(lib().dfx_lnorm_set_params(self._h, _p(g), _p(b), _p(s)))
+
+
+class Linear(_Handle):
+    """dfx_linear_* handle: int8 linear layer over a row matrix of tokens (include/dfx.h): `rows` rows of `k` valid uint8 /
+    int8 elements, src_ld apart, times an int8 {n, k} weight (an nn.Linear weight), per-n bias and scales, dst rows dst_ld
+    apart in any of the four dtypes.  table: the index type (uint8 / int8) of an optional 256-byte table behind the requant
+    (gelu_table()); set_weights() and, with a table, set_table() first; submit(src, dst)."""
+
+    _OP, _INFO, _ROUTES = "dfx_linear", LinearInfo, 1
+
+    def __init__(self, rows, k, n, src_dtype=np.int8, dst_dtype=np.int8, bia_dt=DFX_UNDEF, relu=False, rm=ROUND_NEAREST, nscales=1,
+                 src_ld=None, dst_ld=None, table=None, force_path=LINEAR_AUTO):
+        code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
+        d = LinearDesc()
+        d.rows, d.k, d.n, d.src_dt, d.dst_dt, d.bia_dt = rows, k, n, code(src_dtype), code(dst_dtype), code(bia_dt)
+        d.relu, d.round_mode, d.nscales = int(relu), rm, nscales
+        d.lut_in_dt = DFX_UNDEF if table is None else code(table)
+        d.force_path = force_path
+        d.src_ld = k if src_ld is None else src_ld
+        d.dst_ld = n if dst_ld is None else dst_ld
+        self.desc = d
+        self.src_shape, self.dst_shape = (rows, k), (rows, n)
+        self.src_np_dtype, self.dst_np_dtype = _NP.get(d.src_dt), _NP.get(d.dst_dt)
+        self._create(d)
+
+    def set_weights(self, wei, scales, bia=None):
+        """wei: int8 {n, k}; scales: 1 or n floats; bia: n entries of the descriptor's bias dtype"""
+        d = self.desc
+        ws = [np.ascontiguousarray(wei, dtype=np.int8), None if bia is None else np.ascontiguousarray(bia),
+              np.ascontiguousarray(scales, dtype=np.float32)]
+        assert ws[0].size == d.n * d.k, ws[0].shape
+        assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.n)
+        _check(lib().dfx_linear_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+    def set_table(self, table):
+        """256 bytes (uint8, or int8 viewed as bytes)"""
+        t = np.ascontiguousarray(table).view(np.uint8).reshape(-1)
+        assert t.size == 256
+        _check(lib().dfx_linear_set_table(self._h, _p(t)))
 
 
 class TopK(Head):

@@ -2760,6 +2760,101 @@ private:
   std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
+// ---- int8 token linear layer (dfx_linear_*) over the rows of an nhwc tensor (rows = bs * h * w, src_ld = C, k <= C); dst
+// {bs, C', h, w} with C' >= n, whose pad channels the kernel leaves alone (undefined on the host afterwards, as op_layer_norm's).
+// The weights are a plain oihw {n, k, 1, 1} tensor, hashed and re-packed as op_inner_product's; the table is copied at
+// construction.  src is registered as a read, dst as a write (op_state).  One device: the op is not sharded. ----
+class op_linear : public op {
+public:
+  op_linear(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
+            std::unique_ptr<memory> &dst, bool relu, const std::vector<float> &scales, round_mode rm, int k_valid, const std::vector<u8> &table,
+            memory::dtype table_in)
+      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0), packed_versions_(0) {
+    using fmt = memory::format;
+    if (!src_ || !wei_ || !dst_) error_and_exit("Init Linear op failed! (null tensor)");
+    if (src_ == dst_) error_and_exit("Init Linear op failed! (in place is not built)");
+    if (wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc || dst_->dim_format() != fmt::nhwc ||
+        wei_->dim_format() != fmt::oihw || (bia_ && bia_->dim_format() != fmt::x))
+      error_and_exit("Init Linear op failed! (data type / format)");
+    auto i = src_->std_dims(), w = wei_->std_dims(), o = dst_->std_dims();
+    if (i[0] != o[0] || i[2] != o[2] || i[3] != o[3]) error_and_exit("Init Linear op failed! (batch size / height / width do not equal)");
+    const int k = k_valid > 0 ? k_valid : i[1];
+    if (w[1] != k || w[2] != 1 || w[3] != 1) error_and_exit("Init Linear op failed! (weights must be {n, k, 1, 1})");
+    if (bia_ && (int)bia_->size() != w[0]) error_and_exit("Init Linear op failed! (Bias channel do not match)");
+    if (!table.empty() && table.size() != 256) error_and_exit("Init Linear op failed! (the table must be empty or have 256 bytes)");
+    if (table.empty() != (table_in == memory::dtype::undef)) error_and_exit("Init Linear op failed! (a table needs table_in, and table_in a table)");
+    dfx_linear_desc d;
+    memset(&d, 0, sizeof(d));
+    d.rows = (long long)i[0] * i[2] * i[3];
+    d.k = k; d.n = w[0];
+    d.src_dt = to_dfx_dtype(src_->data_type());
+    d.dst_dt = to_dfx_dtype(dst_->data_type());
+    d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
+    d.relu = relu;
+    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.nscales = (int)scales_.size();
+    d.lut_in_dt = table.empty() ? DFX_UNDEF : to_dfx_dtype(table_in);
+    d.force_path = -1;
+    d.src_ld = i[1];
+    d.dst_ld = o[1];
+    if (dfx_linear_create(&d, &h_) != DFX_OK) error_and_exit("Init Linear op failed! (%s)", dfx_last_error());
+    if (!table.empty() && dfx_linear_set_table(h_, table.data()) != DFX_OK) error_and_exit("Init Linear op failed! (%s)", dfx_last_error());
+    st_.ensure_stream();
+  }
+  ~op_linear() override {
+    st_.retire(*dst_);
+    dfx_linear_destroy(h_);
+  }
+
+  void submit() override {
+    run(true);
+    st_.fetch_out(*dst_);
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+  void submit_async() override { run(false); }
+  void wait() override {
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled(*dst_);
+  }
+
+protected:
+  void infer() override { run(true); }
+  unsigned long long weights_hash() {
+    using detail::hash_bytes;
+    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
+    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
+    return v | 1ull;
+  }
+  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
+  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
+    const unsigned long long vers = weights_versions();
+    if (sync_host || vers != packed_versions_) {
+      const unsigned long long hash = weights_hash();
+      if (hash != packed_hash_) {
+        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
+        check_dfx(dfx_linear_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
+                  "linear set_weights");
+        packed_hash_ = hash;
+      }
+      packed_versions_ = vers;
+    }
+    const void *in = st_.sync_in(*src_, sync_host);
+    void *o = st_.device_out(*dst_);
+    st_.profile_begin();
+    check_dfx(dfx_linear_submit(h_, in, o, st_.stream), "linear submit");
+    st_.profile_end(name());
+  }
+  const char *name() override { return "linear"; }
+
+private:
+  memory *src_, *wei_, *bia_, *dst_;
+  std::vector<float> scales_;
+  dfx_linear_t *h_;
+  unsigned long long packed_hash_, packed_versions_;
+  detail::op_state st_;
+};
+
 // ---- image-wide top-K with peak filter (dfx_select_*): the k best elements of every image of an nhwc score tensor,
 // optionally only 3x3 local maxima and only elements >= min_val, with whole pixel rows of further nhwc tensors gathered
 // behind it.  src and the gather sources are registered as reads, idx, count, val and the gather destinations as writes
@@ -3666,6 +3761,12 @@ std::unique_ptr<op> softmax(const std::unique_ptr<memory> &src, const std::array
 std::unique_ptr<op> layer_norm(const std::unique_ptr<memory> &src, const std::vector<float> &gamma, const std::vector<float> &beta,
                                std::unique_ptr<memory> &dst, float eps, norm_mode mode, const std::vector<u8> &shifts, int c_valid) {
   return std::unique_ptr<op>(new op_layer_norm(src, gamma, beta, dst, eps, mode, shifts, c_valid));
+}
+
+std::unique_ptr<op> linear(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
+                           std::unique_ptr<memory> &dst, bool relu, std::vector<float> scales, round_mode rm, int k_valid,
+                           const std::vector<u8> &table, memory::dtype table_in) {
+  return std::unique_ptr<op>(new op_linear(src, wei, bia, dst, relu, scales, rm, k_valid, table, table_in));
 }
 
 std::array<long long, 3> attention_strides(int bs, int heads, int t, int d, long long ld) {

@@ -508,6 +508,22 @@ int dfx_lnorm_submit(dfx_lnorm_t *hv, const void *src, void *dst, dfx_stream_t s
 }
 int dfx_lnorm_destroy(dfx_lnorm_t *h) { return destroy_handle(h); }
 
+// ---- token linear layer: one read (src), one write (dst); set_weights reads the borrowed weights and bias ----
+int dfx_linear_create(const dfx_linear_desc *d, dfx_linear_t **out) {
+  if (!d || !out || d->rows < 1 || d->k < 1 || d->n < 1 || d->src_ld < d->k || d->dst_ld < d->n) return fail(DFX_ERR_INVALID, "bad linear descriptor");
+  handle *h = new_handle("linear");
+  const size_t rows = (size_t)d->rows;
+  h->src.push_back(((rows - 1) * d->src_ld + d->k) * dt_size(d->src_dt));
+  h->dst = ((rows - 1) * d->dst_ld + d->n) * dt_size(d->dst_dt);
+  h->wei = {(size_t)d->n * d->k, d->bia_dt ? (size_t)d->n * dt_size(d->bia_dt) : 0};
+  *out = reinterpret_cast<dfx_linear_t *>(h);
+  return DFX_OK;
+}
+int dfx_linear_set_weights(dfx_linear_t *h, const int8_t *w, const void *b, const float *) { return set_weights(h, "dfx_linear_set_weights", {w, b}); }
+int dfx_linear_set_table(dfx_linear_t *h, const uint8_t *) { return set_weights(h, "dfx_linear_set_table", {}); }
+int dfx_linear_submit(dfx_linear_t *h, const void *src, void *dst, dfx_stream_t s) { return submit1(h, "dfx_linear_submit", src, dst, s); }
+int dfx_linear_destroy(dfx_linear_t *h) { return destroy_handle(h); }
+
 // ---- image-wide top-K: reads src and the gather sources (`src`); writes idx (`dst`), val when given (`lat`), count and the
 // gather destinations (this op borrows no host tensors: `wei` holds the bytes of count and of each gather destination) ----
 int dfx_select_create(const dfx_select_desc *d, dfx_select_t **out) {

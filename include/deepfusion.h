@@ -459,6 +459,24 @@ std::unique_ptr<op> layer_norm(const std::unique_ptr<memory> &src, const std::ve
                                const std::vector<float> &beta, std::unique_ptr<memory> &dst, float eps,
                                norm_mode mode = norm_mode::layer, const std::vector<u8> &shifts = {}, int c_valid = 0);
 
+// ---- extension: int8 token linear layer (dfx_linear_* in dfx.h): the weight multiplies of a transformer block -- QKV and output
+// projection, fc1 (+ GELU through a byte table) and fc2 -- between layer_norm(), attention() and scaled_sum().  src: an nhwc
+// tensor {bs, C, h, w} of u8 / s8; every pixel (token) is a row of C channels of which the first k_valid take part (0: all),
+// as layer_norm() reads them: attention()'s head-interleaved context is read in place.  wei: plain oihw s8 {n, k, 1, 1} (an
+// nn.Linear weight), k <= 65025; bia: format x, n entries, or null; scales: 1 or n.  dst: nhwc {bs, C', h, w} of u8 / s8 / s32
+// / f32 with C' >= n; the kernel does not write the channels from n on (UNDEFINED on the host afterwards, as softmax()'s).
+// Arithmetic, scales, ReLU and rounding are inner_product()'s.  table (256 bytes, or empty) with table_in = u8 / s8: the
+// requant produces the byte t it would store into a table_in dst and the op stores table[t] (u8) or table[t + 128] (s8)
+// instead, as scaled_sum() does; dst must then be u8 or s8 and ReLU follows relu / table_in.  dst must not be src.  Bit-exact
+// and the same on every kernel path.  Weight hashing and submit / submit_async / wait are inner_product()'s; the op runs on
+// ONE device (DEEPFUSION_DEVICES does not shard it).  Not built: a fused residual add (scaled_sum() joins the residual),
+// split-K, s32 / f32 sources, u8 weights, a fused layer norm in front. ----
+std::unique_ptr<op> linear(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei,
+                           const std::unique_ptr<memory> &bia, std::unique_ptr<memory> &dst,
+                           bool relu = false, std::vector<float> scales = {1.f}, round_mode rm = round_mode::nearest,
+                           int k_valid = 0, const std::vector<u8> &table = {},
+                           memory::dtype table_in = memory::dtype::undef);
+
 // ---- extension: batched int8 matrix product of two DEVICE tensors (dfx_bmm_* in dfx.h): the multiply whose second operand is
 // not a weight -- Q.K^T and P.V of an attention / non-local block, a correlation layer.  a (u8 / s8), b (s8) and c (u8 / s8 /
 // s32 / f32) are tensors of any dims; `shape` says where the matrices lie in them, in ELEMENTS from each tensor's first:

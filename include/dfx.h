@@ -1316,6 +1316,87 @@ typedef struct dfx_lnorm_info {
 } dfx_lnorm_info;
 typedef struct dfx_lnorm dfx_lnorm_t;
 
+/* ---- int8 token linear layer over a ROW MATRIX: the four weight multiplies of a transformer block (QKV projection, output
+ *      projection, fc1 + GELU, fc2) between dfx_lnorm, dfx_attn and dfx_wsum, weight-stationary.
+ *
+ *      Operands.  src is a row matrix as in dfx_lnorm and dfx_head: `rows` rows of `k` valid elements, src_ld >= k elements
+ *      apart, dtype u8 or s8.  Columns k .. src_ld-1 never take part, whatever they hold.  wei is s8 {n, k}, plain row-major
+ *      (an nn.Linear weight), a HOST pointer at set_weights.  bia is an optional per-n vector of any of the four dtypes,
+ *      converted as dfx_fc converts it.  scales: 1 or n.  dst is rows dst_ld >= n elements apart, u8 / s8 / s32 / f32;
+ *      elements n .. dst_ld-1 are NOT written.  Any rows >= 1 with rows * max(src_ld, dst_ld) <= 2^40, any n >= 1
+ *      (n <= 2^31 - 128), 1 <= k <= 65025.
+ *
+ *      Arithmetic: dfx_fc's, word for word.  acc = sum_c src[m][c] * wei[o][c] is an exact s32; then
+ *        f = float(acc); f = f + bias[o]; f = f * scale[o or 0]; ReLU (asked for, or the stored type is u8); store
+ *      with a separately rounded add and multiply, never an FMA, and the x86 conversion and saturations of
+ *      csrc/dfx_device.cuh (f32: the value; s32: vcvtps2dq under the round mode; s8 / u8: that, then signed / unsigned
+ *      saturation).
+ *
+ *      Optional table (lut_in_dt = DFX_U8 | DFX_S8; DFX_UNDEF: none; dfx_linear_set_table).  The requant above produces the
+ *      byte t the op would have stored with dst_dt = lut_in_dt; the op stores lut[lut_in_dt == DFX_U8 ? t : t + 128]
+ *      instead -- dfx_wsum's and dfx_se's index convention.  dst_dt must be u8 or s8 and the table's bytes are stored
+ *      verbatim.  With a table, ReLU is decided by relu / lut_in_dt, not by dst_dt.  This is how GELU rides behind fc1
+ *      without another pass over the widest tensor of the block (Python: dfa.gelu_table).
+ *
+ *      Requant route: "fast" / "exact", proved at set_weights from the actual weights as dfx_fc proves it: fast when the
+ *      round mode is nearest, DFX_NO_FAST is not set and, for every n, bias and scale are finite and
+ *      (B + |bias|) * |scale| <= 2^30, B = 255 * max(P, N) for a u8 src and 128 * (P + N) for an s8 src (P, N: the sums of
+ *      the row's positive / negative weights' magnitudes).  The generic kernel is always exact and defines the bits.
+ *
+ *      Not built: a fused residual add (dfx_wsum joins the residual); split-K for few tiles under a deep K; k > 65025;
+ *      s32 / f32 sources; u8 weights; a fused layer norm in front; multi-device sharding.
+ *      Parity unpinned: the reference has no such op. ---- */
+typedef struct dfx_linear_desc {
+  int64_t rows;                /* >= 1; rows * max(src_ld, dst_ld) <= 2^40 */
+  int32_t k, n;
+  int32_t src_dt;              /* DFX_U8 | DFX_S8 */
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8; with a table DFX_S8 | DFX_U8 */
+  int32_t bia_dt;              /* DFX_UNDEF = none */
+  int32_t relu, round_mode, nscales /* 1 | n */;
+  int32_t lut_in_dt;           /* DFX_UNDEF = no table | DFX_U8 | DFX_S8 */
+  int32_t force_path;          /* -1 auto | DFX_LINEAR_TILE | DFX_LINEAR_GENERIC */
+  int64_t src_ld, dst_ld;      /* elements between rows: >= k, >= n */
+} dfx_linear_desc;
+enum {  /* dfx_linear_info.path */
+  DFX_LINEAR_TILE = 0,         /* linear_tile_kernel<BM> (linear.cuh): 256 lanes own a BM x 128 tile of dst, BM = 128, or 64 where
+                                  128 would leave fewer tiles than CUs; K in slabs of 64; each slab of the token tile and of the
+                                  weight block goes global -> LDS once per workgroup (two buffers, one barrier per slab) and
+                                  feeds v_mfma_i32_32x32x32_i8 through conflict-free 16-byte LDS reads; the weights are packed
+                                  by the host in the tile's own order (linear_pack.h).  Class: src_ld % 16 == 0; src 16-byte
+                                  aligned (checked per submit: others take the generic kernel for that submit).  In this
+                                  class a row is read up to k rounded up to 16, which lies within its pitch and within the
+                                  16-byte granule of its last valid byte.  4 adjacent n leave as one store where dst is
+                                  aligned for it and dst_ld % 4 == 0. */
+  DFX_LINEAR_GENERIC = 1       /* one thread per dst element, grid-stride, any pitch and alignment, exact requant.  It defines
+                                  the bits. */
+};
+/* DFX_LINEAR_AUTO_NOTE: measured with tools/bench_linear on one MI355X (profiles/linear/bench_linear.txt: s8 in and out, forced
+ * legs alternating in one process, buffer sets in rotation beyond the Infinity Cache, windows of at least 3 ms, median of 5
+ * rounds; the rounds' extremes are in the file: most legs stay within 1 % of their median, the widest reaches + 11 %).  The yardstick is dfx_bmm's MFMA kernel
+ * on the same operands (the weights as a device B, no bias).  At the tile height the plan takes, the tile kernel beat it and the
+ * generic kernel at all 14 points, by far more than the rounds' spread at 12 of them and by 6 % and 7 % at the two smallest:
+ *   ViT-B rows 1576:  768->2304 11.8 us against 29.0;  768->768 10.5 / 16.4;  768->3072 + table 16.7 / 35.9;  3072->768 29.8 / 52.5
+ *   ViT-B rows 12608: 768->2304 58.4 / 175.6;  768->768 29.2 / 68.9;  768->3072 + table 80.4 / 231.8;  3072->768 74.7 / 252.7
+ *   Swin stage 1 rows 9408: 96->288 6.93 / 7.34;  96->384 + table 6.82 / 7.38;  384->96 7.44 / 8.69
+ *   DETR rows 1700:   256->256 6.10 / 6.56;  256->2048 7.31 / 13.1;  2048->256 20.7 / 25.3
+ * (the generic kernel: 108 us to 25.9 ms).  AUTO RULE: DFX_LINEAR_TILE in its class from the smallest of each size that was
+ * measured -- rows >= 1576, n >= 96, k >= 96, at least 54 tiles of 64 x 128 and 1700 * 256 * 256 multiply-adds -- and
+ * DFX_LINEAR_GENERIC everywhere else: nothing smaller was timed.  Where it LOSES: few tiles under a deep K, to dfx_fc's split-K
+ * on a u8 copy of src -- 3072->768 at rows 1576 takes 29.8 us against 20.4, 2048->256 at rows 1700 20.7 against 14.3 -- and it
+ * reaches 17 % of the 4600 TOP/s int8 matrix peak at best; eager torch._int_mm / f16 torch.matmul (no requant) are 1.18x to 1.35x
+ * faster on the four ViT-B rows-12608 matrices and 1.54x at 3072->768 rows 1576 (profiles/linear/speed_vs_torch.txt; DESIGN.md
+ * section 4.24). */
+typedef struct dfx_linear_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  uint64_t algorithmic_ops;    /* 2 * rows * n * k */
+  uint64_t algorithmic_bytes;  /* rows * k src bytes + n * k weights + rows * n dst elements + bias (4 n) + scales (4 each) +
+                                  the table (256) */
+  char kernel_name[96];        /* "linear_tile<s8,s8,bm128> fast +lut", "linear_generic<u8,f32>": src type, dst type */
+} dfx_linear_info;
+typedef struct dfx_linear dfx_linear_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -1871,6 +1952,32 @@ int dfx_lnorm_submit(dfx_lnorm_t *h, const void *src_dev, void *dst_dev, dfx_str
 int dfx_lnorm_query(const dfx_lnorm_t *h, dfx_lnorm_info *info);
 int dfx_lnorm_destroy(dfx_lnorm_t *h);
 
+/* ---- int8 token linear layer (dfx_linear_desc above).  The descriptor is validated before anything touches a device, in
+ *      this order: DFX_ERR_INVALID for rows < 1, k outside 1 .. 65025, n outside 1 .. 2^31 - 128, a src dtype other than u8 /
+ *      s8, a bad dst dtype, bias dtype, round mode, a scales count other than 1 or n, a lut_in_dt other than none / u8 / s8,
+ *      a table with a 4-byte dst, a bad force_path, src_ld < k, dst_ld < n, rows * max(src_ld, dst_ld) > 2^40; then
+ *      DFX_ERR_UNSUPPORTED only for force_path = DFX_LINEAR_TILE outside that class.  "No HIP device" is reported only for
+ *      a valid descriptor.
+ *      set_weights: host pointers, copied: wei s8 {n, k} row-major, bia n entries of bia_dt (NULL when DFX_UNDEF), scales
+ *      nscales floats.  It packs the device image (weights in the tile's order | compensation | bias | scale | table),
+ *      proves the requant route and may be called again (not while a submit of the handle is in flight).
+ *      set_table: 256 host bytes, copied; DFX_ERR_INVALID on a handle created without a table.  May be called again.
+ *      submit: asynchronous on `s`; ONE launch with its own arguments; it never writes to the handle: one handle serves
+ *      several streams and host threads at once.  DFX_ERR_STATE, with nothing launched, before set_weights and, on a
+ *      handle created with a table, before set_table.  DFX_ERR_INVALID, with nothing launched, for a null pointer, a dst
+ *      that is not aligned to its element and a dst that overlaps src.  A src that is not 16-byte aligned takes the generic
+ *      kernel for that submit.  submit_host: synchronous, densely packed host tensors (src {rows, k}, dst {rows, n}) only
+ *      where src_ld == k and dst_ld == n (DFX_ERR_UNSUPPORTED otherwise).
+ *      Tuning switches: DFX_LINEAR_GRID=n caps the grid of either kernel; DFX_LINEAR_BM=64|128 fixes the tile height.
+ *      No CPU fallback.  Auto: DFX_LINEAR_AUTO_NOTE. ---- */
+int dfx_linear_create(const dfx_linear_desc *desc, dfx_linear_t **out);
+int dfx_linear_set_weights(dfx_linear_t *h, const int8_t *wei, const void *bia, const float *scales);
+int dfx_linear_set_table(dfx_linear_t *h, const uint8_t lut[256]);
+int dfx_linear_submit(dfx_linear_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_linear_submit_host(dfx_linear_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_linear_query(const dfx_linear_t *h, dfx_linear_info *info);
+int dfx_linear_destroy(dfx_linear_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -1981,6 +2088,11 @@ int dfx_debug_bmm_requant(const dfx_bmm_t *h, int32_t out[1]);
 int dfx_debug_attn_launches(int64_t out[2]);
 /* the same for dfx_lnorm_submit: out[DFX_LNORM_ROW], out[DFX_LNORM_GENERIC] */
 int dfx_debug_lnorm_launches(int64_t out[2]);
+/* the same for dfx_linear_submit: out[DFX_LINEAR_TILE], out[DFX_LINEAR_GENERIC] */
+int dfx_debug_linear_launches(int64_t out[2]);
+/* the token linear op's one stage as the last dfx_linear_set_weights proved it, same numbering (0 exact, 1 fast; the generic
+ * path is always exact).  DFX_ERR_STATE before set_weights. */
+int dfx_debug_linear_requant(const dfx_linear_t *h, int32_t out[1]);
 
 #ifdef __cplusplus
 }

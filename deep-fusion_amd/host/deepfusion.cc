@@ -140,7 +140,7 @@ inline std::vector<shard_range> plan_shards(int batch) {
   return v;
 }
 
-// shared plumbing of the two ops: access to the tensors' private state
+// shared plumbing of the ops (op_base holds one): access to the tensors' private state
 struct op_state {
   dfx_stream_t stream = nullptr;
 
@@ -218,10 +218,10 @@ struct op_state {
   }
   // this op's stream has just been synchronised: nothing it launched is still writing its output or reading its inputs;
   // ops on other streams need not (and, once this op is gone, could not) wait on it
-  void settled(memory &) { unregister(); }
+  void settled() { unregister(); }
   // the op is being destroyed while a launch of it may still be writing its output or reading an input (the reference
   // only asks that tensors outlive ops): finish that work, then forget the stream -- it is about to be destroyed
-  void retire(memory &) {
+  void retire() {
     if (stream && !touched.empty()) {
       dfx_stream_sync(stream);
       unregister();
@@ -257,11 +257,15 @@ struct op_state {
     m.st_->producer = nullptr;
     m.st_->device_ahead = false;
   }
-  ~op_state() {
+  // the events and the stream go (op_base::teardown, before the tensors a derived class owns)
+  void close() {
     if (ev0) dfx_event_destroy(ev0);
     if (ev1) dfx_event_destroy(ev1);
     if (stream) dfx_stream_destroy(stream);
+    ev0 = ev1 = nullptr;
+    stream = nullptr;
   }
+  ~op_state() { close(); }
 };
 
 }  // namespace detail
@@ -349,8 +353,247 @@ void op::wait() {}
 
 namespace {
 
+int to_dfx_round(round_mode rm) { return rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST; }
+
+// a dfx_*_destroy as a function of the opaque handle that op_base keeps
+template <class H, int (*Destroy)(H *)>
+int destroy_as(void *h) {
+  return Destroy(static_cast<H *>(h));
+}
+// a dfx_*_create that takes (descriptor, handle): `fmt` is the class's "Init ... op failed! (%s)"
+template <class H, class D>
+void *create_or_exit(int (*create)(const D *, H **), const D &d, const char *fmt) {
+  H *h = nullptr;
+  if (create(&d, &h) != DFX_OK) error_and_exit(fmt, dfx_last_error());
+  return h;
+}
+
+// ---- what every op class shares: submit / submit_async / wait / infer, the single-device run, the batch shards of
+// DEEPFUSION_DEVICES, the profile brackets and the borrowed-weights protocol.  A derived class validates, fills its
+// descriptor and then says, in its constructor:
+//   reads(m, bytes per image [, own])   the tensors a launch reads, in the order launch() gets their device pointers.  m may be
+//                                       null (an optional tensor: the slot stays, its pointer is null).  own: a tensor of the op
+//                                       itself that no caller can refill behind data()'s back -- even submit() trusts its version
+//                                       counter and uploads it once
+//   writes(m, bytes per image)          the tensors it writes.  The order is at once the order of device_out(), of the copies back
+//                                       in submit() and of a shard's downloads
+//   borrows(m)                          a host tensor of the caller's that pack() reads (weights, biases); null is skipped.  None
+//                                       at all: nothing is ever packed (squeeze_excite's pool-only mode, every op without weights)
+//   build(batch, create)                LAST: create(n) makes a handle for n images on the current device, with whatever follows
+//                                       a create (set_params, set_table).  batch > 0: the class shards over that many images,
+//                                       tensors are batch-major and bytes per image must be given.  0: one handle on one device
+// and overrides pack(handle) and launch(handle, pointers, stream): pointers are the reads', then the writes'.  The base
+// constructor takes the handle's destroy function (a destructor cannot call down into a derived class). ----
+class op_base : public op {
+public:
+  ~op_base() override { teardown(); }
+
+  void submit() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      sync_shards();
+      return;
+    }
+    run(true);
+    fetch_outputs();
+    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+    st_.settled();
+  }
+  // (sharded: host in -> host out like submit(), without the final wait; the device-resident
+  // chaining extension is single-device)
+  void submit_async() override {
+    if (!shards_.empty()) {
+      enqueue_shards();
+      return;
+    }
+    run(false);
+    if (fetch_on_async_ && detail::requested_shards() > 1) fetch_outputs();
+  }
+  void wait() override {
+    if (!shards_.empty()) {
+      sync_shards();
+    } else {
+      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
+      st_.settled();
+    }
+  }
+
+protected:
+  explicit op_base(int (*destroy)(void *)) : destroy_(destroy) {}
+
+  void reads(memory *m, size_t img = 0, bool own = false) { reads_.push_back(tensor{m, img, own}); }
+  void writes(memory *m, size_t img = 0) { writes_.push_back(tensor{m, img, false}); }
+  void borrows(memory *m) {
+    if (m) weights_.push_back(m);
+  }
+  size_t n_reads() const { return reads_.size(); }
+
+  template <class Create>
+  void build(int batch, Create create) {
+    if (batch > 0) {
+      for (const detail::shard_range &r : detail::plan_shards(batch)) {
+        shard sh;
+        sh.r = r;
+        check_dfx(dfx_set_device(r.device), "set device");
+        sh.h = create(r.n);
+        check_dfx(dfx_stream_create(&sh.stream), "stream create");
+        for (const std::vector<tensor> *list : {&reads_, &writes_})
+          for (const tensor &t : *list) {
+            void *p = nullptr;
+            if (t.m) check_dfx(dfx_mem_alloc_device(&p, (size_t)r.n * t.img), "device alloc");
+            sh.buf.push_back(p);
+          }
+        shards_.push_back(sh);
+      }
+    }
+    if (!shards_.empty()) {
+      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+      return;
+    }
+    h_ = create(batch);
+    ptr_.resize(reads_.size() + writes_.size());
+    st_.ensure_stream();
+  }
+  // What a destructor does, in the order the C ABI sees it: per shard set device, handle, stream, input buffers, output
+  // buffers; back to the first shard's device; wait for a launch that is still in flight (retire); the handle; the events
+  // and the stream.  The destructor calls it; a class that owns tensors its launches read (op_nms) calls it from its own
+  // destructor, before those tensors go.  The second call does nothing.
+  void teardown() {
+    if (torn_down_) return;
+    torn_down_ = true;
+    for (shard &sh : shards_) {
+      dfx_set_device(sh.r.device);
+      destroy_(sh.h);
+      dfx_stream_destroy(sh.stream);
+      for (void *p : sh.buf) dfx_mem_free_device(p);
+    }
+    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
+    st_.retire();
+    destroy_(h_);
+    st_.close();
+  }
+
+  void infer() override {
+    if (!shards_.empty()) enqueue_shards();
+    else run(true);
+  }
+  // set_weights (and its like) on `h` from the borrowed tensors; only called when there are any
+  virtual void pack(void * /*handle*/) {}
+  // enqueue the op on `s`: p[0 .. reads) are the device pointers of the reads, p[reads ..) of the writes, null where absent
+  virtual void launch(void *handle, void *const *p, dfx_stream_t s) = 0;
+
+  // OPTION (op_conv_pool, op_eltwise): under DEEPFUSION_DEVICES > 1 submit_async() also copies the result to the host, where
+  // a sharded neighbour, which works host to host, finds it after wait().  The other classes that do not shard leave the
+  // result on the device; the difference is historical and kept as it is.
+  bool fetch_on_async_ = false;
+
+private:
+  struct tensor {
+    memory *m;
+    size_t img;  // bytes per image (sharding classes)
+    bool own;
+  };
+  struct shard {
+    detail::shard_range r;
+    void *h = nullptr;
+    dfx_stream_t stream = nullptr;
+    std::vector<void *> buf;  // this shard's images of every read, then of every write; null where the tensor is absent
+    unsigned long long wei_seen = 0;  // hash of the weights the handle was packed from
+  };
+
+  unsigned long long weights_hash() const {
+    unsigned long long v = 1469598103934665603ull;
+    for (memory *m : weights_) v = detail::hash_bytes(m->host_data(), m->buffer_size(), v);
+    return v | 1ull;  // (never 0 = "nothing packed yet")
+  }
+  unsigned long long weights_versions() const {
+    unsigned long long v = 0;
+    for (memory *m : weights_) v += m->host_version();
+    return v;
+  }
+  void fetch_outputs() {
+    for (const tensor &t : writes_)
+      if (t.m) st_.fetch_out(*t.m);
+  }
+  // every shard: upload its images from the host tensors, launch, download into the host tensors
+  void enqueue_shards() {
+    const unsigned long long v = weights_.empty() ? 0 : weights_hash();
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      if (!weights_.empty() && v != sh.wei_seen) {
+        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+        pack(sh.h);
+        sh.wei_seen = v;
+      }
+      size_t k = 0;
+      for (const tensor &t : reads_) {
+        if (t.m)
+          check_dfx(dfx_memcpy_h2d(sh.buf[k], static_cast<const char *>(t.m->host_data()) + sh.r.n0 * t.img, sh.r.n * t.img, sh.stream),
+                    "H2D copy");
+        ++k;
+      }
+      launch(sh.h, sh.buf.data(), sh.stream);
+      for (const tensor &t : writes_) {
+        if (t.m)
+          check_dfx(dfx_memcpy_d2h(static_cast<char *>(const_cast<void *>(t.m->host_data())) + sh.r.n0 * t.img, sh.buf[k], sh.r.n * t.img,
+                                   sh.stream),
+                    "D2H copy");
+        ++k;
+      }
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+    for (const tensor &t : writes_)
+      if (t.m) detail::op_state::host_is_current(*t.m);
+  }
+  void sync_shards() {
+    for (shard &sh : shards_) {
+      check_dfx(dfx_set_device(sh.r.device), "set device");
+      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
+    }
+    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
+  }
+  // sync_host == true: reference semantics (host buffers are re-read: inputs uploaded, weights
+  // re-packed when their bytes changed).  false: the asynchronous device-resident extension,
+  // which trusts the data() version counters.
+  void run(bool sync_host) {
+    // weights are borrowed host tensors the caller may rewrite between submits (the reference
+    // re-reads them on every call).  What the handle holds is described by TWO values taken at pack
+    // time: the hash of the packed bytes and the sum of the tensors' data() counters.  submit() re-reads
+    // the bytes (hash); submit_async() trusts the counters, and only when they moved looks at the bytes.
+    if (!weights_.empty()) {
+      const unsigned long long vers = weights_versions();
+      if (sync_host || vers != packed_versions_) {
+        const unsigned long long hash = weights_hash();
+        if (hash != packed_hash_) {
+          check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
+          pack(h_);
+          packed_hash_ = hash;
+        }
+        packed_versions_ = vers;
+      }
+    }
+    // (a tensor may be read and written: resize_add's lateral, scaled_sum's and squeeze_excite's src -- uploaded, then overwritten)
+    size_t k = 0;
+    for (const tensor &t : reads_) ptr_[k++] = t.m ? st_.sync_in(*t.m, sync_host && !t.own) : nullptr;
+    for (const tensor &t : writes_) ptr_[k++] = t.m ? st_.device_out(*t.m) : nullptr;
+    st_.profile_begin();
+    launch(h_, ptr_.data(), st_.stream);
+    st_.profile_end(name());
+  }
+
+  int (*destroy_)(void *);
+  detail::op_state st_;
+  std::vector<tensor> reads_, writes_;
+  std::vector<memory *> weights_;
+  void *h_ = nullptr;                                         // the single-device handle; null when sharded
+  unsigned long long packed_hash_ = 0, packed_versions_ = 0;  // what h_ was packed from (see run())
+  std::vector<void *> ptr_;                                   // run()'s device pointers, sized once
+  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1: one entry per batch shard; empty otherwise
+  bool torn_down_ = false;
+};
+
 // ---- conv: replaces op_conv<T> ----
-class op_conv : public op {
+class op_conv : public op_base {
 public:
   op_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei,
           const std::unique_ptr<memory> &bia, std::array<int, 2> stride, std::array<int, 2> pad,
@@ -358,8 +601,8 @@ public:
           const std::vector<float> &scales1, const std::unique_ptr<memory> &wei1x1,
           const std::unique_ptr<memory> &bia1x1, bool relu0, bool relu1, round_mode rm0,
           round_mode rm1)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), wei1_(wei1x1.get()), bia1_(bia1x1.get()),
-        dst_(dst.get()), scales0_(scales0), scales1_(scales1), h_(nullptr), packed_hash_(0), packed_versions_(0) {
+      : op_base(destroy_as<dfx_conv_t, dfx_conv_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), wei1_(wei1x1.get()), bia1_(bia1x1.get()),
+        dst_(dst.get()), scales0_(scales0), scales1_(scales1) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !dst_) error_and_exit("Init Conv op failed! (null tensor)");
     // dtype / format gate of jit_conv_kernel::init_conf (jit_conv_kernel.cc:531-564)
@@ -396,171 +639,45 @@ public:
     d.bia0_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.bia1_dt = bia1_ ? to_dfx_dtype(bia1_->data_type()) : DFX_UNDEF;
     d.conv0_relu = relu0; d.conv1_relu = relu1;
-    d.conv0_round_mode = rm0 == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
-    d.conv1_round_mode = rm1 == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.conv0_round_mode = to_dfx_round(rm0);
+    d.conv1_round_mode = to_dfx_round(rm1);
     d.conv0_nscales = (int)scales0_.size();
     d.conv1_nscales = wei1_ ? (int)scales1_.size() : 1;
     d.force_variant = -1;
     const size_t src_img = (size_t)d.ih * d.iw * d.ic;
     const size_t dst_img = (size_t)d.oh * d.ow * (d.oc1x1 ? d.oc1x1 : d.oc) * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
-      sh.src_off = r.n0 * src_img; sh.src_bytes = r.n * src_img;
-      sh.dst_off = r.n0 * dst_img; sh.dst_bytes = r.n * dst_img;
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    borrows(wei_); borrows(bia_); borrows(wei1_); borrows(bia1_);
+    build(d.bs, [&](int n) -> void * {
       dfx_conv_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_conv_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init Conv op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, sh.src_bytes), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, sh.dst_bytes), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_conv_create(&d, &h_) != DFX_OK) error_and_exit("Init Conv op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_conv() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_conv_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_conv_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  // (sharded: host in -> host out like submit(), without the final wait; the device-resident
-  // chaining extension is single-device)
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_conv_create, ds, "Init Conv op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
+  void pack(void *h) override {
+    check_dfx(dfx_conv_set_weights(static_cast<dfx_conv_t *>(h), (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr,
+                                   scales0_.data(), wei1_ ? (const int8_t *)wei1_->host_data() : nullptr,
+                                   bia1_ ? bia1_->host_data() : nullptr, scales1_.data()),
+              "conv set_weights");
   }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    if (wei1_) v = hash_bytes(wei1_->host_data(), wei1_->buffer_size(), v);
-    if (bia1_) v = hash_bytes(bia1_->host_data(), bia1_->buffer_size(), v);
-    return v | 1ull;  // (never 0 = "nothing packed yet")
-  }
-  unsigned long long weights_versions() const {
-    return wei_->host_version() + (bia_ ? bia_->host_version() : 0) + (wei1_ ? wei1_->host_version() : 0) +
-           (bia1_ ? bia1_->host_version() : 0);
-  }
-  // every shard: upload its images from the host tensor, launch, download into the host tensor
-  void enqueue_shards() {
-    const unsigned long long v = weights_hash();
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        check_dfx(dfx_conv_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr,
-                                       scales0_.data(), wei1_ ? (const int8_t *)wei1_->host_data() : nullptr,
-                                       bia1_ ? bia1_->host_data() : nullptr, scales1_.data()),
-                  "conv set_weights");
-        sh.wei_seen = v;
-      }
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.src_off, sh.src_bytes, sh.stream), "H2D copy");
-      check_dfx(dfx_conv_submit(sh.h, sh.src, sh.dst, sh.stream), "conv submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.dst_off, sh.dst, sh.dst_bytes, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  // sync_host == true: reference semantics (host buffers are re-read: inputs uploaded, weights
-  // re-packed when their bytes changed).  false: the asynchronous device-resident extension,
-  // which trusts the data() version counters.
-  void run(bool sync_host) {
-    // weights are borrowed host tensors the caller may rewrite between submits (the reference
-    // re-reads them on every call).  What the handle holds is described by TWO values taken at pack
-    // time: the hash of the packed bytes and the sum of the tensors' data() counters.  submit() re-reads
-    // the bytes (hash); submit_async() trusts the counters, and only when they moved looks at the bytes.
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_conv_set_weights(h_, (const int8_t *)wei_->host_data(),
-                                       bia_ ? bia_->host_data() : nullptr, scales0_.data(),
-                                       wei1_ ? (const int8_t *)wei1_->host_data() : nullptr,
-                                       bia1_ ? bia1_->host_data() : nullptr, scales1_.data()),
-                  "conv set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    void *s = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_conv_submit(h_, s, o, st_.stream), "conv submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_conv_submit(static_cast<dfx_conv_t *>(h), p[0], p[1], s), "conv submit");
   }
   const char *name() override { return "conv"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_conv_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    size_t src_off = 0, src_bytes = 0, dst_off = 0, dst_bytes = 0;
-    unsigned long long wei_seen = 0;
-  };
   memory *src_, *wei_, *bia_, *wei1_, *bia1_, *dst_;
   std::vector<float> scales0_, scales1_;  // owned copies (the reference keeps a dangling pointer)
-  dfx_conv_t *h_;
-  unsigned long long packed_hash_, packed_versions_;  // what h_ was packed from (see run())
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1: one entry per batch shard; empty otherwise
 };
 
 // ---- concat: replaces op_concat<T> ----
-class op_concat : public op {
+class op_concat : public op_base {
 public:
   op_concat(const std::vector<std::unique_ptr<memory>> &srcs, std::unique_ptr<memory> &dst, bool relu)
-      : dst_(dst.get()), h_(nullptr) {
+      : op_base(destroy_as<dfx_concat_t, dfx_concat_destroy>), dst_(dst.get()) {
     if (!dst_ || srcs.empty()) error_and_exit("Init Concat op failed!");
     if (dst_->dim_format() != memory::format::nhwc) error_and_exit("Init Concat op failed! (format)");
     auto dm = dst_->actual_dims();  // {n,h,w,c}
@@ -584,134 +701,36 @@ public:
     d.post_relu = relu;
     d.channels = ch.data();
     const size_t esz = dtype_size(dst_->data_type()), px = (size_t)dm[1] * dm[2];
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    for (size_t k = 0; k < srcs_.size(); ++k) reads(srcs_[k], px * ch[k] * esz);
+    writes(dst_, px * total * esz);
+    build(d.bs, [&](int n) -> void * {
       dfx_concat_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_concat_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init Concat op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      for (int c : ch) {
-        void *p = nullptr;
-        check_dfx(dfx_mem_alloc_device(&p, (size_t)r.n * px * c * esz), "device alloc");
-        sh.srcs.push_back(p);
-        sh.src_img.push_back(px * c * esz);
-      }
-      sh.dst_img = px * total * esz;
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * sh.dst_img), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_concat_create(&d, &h_) != DFX_OK) error_and_exit("Init Concat op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_concat() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_concat_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      for (void *p : sh.srcs) dfx_mem_free_device(p);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_concat_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_concat_create, ds, "Init Concat op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
-  }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      std::vector<const void *> p;
-      for (size_t k = 0; k < srcs_.size(); ++k) {
-        const char *hs = static_cast<const char *>(srcs_[k]->host_data());
-        check_dfx(dfx_memcpy_h2d(sh.srcs[k], hs + sh.r.n0 * sh.src_img[k], sh.r.n * sh.src_img[k], sh.stream), "H2D copy");
-        p.push_back(sh.srcs[k]);
-      }
-      check_dfx(dfx_concat_submit(sh.h, p.data(), sh.dst, sh.stream), "concat submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * sh.dst_img, sh.dst, sh.r.n * sh.dst_img, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {
-    std::vector<const void *> p;
-    for (memory *m : srcs_) p.push_back(st_.sync_in(*m, sync_host));
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_concat_submit(h_, p.data(), o, st_.stream), "concat submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_concat_submit(static_cast<dfx_concat_t *>(h), p, p[n_reads()], s), "concat submit");
   }
   const char *name() override { return "concat"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_concat_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    std::vector<void *> srcs;
-    std::vector<size_t> src_img;  // bytes per image of each input
-    void *dst = nullptr;
-    size_t dst_img = 0;
-  };
   std::vector<memory *> srcs_;
   memory *dst_;
-  dfx_concat_t *h_;
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- conv + relu + max pooling (reference roadmap, README.md:64): the conv runs as the unfused conv
 // op into a device buffer the op owns (the intermediate never visits the host), the pooling kernel
 // reads it (from L2 / the Infinity Cache for the sizes of test_conv_relu_pooling.cc) ----
-class op_conv_pool : public op {
+class op_conv_pool : public op_base {
 public:
   op_conv_pool(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei,
                const std::unique_ptr<memory> &bia, std::array<int, 2> stride, std::array<int, 2> pad,
                std::array<int, 2> pk, std::array<int, 2> ps, std::array<int, 2> pp, std::unique_ptr<memory> &dst,
                bool relu, const std::vector<float> &scales, round_mode rm, pool_algo algo)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), conv_(nullptr),
-        pool_(nullptr), mid_(nullptr), packed_hash_(0), packed_versions_(0) {
+      : op_base(destroy_parts), src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !dst_) error_and_exit("Init ConvReluPool op failed! (null tensor)");
     bool ok = src_->data_type() == memory::dtype::u8 && wei_->data_type() == memory::dtype::s8 &&
@@ -736,104 +755,84 @@ public:
     d.bia0_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.bia1_dt = DFX_UNDEF;
     d.conv0_relu = relu;
-    d.conv0_round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.conv0_round_mode = to_dfx_round(rm);
     d.conv1_round_mode = DFX_ROUND_NEAREST;
     d.conv0_nscales = (int)scales_.size();
     d.conv1_nscales = 1;
     d.force_variant = -1;
-    // 2x2 stride-2 pooling without padding over an even-sized conv output: fused into the conv kernel's
-    // store stage where that kernel covers the conv (dfx.h, dfx_conv_desc::fuse_pool); one launch, the
-    // unpooled activation never exists
-    if (algo == pool_algo::max && pk[0] == 2 && pk[1] == 2 && ps[0] == 2 && ps[1] == 2 && pp[0] == 0 && pp[1] == 0 && ch % 2 == 0 && cw % 2 == 0 &&
-        o[2] == ch / 2 && o[3] == cw / 2) {
-      dfx_conv_desc df = d;
-      df.fuse_pool = 2;
-      if (dfx_conv_create(&df, &conv_) == DFX_OK) {
-        st_.ensure_stream();
-        return;
+    reads(src_);
+    writes(dst_);
+    borrows(wei_); borrows(bia_);
+    fetch_on_async_ = true;  // (this op is not sharded, its neighbours may be: see op_base)
+    build(0, [&](int) -> void * {
+      parts *h = new parts();
+      // 2x2 stride-2 pooling without padding over an even-sized conv output: fused into the conv kernel's
+      // store stage where that kernel covers the conv (dfx.h, dfx_conv_desc::fuse_pool); one launch, the
+      // unpooled activation never exists
+      if (algo == pool_algo::max && pk[0] == 2 && pk[1] == 2 && ps[0] == 2 && ps[1] == 2 && pp[0] == 0 && pp[1] == 0 && ch % 2 == 0 && cw % 2 == 0 &&
+          o[2] == ch / 2 && o[3] == cw / 2) {
+        dfx_conv_desc df = d;
+        df.fuse_pool = 2;
+        if (dfx_conv_create(&df, &h->conv) == DFX_OK) return h;
+        h->conv = nullptr;
       }
-      conv_ = nullptr;
-    }
-    if (dfx_conv_create(&d, &conv_) != DFX_OK) error_and_exit("Init ConvReluPool op failed! (%s)", dfx_last_error());
-    dfx_pool_desc p;
-    memset(&p, 0, sizeof(p));
-    p.bs = s[0]; p.c = w[0]; p.ih = ch; p.iw = cw; p.oh = o[2]; p.ow = o[3];
-    p.kh = pk[0]; p.kw = pk[1]; p.sh = ps[0]; p.sw = ps[1]; p.pad_t = pp[0]; p.pad_l = pp[1];
-    p.dt = d.dst_dt;
-    p.algo = algo == pool_algo::max ? DFX_POOL_MAX
-           : algo == pool_algo::avg_include_padding ? DFX_POOL_AVG_INCLUDE_PADDING : DFX_POOL_AVG_EXCLUDE_PADDING;
-    if (dfx_pool_create(&p, &pool_) != DFX_OK) error_and_exit("Init ConvReluPool op failed! (%s)", dfx_last_error());
-    check_dfx(dfx_mem_alloc_device(&mid_, (size_t)s[0] * ch * cw * w[0] * dtype_size(dst_->data_type())), "device alloc");
-    st_.ensure_stream();
-  }
-  ~op_conv_pool() override {
-    st_.retire(*dst_);
-    dfx_conv_destroy(conv_);
-    if (pool_) dfx_pool_destroy(pool_);
-    if (mid_) dfx_mem_free_device(mid_);
-  }
-  void submit() override {
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  // (this op is not sharded.  Under DEEPFUSION_DEVICES > 1 its neighbours are, and they work host to host: the result
-  // is sent to the host as well, where a sharded consumer finds it after wait())
-  void submit_async() override {
-    run(false);
-    if (detail::requested_shards() > 1) st_.fetch_out(*dst_);
-  }
-  void wait() override {
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
+      if (dfx_conv_create(&d, &h->conv) != DFX_OK) error_and_exit("Init ConvReluPool op failed! (%s)", dfx_last_error());
+      dfx_pool_desc p;
+      memset(&p, 0, sizeof(p));
+      p.bs = s[0]; p.c = w[0]; p.ih = ch; p.iw = cw; p.oh = o[2]; p.ow = o[3];
+      p.kh = pk[0]; p.kw = pk[1]; p.sh = ps[0]; p.sw = ps[1]; p.pad_t = pp[0]; p.pad_l = pp[1];
+      p.dt = d.dst_dt;
+      p.algo = algo == pool_algo::max ? DFX_POOL_MAX
+             : algo == pool_algo::avg_include_padding ? DFX_POOL_AVG_INCLUDE_PADDING : DFX_POOL_AVG_EXCLUDE_PADDING;
+      if (dfx_pool_create(&p, &h->pool) != DFX_OK) error_and_exit("Init ConvReluPool op failed! (%s)", dfx_last_error());
+      check_dfx(dfx_mem_alloc_device(&h->mid, (size_t)s[0] * ch * cw * w[0] * dtype_size(dst_->data_type())), "device alloc");
+      return h;
+    });
   }
 
 protected:
-  void infer() override { run(true); }
-  void run(bool sync_host) {
-    const unsigned long long vers = wei_->host_version() + (bia_ ? bia_->host_version() : 0);
-    if (sync_host || vers != packed_versions_) {  // (as op_conv::run)
-      unsigned long long hash = detail::hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-      if (bia_) hash = detail::hash_bytes(bia_->host_data(), bia_->buffer_size(), hash);
-      hash |= 1ull;
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-        check_dfx(dfx_conv_set_weights(conv_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr,
-                                       scales_.data(), nullptr, nullptr, nullptr),
-                  "conv set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    void *s = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    if (!pool_) {  // pooling fused into the conv kernel
-      check_dfx(dfx_conv_submit(conv_, s, o, st_.stream), "conv submit");
+  void pack(void *h) override {
+    check_dfx(dfx_conv_set_weights(static_cast<parts *>(h)->conv, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr,
+                                   scales_.data(), nullptr, nullptr, nullptr),
+              "conv set_weights");
+  }
+  void launch(void *hv, void *const *p, dfx_stream_t s) override {  // (both launches inside the one profile bracket)
+    parts *h = static_cast<parts *>(hv);
+    if (!h->pool) {  // pooling fused into the conv kernel
+      check_dfx(dfx_conv_submit(h->conv, p[0], p[1], s), "conv submit");
     } else {
-      check_dfx(dfx_conv_submit(conv_, s, mid_, st_.stream), "conv submit");
-      check_dfx(dfx_pool_submit(pool_, mid_, o, st_.stream), "pool submit");
+      check_dfx(dfx_conv_submit(h->conv, p[0], h->mid, s), "conv submit");
+      check_dfx(dfx_pool_submit(h->pool, h->mid, p[1], s), "pool submit");
     }
-    st_.profile_end(name());
   }
   const char *name() override { return "conv_relu_pool"; }
 
 private:
+  // OPTION: this class's handle is two handles and a buffer of its own -- the conv, and where the pooling is not fused
+  // into it the pooling op and the unpooled activation between them
+  struct parts {
+    dfx_conv_t *conv = nullptr;
+    dfx_pool_t *pool = nullptr;
+    void *mid = nullptr;
+  };
+  static int destroy_parts(void *hv) {
+    parts *h = static_cast<parts *>(hv);
+    if (!h) return DFX_OK;
+    dfx_conv_destroy(h->conv);
+    if (h->pool) dfx_pool_destroy(h->pool);
+    if (h->mid) dfx_mem_free_device(h->mid);
+    delete h;
+    return DFX_OK;
+  }
   memory *src_, *wei_, *bia_, *dst_;
   std::vector<float> scales_;
-  dfx_conv_t *conv_;
-  dfx_pool_t *pool_;
-  void *mid_;
-  unsigned long long packed_hash_, packed_versions_;
-  detail::op_state st_;
 };
 
 // ---- eltwise sum (+relu) (reference roadmap, README.md:65) ----
-class op_eltwise : public op {
+class op_eltwise : public op_base {
 public:
   op_eltwise(const std::vector<std::unique_ptr<memory>> &srcs, std::unique_ptr<memory> &dst, bool relu)
-      : dst_(dst.get()), h_(nullptr) {
+      : op_base(destroy_as<dfx_eltwise_t, dfx_eltwise_destroy>), dst_(dst.get()) {
     if (!dst_ || srcs.size() < 2) error_and_exit("Init EltwiseSum op failed!");
     for (auto &m : srcs) {
       if (!m || m->dim_format() != dst_->dim_format() || m->data_type() != dst_->data_type() ||
@@ -846,53 +845,29 @@ public:
     d.elems = (long long)dst_->size();
     d.dt = to_dfx_dtype(dst_->data_type());
     d.post_relu = relu;
-    if (dfx_eltwise_create(&d, &h_) != DFX_OK) error_and_exit("Init EltwiseSum op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_eltwise() override {
-    st_.retire(*dst_);
-    dfx_eltwise_destroy(h_);
-  }
-  void submit() override {
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {  // (not sharded: see op_conv_pool::submit_async)
-    run(false);
-    if (detail::requested_shards() > 1) st_.fetch_out(*dst_);
-  }
-  void wait() override {
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
+    for (memory *m : srcs_) reads(m);
+    writes(dst_);
+    fetch_on_async_ = true;  // (not sharded: see op_conv_pool)
+    build(0, [&](int) -> void * { return create_or_exit(dfx_eltwise_create, d, "Init EltwiseSum op failed! (%s)"); });
   }
 
 protected:
-  void infer() override { run(true); }
-  void run(bool sync_host) {
-    std::vector<const void *> p;
-    for (memory *m : srcs_) p.push_back(st_.sync_in(*m, sync_host));
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_eltwise_submit(h_, p.data(), o, st_.stream), "eltwise submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_eltwise_submit(static_cast<dfx_eltwise_t *>(h), p, p[n_reads()], s), "eltwise submit");
   }
   const char *name() override { return "eltwise_sum"; }
 
 private:
   std::vector<memory *> srcs_;
   memory *dst_;
-  dfx_eltwise_t *h_;
-  detail::op_state st_;
 };
 
 // ---- activation reorder (dfx_reorder_*): layout / dtype / scale conversion, channel pad and crop ----
-class op_reorder : public op {
+class op_reorder : public op_base {
 public:
   op_reorder(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &dst, const std::vector<float> &scales,
              round_mode rm)
-      : src_(src.get()), dst_(dst.get()), scales_(scales), h_(nullptr) {
+      : op_base(destroy_as<dfx_reorder_t, dfx_reorder_destroy>), src_(src.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!src_ || !dst_) error_and_exit("Init Reorder op failed! (null tensor)");
     for (memory *m : {src_, dst_})
@@ -907,125 +882,41 @@ public:
     d.dst_fmt = dst_->dim_format() == fmt::nhwc ? DFX_FMT_NHWC : DFX_FMT_NCHW;
     d.src_dt = to_dfx_dtype(src_->data_type());
     d.dst_dt = to_dfx_dtype(dst_->data_type());
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.n_scales = (int)scales_.size();
     // both layouts are batch-major: a batch shard is a contiguous byte range of src and of dst
     const size_t src_img = (size_t)d.h * d.w * d.src_c * dtype_size(src_->data_type());
     const size_t dst_img = (size_t)d.h * d.w * d.dst_c * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
-      sh.src_off = r.n0 * src_img; sh.src_bytes = r.n * src_img;
-      sh.dst_off = r.n0 * dst_img; sh.dst_bytes = r.n * dst_img;
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    build(d.bs, [&](int n) -> void * {
       dfx_reorder_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_reorder_create(&ds, scales_.data(), &sh.h) != DFX_OK) error_and_exit("Init Reorder op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, sh.src_bytes), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, sh.dst_bytes), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_reorder_create(&d, scales_.data(), &h_) != DFX_OK) error_and_exit("Init Reorder op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_reorder() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_reorder_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_reorder_destroy(h_);
-  }
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  // (sharded: host in -> host out like submit(), without the final wait -- see op_conv)
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      dfx_reorder_t *h = nullptr;
+      if (dfx_reorder_create(&ds, scales_.data(), &h) != DFX_OK) error_and_exit("Init Reorder op failed! (%s)", dfx_last_error());
+      return h;
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
-  }
-  void enqueue_shards() {
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.src_off, sh.src_bytes, sh.stream), "H2D copy");
-      check_dfx(dfx_reorder_submit(sh.h, sh.src, sh.dst, sh.stream), "reorder submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.dst_off, sh.dst, sh.dst_bytes, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {
-    void *s = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_reorder_submit(h_, s, o, st_.stream), "reorder submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_reorder_submit(static_cast<dfx_reorder_t *>(h), p[0], p[1], s), "reorder submit");
   }
   const char *name() override { return "reorder"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_reorder_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    size_t src_off = 0, src_bytes = 0, dst_off = 0, dst_bytes = 0;
-  };
   memory *src_, *dst_;
   std::vector<float> scales_;
-  dfx_reorder_t *h_;
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- concat + pointwise conv in one launch (dfx_catconv_*): the branches are read in place, the concatenated
 // tensor is never written.  Checks are op_concat's for the branches and op_conv's for weights, bias and dst. ----
-class op_concat_conv : public op {
+class op_concat_conv : public op_base {
 public:
   op_concat_conv(const std::vector<std::unique_ptr<memory>> &srcs, const std::unique_ptr<memory> &wei,
                  const std::unique_ptr<memory> &bia, std::unique_ptr<memory> &dst, bool relu,
                  const std::vector<float> &scales, round_mode rm)
-      : wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0), packed_versions_(0) {
+      : op_base(destroy_as<dfx_catconv_t, dfx_catconv_destroy>), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!wei_ || !dst_ || srcs.empty()) error_and_exit("Init ConcatConv op failed! (null tensor)");
     if (wei_->data_type() != memory::dtype::s8 || dst_->dim_format() != fmt::nhwc ||
@@ -1056,166 +947,47 @@ public:
     d.dst_dt = to_dfx_dtype(dst_->data_type());
     d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.relu = relu;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)scales_.size();
     d.force_path = -1;
     d.channels = ch.data();
     const size_t px = (size_t)d.h * d.w;
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    for (size_t k = 0; k < srcs_.size(); ++k) reads(srcs_[k], px * ch[k]);  // (a shard is an offset into every branch)
+    writes(dst_, px * d.oc * dtype_size(dst_->data_type()));
+    borrows(wei_); borrows(bia_);
+    build(d.bs, [&](int n) -> void * {
       dfx_catconv_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_catconv_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init ConcatConv op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      for (int c : ch) {
-        void *p = nullptr;
-        check_dfx(dfx_mem_alloc_device(&p, (size_t)r.n * px * c), "device alloc");
-        sh.srcs.push_back(p);
-        sh.src_img.push_back(px * c);
-      }
-      sh.dst_img = px * d.oc * dtype_size(dst_->data_type());
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * sh.dst_img), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_catconv_create(&d, &h_) != DFX_OK) error_and_exit("Init ConcatConv op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_concat_conv() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_catconv_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      for (void *p : sh.srcs) dfx_mem_free_device(p);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_catconv_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_catconv_create, ds, "Init ConcatConv op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
+  void pack(void *h) override {
+    check_dfx(dfx_catconv_set_weights(static_cast<dfx_catconv_t *>(h), (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr,
+                                      scales_.data()),
+              "concat_conv set_weights");
   }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    return v | 1ull;
-  }
-  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard; a shard is an offset into every branch)
-    const unsigned long long v = weights_hash();
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        check_dfx(dfx_catconv_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "concat_conv set_weights");
-        sh.wei_seen = v;
-      }
-      std::vector<const void *> p;
-      for (size_t k = 0; k < srcs_.size(); ++k) {
-        const char *hs = static_cast<const char *>(srcs_[k]->host_data());
-        check_dfx(dfx_memcpy_h2d(sh.srcs[k], hs + sh.r.n0 * sh.src_img[k], sh.r.n * sh.src_img[k], sh.stream), "H2D copy");
-        p.push_back(sh.srcs[k]);
-      }
-      check_dfx(dfx_catconv_submit(sh.h, p.data(), sh.dst, sh.stream), "concat_conv submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * sh.dst_img, sh.dst, sh.r.n * sh.dst_img, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_catconv_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "concat_conv set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    std::vector<const void *> p;
-    for (memory *m : srcs_) p.push_back(st_.sync_in(*m, sync_host));
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_catconv_submit(h_, p.data(), o, st_.stream), "concat_conv submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_catconv_submit(static_cast<dfx_catconv_t *>(h), p, p[n_reads()], s), "concat_conv submit");
   }
   const char *name() override { return "concat_conv"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_catconv_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    std::vector<void *> srcs;
-    std::vector<size_t> src_img;  // bytes per image of each branch
-    void *dst = nullptr;
-    size_t dst_img = 0;
-    unsigned long long wei_seen = 0;
-  };
   std::vector<memory *> srcs_;
   memory *wei_, *bia_, *dst_;
   std::vector<float> scales_;
-  dfx_catconv_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- depthwise conv (dfx_dwconv_*): every channel has its own kh x kw window.  Checks are op_conv's; the weights are
 // a plain oihw {c, 1, kh, kw} tensor, and dst's dims give the output size (windows may hang over the bottom / right
 // edge). ----
-class op_depthwise_conv : public op {
+class op_depthwise_conv : public op_base {
 public:
   op_depthwise_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
                     std::array<int, 2> stride, std::array<int, 2> padding, std::unique_ptr<memory> &dst, bool relu,
                     const std::vector<float> &scales, round_mode rm)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0),
-        packed_versions_(0) {
+      : op_base(destroy_as<dfx_dwconv_t, dfx_dwconv_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !dst_) error_and_exit("Init DepthwiseConv op failed! (null tensor)");
     if (src_->data_type() != memory::dtype::u8 || wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc ||
@@ -1233,152 +1005,45 @@ public:
     d.dst_dt = to_dfx_dtype(dst_->data_type());
     d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.relu = relu;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)scales_.size();
     d.force_path = -1;
-    src_img_ = (size_t)d.ih * d.iw * d.c;
-    dst_img_ = (size_t)d.oh * d.ow * d.c * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)d.ih * d.iw * d.c;
+    const size_t dst_img = (size_t)d.oh * d.ow * d.c * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    borrows(wei_); borrows(bia_);
+    build(d.bs, [&](int n) -> void * {
       dfx_dwconv_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_dwconv_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init DepthwiseConv op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_dwconv_create(&d, &h_) != DFX_OK) error_and_exit("Init DepthwiseConv op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_depthwise_conv() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_dwconv_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_dwconv_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_dwconv_create, ds, "Init DepthwiseConv op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
+  void pack(void *h) override {
+    const void *bia = bia_ ? bia_->host_data() : nullptr;
+    check_dfx(dfx_dwconv_set_weights(static_cast<dfx_dwconv_t *>(h), (const int8_t *)wei_->host_data(), bia, scales_.data()), "depthwise_conv set_weights");
   }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    return v | 1ull;
-  }
-  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const unsigned long long v = weights_hash();
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        check_dfx(dfx_dwconv_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "depthwise_conv set_weights");
-        sh.wei_seen = v;
-      }
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_dwconv_submit(sh.h, sh.src, sh.dst, sh.stream), "depthwise_conv submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_dwconv_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "depthwise_conv set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_dwconv_submit(h_, in, o, st_.stream), "depthwise_conv submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_dwconv_submit(static_cast<dfx_dwconv_t *>(h), p[0], p[1], s), "depthwise_conv submit");
   }
   const char *name() override { return "depthwise_conv"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_dwconv_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    unsigned long long wei_seen = 0;
-  };
   memory *src_, *wei_, *bia_, *dst_;
   std::vector<float> scales_;
-  dfx_dwconv_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- grouped conv (dfx_gconv_*): output channel o reads the ic / groups input channels of its group.  Checks are
 // op_depthwise_conv's; the weights are a plain oihw {oc, ic / groups, kh, kw} tensor, and dst's dims give the output size
-// (windows may hang over the bottom / right edge).  Weight hashing and batch sharding are op_depthwise_conv's. ----
-class op_grouped_conv : public op {
+// (windows may hang over the bottom / right edge).  Weight hashing and batch sharding are op_base's. ----
+class op_grouped_conv : public op_base {
 public:
   op_grouped_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
                   int groups, std::array<int, 2> stride, std::array<int, 2> padding, std::unique_ptr<memory> &dst, bool relu,
                     const std::vector<float> &scales, round_mode rm)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0),
-        packed_versions_(0) {
+      : op_base(destroy_as<dfx_gconv_t, dfx_gconv_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !dst_) error_and_exit("Init GroupedConv op failed! (null tensor)");
     if (src_->data_type() != memory::dtype::u8 || wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc ||
@@ -1396,152 +1061,45 @@ public:
     d.dst_dt = to_dfx_dtype(dst_->data_type());
     d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.relu = relu;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)scales_.size();
     d.force_path = -1;
-    src_img_ = (size_t)d.ih * d.iw * d.ic;
-    dst_img_ = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)d.ih * d.iw * d.ic;
+    const size_t dst_img = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    borrows(wei_); borrows(bia_);
+    build(d.bs, [&](int n) -> void * {
       dfx_gconv_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_gconv_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init GroupedConv op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_gconv_create(&d, &h_) != DFX_OK) error_and_exit("Init GroupedConv op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_grouped_conv() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_gconv_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_gconv_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_gconv_create, ds, "Init GroupedConv op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
+  void pack(void *h) override {
+    const void *bia = bia_ ? bia_->host_data() : nullptr;
+    check_dfx(dfx_gconv_set_weights(static_cast<dfx_gconv_t *>(h), (const int8_t *)wei_->host_data(), bia, scales_.data()), "grouped_conv set_weights");
   }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    return v | 1ull;
-  }
-  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const unsigned long long v = weights_hash();
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        check_dfx(dfx_gconv_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "grouped_conv set_weights");
-        sh.wei_seen = v;
-      }
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_gconv_submit(sh.h, sh.src, sh.dst, sh.stream), "grouped_conv submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_gconv_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "grouped_conv set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_gconv_submit(h_, in, o, st_.stream), "grouped_conv submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_gconv_submit(static_cast<dfx_gconv_t *>(h), p[0], p[1], s), "grouped_conv submit");
   }
   const char *name() override { return "grouped_conv"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_gconv_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    unsigned long long wei_seen = 0;
-  };
   memory *src_, *wei_, *bia_, *dst_;
   std::vector<float> scales_;
-  dfx_gconv_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- first-layer conv over a 1- to 4-channel image (dfx_imgconv_*).  Checks are op_grouped_conv's; the weights are a
 // plain oihw {oc, ic, kh, kw} tensor, and dst's dims give the output size (windows may hang over the bottom / right
-// edge).  Weight hashing and batch sharding are op_depthwise_conv's. ----
-class op_image_conv : public op {
+// edge).  Weight hashing and batch sharding are op_base's. ----
+class op_image_conv : public op_base {
 public:
   op_image_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
                 std::array<int, 2> stride, std::array<int, 2> padding, std::unique_ptr<memory> &dst, bool relu,
                 const std::vector<float> &scales, round_mode rm)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0),
-        packed_versions_(0) {
+      : op_base(destroy_as<dfx_imgconv_t, dfx_imgconv_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !dst_) error_and_exit("Init ImageConv op failed! (null tensor)");
     if (src_->data_type() != memory::dtype::u8 || wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc ||
@@ -1559,152 +1117,45 @@ public:
     d.dst_dt = to_dfx_dtype(dst_->data_type());
     d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.relu = relu;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)scales_.size();
     d.force_path = -1;
-    src_img_ = (size_t)d.ih * d.iw * d.ic;
-    dst_img_ = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)d.ih * d.iw * d.ic;
+    const size_t dst_img = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    borrows(wei_); borrows(bia_);
+    build(d.bs, [&](int n) -> void * {
       dfx_imgconv_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_imgconv_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init ImageConv op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_imgconv_create(&d, &h_) != DFX_OK) error_and_exit("Init ImageConv op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_image_conv() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_imgconv_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_imgconv_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_imgconv_create, ds, "Init ImageConv op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
+  void pack(void *h) override {
+    const void *bia = bia_ ? bia_->host_data() : nullptr;
+    check_dfx(dfx_imgconv_set_weights(static_cast<dfx_imgconv_t *>(h), (const int8_t *)wei_->host_data(), bia, scales_.data()), "image_conv set_weights");
   }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    return v | 1ull;
-  }
-  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const unsigned long long v = weights_hash();
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        check_dfx(dfx_imgconv_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "image_conv set_weights");
-        sh.wei_seen = v;
-      }
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_imgconv_submit(sh.h, sh.src, sh.dst, sh.stream), "image_conv submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_imgconv_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "image_conv set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_imgconv_submit(h_, in, o, st_.stream), "image_conv submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_imgconv_submit(static_cast<dfx_imgconv_t *>(h), p[0], p[1], s), "image_conv submit");
   }
   const char *name() override { return "image_conv"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_imgconv_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    unsigned long long wei_seen = 0;
-  };
   memory *src_, *wei_, *bia_, *dst_;
   std::vector<float> scales_;
-  dfx_imgconv_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- transposed conv (dfx_deconv_*).  Checks are op_grouped_conv's; the weights are a plain oihw {oc, ic, kh, kw} tensor
 // (oneDNN's logical order for deconvolution), and dst's dims give the output size (output_padding, cropping).  Weight
-// hashing and batch sharding are op_depthwise_conv's. ----
-class op_deconvolution : public op {
+// hashing and batch sharding are op_base's. ----
+class op_deconvolution : public op_base {
 public:
   op_deconvolution(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
                 std::array<int, 2> stride, std::array<int, 2> padding, std::unique_ptr<memory> &dst, bool relu,
                 const std::vector<float> &scales, round_mode rm)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0),
-        packed_versions_(0) {
+      : op_base(destroy_as<dfx_deconv_t, dfx_deconv_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !dst_) error_and_exit("Init Deconvolution op failed! (null tensor)");
     if (src_->data_type() != memory::dtype::u8 || wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc ||
@@ -1721,151 +1172,44 @@ public:
     d.dst_dt = to_dfx_dtype(dst_->data_type());
     d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.relu = relu;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)scales_.size();
     d.force_path = -1;
-    src_img_ = (size_t)d.ih * d.iw * d.ic;
-    dst_img_ = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)d.ih * d.iw * d.ic;
+    const size_t dst_img = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    borrows(wei_); borrows(bia_);
+    build(d.bs, [&](int n) -> void * {
       dfx_deconv_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_deconv_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init Deconvolution op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_deconv_create(&d, &h_) != DFX_OK) error_and_exit("Init Deconvolution op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_deconvolution() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_deconv_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_deconv_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_deconv_create, ds, "Init Deconvolution op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
+  void pack(void *h) override {
+    const void *bia = bia_ ? bia_->host_data() : nullptr;
+    check_dfx(dfx_deconv_set_weights(static_cast<dfx_deconv_t *>(h), (const int8_t *)wei_->host_data(), bia, scales_.data()), "deconvolution set_weights");
   }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    return v | 1ull;
-  }
-  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const unsigned long long v = weights_hash();
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        check_dfx(dfx_deconv_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "deconvolution set_weights");
-        sh.wei_seen = v;
-      }
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_deconv_submit(sh.h, sh.src, sh.dst, sh.stream), "deconvolution submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_deconv_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "deconvolution set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_deconv_submit(h_, in, o, st_.stream), "deconvolution submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_deconv_submit(static_cast<dfx_deconv_t *>(h), p[0], p[1], s), "deconvolution submit");
   }
   const char *name() override { return "deconvolution"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_deconv_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    unsigned long long wei_seen = 0;
-  };
   memory *src_, *wei_, *bia_, *dst_;
   std::vector<float> scales_;
-  dfx_deconv_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- dilated conv (dfx_dilconv_*).  Checks are op_grouped_conv's; the weights are a plain oihw {oc, ic, kh, kw} tensor and
-// dst's dims give the output size.  Weight hashing and batch sharding are op_depthwise_conv's. ----
-class op_dilated_conv : public op {
+// dst's dims give the output size.  Weight hashing and batch sharding are op_base's. ----
+class op_dilated_conv : public op_base {
 public:
   op_dilated_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
                 std::array<int, 2> stride, std::array<int, 2> dilation, std::array<int, 2> padding, std::unique_ptr<memory> &dst, bool relu,
                 const std::vector<float> &scales, round_mode rm)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0),
-        packed_versions_(0) {
+      : op_base(destroy_as<dfx_dilconv_t, dfx_dilconv_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !dst_) error_and_exit("Init DilatedConv op failed! (null tensor)");
     if (src_->data_type() != memory::dtype::u8 || wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc ||
@@ -1882,151 +1226,44 @@ public:
     d.dst_dt = to_dfx_dtype(dst_->data_type());
     d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.relu = relu;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)scales_.size();
     d.force_path = -1;
-    src_img_ = (size_t)d.ih * d.iw * d.ic;
-    dst_img_ = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)d.ih * d.iw * d.ic;
+    const size_t dst_img = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    borrows(wei_); borrows(bia_);
+    build(d.bs, [&](int n) -> void * {
       dfx_dilconv_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_dilconv_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init DilatedConv op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_dilconv_create(&d, &h_) != DFX_OK) error_and_exit("Init DilatedConv op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_dilated_conv() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_dilconv_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_dilconv_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_dilconv_create, ds, "Init DilatedConv op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
+  void pack(void *h) override {
+    const void *bia = bia_ ? bia_->host_data() : nullptr;
+    check_dfx(dfx_dilconv_set_weights(static_cast<dfx_dilconv_t *>(h), (const int8_t *)wei_->host_data(), bia, scales_.data()), "dilated_conv set_weights");
   }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    return v | 1ull;
-  }
-  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const unsigned long long v = weights_hash();
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        check_dfx(dfx_dilconv_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "dilated_conv set_weights");
-        sh.wei_seen = v;
-      }
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_dilconv_submit(sh.h, sh.src, sh.dst, sh.stream), "dilated_conv submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_dilconv_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "dilated_conv set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_dilconv_submit(h_, in, o, st_.stream), "dilated_conv submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_dilconv_submit(static_cast<dfx_dilconv_t *>(h), p[0], p[1], s), "dilated_conv submit");
   }
   const char *name() override { return "dilated_conv"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_dilconv_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    unsigned long long wei_seen = 0;
-  };
   memory *src_, *wei_, *bia_, *dst_;
   std::vector<float> scales_;
-  dfx_dilconv_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- fully-connected layer (dfx_fc_*): dst[n][o] = requant(sum over c, y, x of src[n][y][x][c] * wei[o][c][y][x]).  Checks
 // are op_grouped_conv's; the weights are a plain oihw {oc, c, h, w} tensor over the whole source image (a flattened-CHW
-// classifier), dst is {bs, oc, 1, 1}.  Weight hashing and batch sharding are op_depthwise_conv's. ----
-class op_inner_product : public op {
+// classifier), dst is {bs, oc, 1, 1}.  Weight hashing and batch sharding are op_base's. ----
+class op_inner_product : public op_base {
 public:
   op_inner_product(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
                    std::unique_ptr<memory> &dst, bool relu, const std::vector<float> &scales, round_mode rm)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0),
-        packed_versions_(0) {
+      : op_base(destroy_as<dfx_fc_t, dfx_fc_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !dst_) error_and_exit("Init InnerProduct op failed! (null tensor)");
     if (src_->data_type() != memory::dtype::u8 || wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc ||
@@ -2043,149 +1280,43 @@ public:
     d.dst_dt = to_dfx_dtype(dst_->data_type());
     d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.relu = relu;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)scales_.size();
     d.force_path = -1;
-    src_img_ = (size_t)d.ih * d.iw * d.ic;
-    dst_img_ = (size_t)d.oc * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)d.ih * d.iw * d.ic;
+    const size_t dst_img = (size_t)d.oc * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    borrows(wei_); borrows(bia_);
+    build(d.bs, [&](int n) -> void * {
       dfx_fc_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_fc_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init InnerProduct op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_fc_create(&d, &h_) != DFX_OK) error_and_exit("Init InnerProduct op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_inner_product() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_fc_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_fc_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_fc_create, ds, "Init InnerProduct op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
+  void pack(void *h) override {
+    const void *bia = bia_ ? bia_->host_data() : nullptr;
+    check_dfx(dfx_fc_set_weights(static_cast<dfx_fc_t *>(h), (const int8_t *)wei_->host_data(), bia, scales_.data()), "inner_product set_weights");
   }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    return v | 1ull;
-  }
-  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const unsigned long long v = weights_hash();
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        check_dfx(dfx_fc_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "inner_product set_weights");
-        sh.wei_seen = v;
-      }
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_fc_submit(sh.h, sh.src, sh.dst, sh.stream), "inner_product submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_fc_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "inner_product set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_fc_submit(h_, in, o, st_.stream), "inner_product submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_fc_submit(static_cast<dfx_fc_t *>(h), p[0], p[1], s), "inner_product submit");
   }
   const char *name() override { return "inner_product"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_fc_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    unsigned long long wei_seen = 0;
-  };
   memory *src_, *wei_, *bia_, *dst_;
   std::vector<float> scales_;
-  dfx_fc_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- activation resize (dfx_resize_*), optionally with a lateral tensor added in the same launch.  No weights: nothing to
-// hash or pack.  Batch sharding is op_depthwise_conv's; the lateral is sharded like dst, whose dims it has. ----
-class op_resize : public op {
+// hash or pack.  Batch sharding is op_base's; the lateral is sharded like dst, whose dims it has. ----
+class op_resize : public op_base {
 public:
   op_resize(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> *lateral, std::unique_ptr<memory> &dst, resize_algo algo,
             resize_coord coord, bool post_relu)
-      : src_(src.get()), lat_(lateral ? lateral->get() : nullptr), dst_(dst.get()), h_(nullptr) {
+      : op_base(destroy_as<dfx_resize_t, dfx_resize_destroy>), src_(src.get()), lat_(lateral ? lateral->get() : nullptr), dst_(dst.get()) {
     using fmt = memory::format;
     if (!src_ || !dst_ || (lateral && !lat_)) error_and_exit("Init Resize op failed! (null tensor)");
     if (src_->dim_format() != fmt::nhwc || dst_->dim_format() != fmt::nhwc || src_->data_type() != dst_->data_type())
@@ -2206,125 +1337,37 @@ public:
     d.add = lat_ ? 1 : 0;
     d.post_relu = post_relu ? 1 : 0;
     d.force_path = -1;
-    src_img_ = (size_t)d.ih * d.iw * d.c * dtype_size(src_->data_type());
-    dst_img_ = (size_t)d.oh * d.ow * d.c * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)d.ih * d.iw * d.c * dtype_size(src_->data_type());
+    const size_t dst_img = (size_t)d.oh * d.ow * d.c * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    reads(lat_, dst_img);  // (absent for resize(); it may be dst)
+    writes(dst_, dst_img);
+    build(d.bs, [&](int n) -> void * {
       dfx_resize_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_resize_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init Resize op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      if (lat_) check_dfx(dfx_mem_alloc_device(&sh.lat, (size_t)r.n * dst_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_resize_create(&d, &h_) != DFX_OK) error_and_exit("Init Resize op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_resize() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_resize_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.lat);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_resize_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_resize_create, ds, "Init Resize op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
-  }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const char *hs = static_cast<const char *>(src_->host_data());
-    const char *hl = lat_ ? static_cast<const char *>(lat_->host_data()) : nullptr;
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      if (lat_) check_dfx(dfx_memcpy_h2d(sh.lat, hl + sh.r.n0 * dst_img_, sh.r.n * dst_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_resize_submit(sh.h, sh.src, sh.lat, sh.dst, sh.stream), "resize submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {
-    const void *in = st_.sync_in(*src_, sync_host);
-    const void *lat = lat_ ? st_.sync_in(*lat_, sync_host) : nullptr;  // (the lateral may be dst: uploaded, then overwritten)
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_resize_submit(h_, in, lat, o, st_.stream), "resize submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_resize_submit(static_cast<dfx_resize_t *>(h), p[0], p[1], p[2], s), "resize submit");
   }
   const char *name() override { return lat_ ? "resize_add" : "resize"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_resize_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *lat = nullptr, *dst = nullptr;
-  };
   memory *src_, *lat_, *dst_;
-  dfx_resize_t *h_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- scaled element-wise sum (dfx_wsum_*): 1 to 8 nhwc tensors of mixed dtypes, scales, bias, ReLU, table.  The scales,
 // the bias and the table are copied at construction: nothing to hash.  dst may be one of the srcs; every src is registered
 // as a read and dst as a write (op_state), so an in-place op waits for earlier readers of that tensor on other streams.
-// Batch sharding is op_resize's: every tensor is batch-major. ----
-class op_scaled_sum : public op {
+// Batch sharding is op_base's: every tensor is batch-major. ----
+class op_scaled_sum : public op_base {
 public:
   op_scaled_sum(const std::vector<std::unique_ptr<memory>> &srcs, const std::vector<std::vector<float>> &scales, std::unique_ptr<memory> &dst,
                 const std::vector<float> &bias, bool post_relu, const std::vector<u8> &table, memory::dtype table_in, round_mode rm)
-      : dst_(dst.get()), h_(nullptr) {
+      : op_base(destroy_as<dfx_wsum_t, dfx_wsum_destroy>), dst_(dst.get()) {
     using fmt = memory::format;
     if (!dst_ || srcs.empty() || srcs.size() > DFX_WSUM_MAX_INPUTS) error_and_exit("Init ScaledSum op failed! (1 to 8 sources and a dst)");
     if (scales.size() != srcs.size()) error_and_exit("Init ScaledSum op failed! (one vector of scales per source)");
@@ -2345,142 +1388,47 @@ public:
     }
     d.n_bias = (int)bias.size();
     d.dst_dt = to_dfx_dtype(dst_->data_type());
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.post_relu = post_relu ? 1 : 0;
     d.lut_in_dt = to_dfx_dtype(table_in);
     d.force_path = -1;
     const size_t img = (size_t)d.h * d.w * d.c;
-    for (memory *m : srcs_) src_img_.push_back(img * dtype_size(m->data_type()));
-    dst_img_ = img * dtype_size(dst_->data_type());
+    for (memory *m : srcs_) reads(m, img * dtype_size(m->data_type()));  // (a source may be dst)
+    writes(dst_, img * dtype_size(dst_->data_type()));
     std::vector<const float *> sp;
     for (const std::vector<float> &s : scales) sp.push_back(s.data());
     const float *bp = bias.empty() ? nullptr : bias.data();
     const u8 *tp = table.empty() ? nullptr : table.data();
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    build(d.bs, [&](int n) -> void * {
       dfx_wsum_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_wsum_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init ScaledSum op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_wsum_set_params(sh.h, sp.data(), bp, tp), "wsum set_params");
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      for (size_t i = 0; i < srcs_.size(); ++i) {
-        void *p = nullptr;
-        check_dfx(dfx_mem_alloc_device(&p, (size_t)r.n * src_img_[i]), "device alloc");
-        sh.src.push_back(p);
-      }
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_wsum_create(&d, &h_) != DFX_OK) error_and_exit("Init ScaledSum op failed! (%s)", dfx_last_error());
-    check_dfx(dfx_wsum_set_params(h_, sp.data(), bp, tp), "wsum set_params");
-    st_.ensure_stream();
-  }
-  ~op_scaled_sum() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_wsum_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      for (void *p : sh.src) dfx_mem_free_device(p);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_wsum_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      dfx_wsum_t *h = static_cast<dfx_wsum_t *>(create_or_exit(dfx_wsum_create, ds, "Init ScaledSum op failed! (%s)"));
+      check_dfx(dfx_wsum_set_params(h, sp.data(), bp, tp), "wsum set_params");
+      return h;
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
-  }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard; every source is uploaded before dst's host bytes change)
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      for (size_t i = 0; i < srcs_.size(); ++i) {
-        const char *hs = static_cast<const char *>(srcs_[i]->host_data());
-        check_dfx(dfx_memcpy_h2d(sh.src[i], hs + sh.r.n0 * src_img_[i], sh.r.n * src_img_[i], sh.stream), "H2D copy");
-      }
-      check_dfx(dfx_wsum_submit(sh.h, (const void *const *)sh.src.data(), sh.dst, sh.stream), "wsum submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {
-    std::vector<const void *> p;
-    for (memory *m : srcs_) p.push_back(st_.sync_in(*m, sync_host));  // (a source may be dst: uploaded, then overwritten)
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_wsum_submit(h_, p.data(), o, st_.stream), "wsum submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_wsum_submit(static_cast<dfx_wsum_t *>(h), p, p[n_reads()], s), "wsum submit");
   }
   const char *name() override { return "scaled_sum"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_wsum_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    std::vector<void *> src;
-    void *dst = nullptr;
-  };
   std::vector<memory *> srcs_;
   memory *dst_;
-  dfx_wsum_t *h_;
-  std::vector<size_t> src_img_;  // bytes per image
-  size_t dst_img_;
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- net head (dfx_head_*): channel top-k / argmax and table softmax over the rows of an nhwc tensor (rows = bs * h * w,
 // src_ld = C, c_valid <= C).  TOPK writes idx {bs, k, h, w} and, if given, val of src's dtype; SOFTMAX writes dst
 // {bs, C', h, w} with C' >= c_valid; the kernel leaves channels c_valid .. C'-1 of the device copy alone, so after the copy
 // back the host's pad channels are undefined (deepfusion.h says so).  The table is copied at construction: nothing to hash.  src is registered as a read,
-// idx / dst and val as writes (op_state).  Batch sharding is op_scaled_sum's: every tensor is batch-major. ----
-class op_head : public op {
+// idx / dst and val as writes (op_state).  Batch sharding is op_base's: every tensor is batch-major. ----
+class op_head : public op_base {
 public:
   op_head(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &out, memory *val, int mode, int k, int c_valid,
           const std::array<uint32_t, 256> *table, float out_scale)
-      : src_(src.get()), out_(out.get()), val_(val), h_(nullptr) {
+      : op_base(destroy_as<dfx_head_t, dfx_head_destroy>), src_(src.get()), out_(out.get()), val_(val) {
     using fmt = memory::format;
     if (!src_ || !out_) error_and_exit("Init Head op failed! (null tensor)");
     if (src_->dim_format() != fmt::nhwc || out_->dim_format() != fmt::nhwc || (val_ && val_->dim_format() != fmt::nhwc))
@@ -2506,130 +1454,40 @@ public:
     }
     d.out_scale = out_scale;
     d.force_path = -1;
-    src_img_ = (size_t)px * i[1] * dtype_size(src_->data_type());
-    out_img_ = (size_t)px * o[1] * dtype_size(out_->data_type());
-    val_img_ = val_ ? (size_t)px * o[1] * dtype_size(val_->data_type()) : 0;
-    for (const detail::shard_range &r : detail::plan_shards(i[0])) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)px * i[1] * dtype_size(src_->data_type());
+    const size_t out_img = (size_t)px * o[1] * dtype_size(out_->data_type());
+    const size_t val_img = val_ ? (size_t)px * o[1] * dtype_size(val_->data_type()) : 0;
+    reads(src_, src_img);
+    writes(out_, out_img);
+    writes(val_, val_img);  // (absent unless top_k() was given one)
+    build(i[0], [&](int n) -> void * {
       dfx_head_desc ds = d;
-      ds.rows = (long long)r.n * px;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_head_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init Head op failed! (%s)", dfx_last_error());
-      if (table && dfx_head_set_table(sh.h, table->data()) != DFX_OK) error_and_exit("Init Head op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.out, (size_t)r.n * out_img_), "device alloc");
-      if (val_) check_dfx(dfx_mem_alloc_device(&sh.val, (size_t)r.n * val_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_head_create(&d, &h_) != DFX_OK) error_and_exit("Init Head op failed! (%s)", dfx_last_error());
-    if (table && dfx_head_set_table(h_, table->data()) != DFX_OK) error_and_exit("Init Head op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_head() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_head_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.out);
-      dfx_mem_free_device(sh.val);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*out_);
-    dfx_head_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*out_);
-    if (val_) st_.fetch_out(*val_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*out_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*out_);
-    }
+      ds.rows = (long long)n * px;
+      dfx_head_t *h = static_cast<dfx_head_t *>(create_or_exit(dfx_head_create, ds, "Init Head op failed! (%s)"));
+      if (table && dfx_head_set_table(h, table->data()) != DFX_OK) error_and_exit("Init Head op failed! (%s)", dfx_last_error());
+      return h;
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
-  }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *ho = static_cast<char *>(const_cast<void *>(out_->host_data()));
-    char *hv = val_ ? static_cast<char *>(const_cast<void *>(val_->host_data())) : nullptr;
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_head_submit(sh.h, sh.src, sh.out, sh.val, sh.stream), "head submit");
-      check_dfx(dfx_memcpy_d2h(ho + sh.r.n0 * out_img_, sh.out, sh.r.n * out_img_, sh.stream), "D2H copy");
-      if (val_) check_dfx(dfx_memcpy_d2h(hv + sh.r.n0 * val_img_, sh.val, sh.r.n * val_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*out_);
-    if (val_) detail::op_state::host_is_current(*val_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*out_);
-    void *v = val_ ? st_.device_out(*val_) : nullptr;
-    st_.profile_begin();
-    check_dfx(dfx_head_submit(h_, in, o, v, st_.stream), "head submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_head_submit(static_cast<dfx_head_t *>(h), p[0], p[1], p[2], s), "head submit");
   }
   const char *name() override { return "head"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_head_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *out = nullptr, *val = nullptr;
-  };
   memory *src_, *out_, *val_;
-  dfx_head_t *h_;
-  size_t src_img_, out_img_, val_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- int8 layer norm / RMS norm (dfx_lnorm_*) over the rows of an nhwc tensor (rows = bs * h * w, src_ld = C, c_valid <= C);
 // dst {bs, C', h, w} with C' >= c_valid, whose pad channels the kernel leaves alone (undefined on the host afterwards, as
 // op_head's softmax).  gamma / beta / shifts are copied at construction.  src is registered as a read, dst as a write
-// (op_state).  Batch sharding is op_head's: both tensors are batch-major. ----
-class op_layer_norm : public op {
+// (op_state).  Batch sharding is op_base's: both tensors are batch-major. ----
+class op_layer_norm : public op_base {
 public:
   op_layer_norm(const std::unique_ptr<memory> &src, const std::vector<float> &gamma, const std::vector<float> &beta,
                 std::unique_ptr<memory> &dst, float eps, norm_mode mode, const std::vector<u8> &shifts, int c_valid)
-      : src_(src.get()), dst_(dst.get()), h_(nullptr) {
+      : op_base(destroy_as<dfx_lnorm_t, dfx_lnorm_destroy>), src_(src.get()), dst_(dst.get()) {
     using fmt = memory::format;
     if (!src_ || !dst_) error_and_exit("Init LayerNorm op failed! (null tensor)");
     if (src_ == dst_) error_and_exit("Init LayerNorm op failed! (in place is not built)");
@@ -2653,123 +1511,39 @@ public:
     if (!shifts.empty() && (long long)shifts.size() != d.c) error_and_exit("Init LayerNorm op failed! (shifts must be empty or have c_valid values)");
     const float *b = beta.empty() ? nullptr : beta.data();
     const u8 *s = shifts.empty() ? nullptr : shifts.data();
-    src_img_ = (size_t)px * i[1] * dtype_size(src_->data_type());
-    dst_img_ = (size_t)px * o[1] * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(i[0])) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)px * i[1] * dtype_size(src_->data_type());
+    const size_t dst_img = (size_t)px * o[1] * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    build(i[0], [&](int n) -> void * {
       dfx_lnorm_desc ds = d;
-      ds.rows = (long long)r.n * px;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_lnorm_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init LayerNorm op failed! (%s)", dfx_last_error());
-      if (dfx_lnorm_set_params(sh.h, gamma.data(), b, s) != DFX_OK) error_and_exit("Init LayerNorm op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_lnorm_create(&d, &h_) != DFX_OK) error_and_exit("Init LayerNorm op failed! (%s)", dfx_last_error());
-    if (dfx_lnorm_set_params(h_, gamma.data(), b, s) != DFX_OK) error_and_exit("Init LayerNorm op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_layer_norm() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_lnorm_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_lnorm_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.rows = (long long)n * px;
+      dfx_lnorm_t *h = static_cast<dfx_lnorm_t *>(create_or_exit(dfx_lnorm_create, ds, "Init LayerNorm op failed! (%s)"));
+      if (dfx_lnorm_set_params(h, gamma.data(), b, s) != DFX_OK) error_and_exit("Init LayerNorm op failed! (%s)", dfx_last_error());
+      return h;
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
-  }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *ho = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_lnorm_submit(sh.h, sh.src, sh.dst, sh.stream), "lnorm submit");
-      check_dfx(dfx_memcpy_d2h(ho + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_lnorm_submit(h_, in, o, st_.stream), "lnorm submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_lnorm_submit(static_cast<dfx_lnorm_t *>(h), p[0], p[1], s), "lnorm submit");
   }
   const char *name() override { return "layer_norm"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_lnorm_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-  };
   memory *src_, *dst_;
-  dfx_lnorm_t *h_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- int8 token linear layer (dfx_linear_*) over the rows of an nhwc tensor (rows = bs * h * w, src_ld = C, k <= C); dst
 // {bs, C', h, w} with C' >= n, whose pad channels the kernel leaves alone (undefined on the host afterwards, as op_layer_norm's).
-// The weights are a plain oihw {n, k, 1, 1} tensor, hashed and re-packed as op_inner_product's; the table is copied at
+// The weights are a plain oihw {n, k, 1, 1} tensor, hashed and re-packed by op_base; the table is copied at
 // construction.  src is registered as a read, dst as a write (op_state).  One device: the op is not sharded. ----
-class op_linear : public op {
+class op_linear : public op_base {
 public:
   op_linear(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
             std::unique_ptr<memory> &dst, bool relu, const std::vector<float> &scales, round_mode rm, int k_valid, const std::vector<u8> &table,
             memory::dtype table_in)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales), h_(nullptr), packed_hash_(0), packed_versions_(0) {
+      : op_base(destroy_as<dfx_linear_t, dfx_linear_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !dst_) error_and_exit("Init Linear op failed! (null tensor)");
     if (src_ == dst_) error_and_exit("Init Linear op failed! (in place is not built)");
@@ -2791,68 +1565,36 @@ public:
     d.dst_dt = to_dfx_dtype(dst_->data_type());
     d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.relu = relu;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)scales_.size();
     d.lut_in_dt = table.empty() ? DFX_UNDEF : to_dfx_dtype(table_in);
     d.force_path = -1;
     d.src_ld = i[1];
     d.dst_ld = o[1];
-    if (dfx_linear_create(&d, &h_) != DFX_OK) error_and_exit("Init Linear op failed! (%s)", dfx_last_error());
-    if (!table.empty() && dfx_linear_set_table(h_, table.data()) != DFX_OK) error_and_exit("Init Linear op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_linear() override {
-    st_.retire(*dst_);
-    dfx_linear_destroy(h_);
-  }
-
-  void submit() override {
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override { run(false); }
-  void wait() override {
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
+    reads(src_);
+    writes(dst_);
+    borrows(wei_); borrows(bia_);
+    build(0, [&](int) -> void * {
+      dfx_linear_t *h = static_cast<dfx_linear_t *>(create_or_exit(dfx_linear_create, d, "Init Linear op failed! (%s)"));
+      if (!table.empty() && dfx_linear_set_table(h, table.data()) != DFX_OK) error_and_exit("Init Linear op failed! (%s)", dfx_last_error());
+      return h;
+    });
   }
 
 protected:
-  void infer() override { run(true); }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    return v | 1ull;
+  void pack(void *h) override {
+    check_dfx(dfx_linear_set_weights(static_cast<dfx_linear_t *>(h), (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr,
+                                     scales_.data()),
+              "linear set_weights");
   }
-  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0); }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_linear_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data()),
-                  "linear set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_linear_submit(h_, in, o, st_.stream), "linear submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_linear_submit(static_cast<dfx_linear_t *>(h), p[0], p[1], s), "linear submit");
   }
   const char *name() override { return "linear"; }
 
 private:
   memory *src_, *wei_, *bia_, *dst_;
   std::vector<float> scales_;
-  dfx_linear_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  detail::op_state st_;
 };
 
 // ---- image-wide top-K with peak filter (dfx_select_*): the k best elements of every image of an nhwc score tensor,
@@ -2860,11 +1602,11 @@ private:
 // behind it.  src and the gather sources are registered as reads, idx, count, val and the gather destinations as writes
 // (op_state).  One handle on one device: DEEPFUSION_DEVICES does not shard this op (its results are per image, but a
 // detector's batch is small). ----
-class op_select : public op {
+class op_select : public op_base {
 public:
   op_select(const std::unique_ptr<memory> &src, std::unique_ptr<memory> &idx, memory *val, std::unique_ptr<memory> &count, int k,
             bool peak3, int min_val, int c_valid, const std::vector<memory *> &gsrc, const std::vector<memory *> &gdst)
-      : src_(src.get()), idx_(idx.get()), val_(val), count_(count.get()), gsrc_(gsrc), gdst_(gdst), h_(nullptr) {
+      : op_base(destroy_as<dfx_select_t, dfx_select_destroy>), src_(src.get()), idx_(idx.get()), val_(val), count_(count.get()), gsrc_(gsrc), gdst_(gdst) {
     using fmt = memory::format;
     using dt = memory::dtype;
     if (!src_ || !idx_ || !count_) error_and_exit("Init Select op failed! (null tensor)");
@@ -2897,64 +1639,43 @@ public:
       d.row_bytes[g] = d.pixel_stride_bytes[g] = (int)(sd[1] * dtype_size(s->data_type()));
     }
     d.force_path = -1;
-    if (dfx_select_create(&d, &h_) != DFX_OK) error_and_exit("Init Select op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_select() override {
-    st_.retire(*idx_);
-    dfx_select_destroy(h_);
-  }
-
-  void submit() override {
-    run(true);
-    st_.fetch_out(*idx_);
-    st_.fetch_out(*count_);
-    if (val_) st_.fetch_out(*val_);
-    for (memory *t : gdst_) st_.fetch_out(*t);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*idx_);
-  }
-  void submit_async() override { run(false); }
-  void wait() override {
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*idx_);
+    reads(src_);
+    for (memory *m : gsrc_) reads(m);
+    writes(idx_);
+    writes(count_);
+    writes(val_);  // (absent unless given)
+    for (memory *m : gdst_) writes(m);
+    build(0, [&](int) -> void * { return create_or_exit(dfx_select_create, d, "Init Select op failed! (%s)"); });
   }
 
 protected:
-  void infer() override { run(true); }
-  void run(bool sync_host) {
-    const void *in = st_.sync_in(*src_, sync_host);
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
     const void *gs[DFX_SELECT_MAX_GATHER] = {nullptr, nullptr, nullptr, nullptr};
     void *gd[DFX_SELECT_MAX_GATHER] = {nullptr, nullptr, nullptr, nullptr};
-    for (size_t g = 0; g < gsrc_.size(); ++g) gs[g] = st_.sync_in(*gsrc_[g], sync_host);
-    void *o = st_.device_out(*idx_);
-    void *c = st_.device_out(*count_);
-    void *v = val_ ? st_.device_out(*val_) : nullptr;
-    for (size_t g = 0; g < gdst_.size(); ++g) gd[g] = st_.device_out(*gdst_[g]);
-    st_.profile_begin();
-    check_dfx(dfx_select_submit(h_, in, o, v, c, gs, gd, st_.stream), "select submit");
-    st_.profile_end(name());
+    void *const *w = p + n_reads();  // idx, count, val, the gather destinations
+    for (size_t g = 0; g < gsrc_.size(); ++g) {
+      gs[g] = p[1 + g];
+      gd[g] = w[3 + g];
+    }
+    check_dfx(dfx_select_submit(static_cast<dfx_select_t *>(h), p[0], w[0], w[2], w[1], gs, gd, s), "select submit");
   }
   const char *name() override { return "select"; }
 
 private:
   memory *src_, *idx_, *val_, *count_;
   std::vector<memory *> gsrc_, gdst_;
-  dfx_select_t *h_;
-  detail::op_state st_;
 };
 
 // ---- box decode + greedy NMS (dfx_nms_*): what a detector does behind select_top_k().  boxes (or idx, deltas and anchors),
 // the two tables and count_in are registered as reads, keep, count and boxes_out as writes (op_state).  The tables are two
 // small tensors of the op's own.  One handle on one device: DEEPFUSION_DEVICES does not shard this op, as it does not
 // shard select_top_k(). ----
-class op_nms : public op {
+class op_nms : public op_base {
 public:
   op_nms(memory *boxes, memory *idx, memory *deltas, memory *anchors, const std::array<float, 256> *tab_c, const std::array<float, 256> *tab_s,
          memory *count_in, memory *keep, memory *count, memory *boxes_out, float iou_thr, int classes, bool per_class, int apx, float clip_w,
          float clip_h)
-      : boxes_(boxes), idx_(idx), deltas_(deltas), anchors_(anchors), count_in_(count_in), keep_(keep), count_(count), boxes_out_(boxes_out),
-        h_(nullptr) {
+      : op_base(destroy_as<dfx_nms_t, dfx_nms_destroy>), boxes_(boxes), idx_(idx), deltas_(deltas), anchors_(anchors), count_in_(count_in), keep_(keep), count_(count), boxes_out_(boxes_out) {
     using fmt = memory::format;
     using dt = memory::dtype;
     const bool decode = boxes_ == nullptr;
@@ -3002,64 +1723,43 @@ public:
     d.classes = classes; d.anchors_per_pixel = apx; d.idx_ld = n;
     d.iou_thr = iou_thr; d.clip_w = clip_w; d.clip_h = clip_h;
     d.force_path = -1;
-    if (dfx_nms_create(&d, &h_) != DFX_OK) error_and_exit("Init Nms op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
+    reads(boxes_);
+    reads(idx_);
+    reads(deltas_);
+    reads(anchors_);
+    reads(tab_c_.get(), 0, true);  // (the op's own tensors: uploaded once)
+    reads(tab_s_.get(), 0, true);
+    reads(count_in_);
+    writes(keep_);
+    writes(count_);
+    writes(boxes_out_);
+    build(0, [&](int) -> void * { return create_or_exit(dfx_nms_create, d, "Init Nms op failed! (%s)"); });
   }
-  ~op_nms() override {
-    st_.retire(*keep_);
-    dfx_nms_destroy(h_);
-  }
-
-  void submit() override {
-    run(true);
-    st_.fetch_out(*keep_);
-    st_.fetch_out(*count_);
-    if (boxes_out_) st_.fetch_out(*boxes_out_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*keep_);
-  }
-  void submit_async() override { run(false); }
-  void wait() override {
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*keep_);
-  }
+  ~op_nms() override { teardown(); }  // (before tab_c_ and tab_s_ go: a launch may still read them)
 
 protected:
-  void infer() override { run(true); }
-  void run(bool sync_host) {
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
     dfx_nms_io io;
     memset(&io, 0, sizeof(io));
-    if (boxes_) io.boxes = st_.sync_in(*boxes_, sync_host);
-    if (idx_) io.idx = st_.sync_in(*idx_, sync_host);
-    if (deltas_) io.deltas = st_.sync_in(*deltas_, sync_host);
-    if (anchors_) io.anchors = st_.sync_in(*anchors_, sync_host);
-    if (tab_c_) io.tab_c = st_.sync_in(*tab_c_, false);
-    if (tab_s_) io.tab_s = st_.sync_in(*tab_s_, false);
-    if (count_in_) io.count_in = st_.sync_in(*count_in_, sync_host);
-    io.keep = st_.device_out(*keep_);
-    io.count = st_.device_out(*count_);
-    if (boxes_out_) io.boxes_out = st_.device_out(*boxes_out_);
-    st_.profile_begin();
-    check_dfx(dfx_nms_submit(h_, &io, st_.stream), "nms submit");
-    st_.profile_end(name());
+    io.boxes = p[0]; io.idx = p[1]; io.deltas = p[2]; io.anchors = p[3]; io.tab_c = p[4]; io.tab_s = p[5]; io.count_in = p[6];
+    io.keep = p[7]; io.count = p[8]; io.boxes_out = p[9];
+    check_dfx(dfx_nms_submit(static_cast<dfx_nms_t *>(h), &io, s), "nms submit");
   }
   const char *name() override { return "nms"; }
 
 private:
   memory *boxes_, *idx_, *deltas_, *anchors_, *count_in_, *keep_, *count_, *boxes_out_;
   std::unique_ptr<memory> tab_c_, tab_s_;
-  dfx_nms_t *h_;
-  detail::op_state st_;
 };
 
 // ---- RoIAlign (dfx_roialign_*): what a two-stage detector does behind box_nms().  The levels, boxes and count / batch_idx
 // are registered as reads, dst as a write (op_state).  One handle on one device: DEEPFUSION_DEVICES does not shard this op,
 // as it does not shard select_top_k(). ----
-class op_roialign : public op {
+class op_roialign : public op_base {
 public:
   op_roialign(const std::vector<memory *> &levels, const std::vector<float> &scales, const std::vector<float> &thr, memory *boxes, memory *count,
               memory *batch_idx, memory *dst, int sampling_ratio, bool aligned, int c_valid)
-      : levels_(levels), boxes_(boxes), count_(count), batch_idx_(batch_idx), dst_(dst), h_(nullptr) {
+      : op_base(destroy_as<dfx_roialign_t, dfx_roialign_destroy>), levels_(levels), boxes_(boxes), count_(count), batch_idx_(batch_idx), dst_(dst) {
     using fmt = memory::format;
     using dt = memory::dtype;
     if (levels_.empty() || levels_.size() > (size_t)DFX_ROIALIGN_MAX_LEVELS || !levels_[0] || !boxes_ || !dst_)
@@ -3099,47 +1799,28 @@ public:
     d.ph = o[2]; d.pw = o[3]; d.dst_ld = o[1];
     d.sampling_ratio = sampling_ratio; d.aligned = aligned ? 1 : 0;
     d.force_path = -1;
-    if (dfx_roialign_create(&d, &h_) != DFX_OK) error_and_exit("Init RoiAlign op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_roialign() override {
-    st_.retire(*dst_);
-    dfx_roialign_destroy(h_);
-  }
-
-  void submit() override {
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override { run(false); }
-  void wait() override {
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
+    for (memory *m : levels_) reads(m);
+    reads(boxes_);
+    reads(count_);      // (absent in the list form, optional in the batched one)
+    reads(batch_idx_);  // (the list form's)
+    writes(dst_);
+    build(0, [&](int) -> void * { return create_or_exit(dfx_roialign_create, d, "Init RoiAlign op failed! (%s)"); });
   }
 
 protected:
-  void infer() override { run(true); }
-  void run(bool sync_host) {
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
     dfx_roialign_io io;
     memset(&io, 0, sizeof(io));
-    for (size_t l = 0; l < levels_.size(); ++l) io.src[l] = st_.sync_in(*levels_[l], sync_host);
-    io.boxes = st_.sync_in(*boxes_, sync_host);
-    if (count_) io.count = st_.sync_in(*count_, sync_host);
-    if (batch_idx_) io.batch_idx = st_.sync_in(*batch_idx_, sync_host);
-    io.dst = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_roialign_submit(h_, &io, st_.stream), "roialign submit");
-    st_.profile_end(name());
+    const size_t nl = levels_.size();
+    for (size_t l = 0; l < nl; ++l) io.src[l] = p[l];
+    io.boxes = p[nl]; io.count = p[nl + 1]; io.batch_idx = p[nl + 2]; io.dst = p[nl + 3];
+    check_dfx(dfx_roialign_submit(static_cast<dfx_roialign_t *>(h), &io, s), "roialign submit");
   }
   const char *name() override { return "roialign"; }
 
 private:
   std::vector<memory *> levels_;
   memory *boxes_, *count_, *batch_idx_, *dst_;
-  dfx_roialign_t *h_;
-  detail::op_state st_;
 };
 
 // ---- batched int8 matrix product (dfx_bmm_*): C[g] = requant(A[g] . B[g](^T)) over matrices that lie in three tensors at the
@@ -3158,84 +1839,65 @@ static dfx_logit_bias_desc logit_bias_desc(const logit_bias &bias, long long row
   return b;
 }
 
-class op_matmul : public op {
+class op_matmul : public op_base {
 public:
   op_matmul(memory *a, memory *b, memory *c, const matmul_shape &sh, const std::vector<float> &scales, bool relu, round_mode rm,
             const logit_bias *bias = nullptr)
-      : a_(a), b_(b), c_(c), h_(nullptr) {
+      : op_base(destroy_as<dfx_bmm_t, dfx_bmm_destroy>), a_(a), b_(b), c_(c) {
     if (!a_ || !b_ || !c_) error_and_exit("Init MatMul op failed! (null tensor)");
     dfx_bmm_desc d;
     memset(&d, 0, sizeof(d));
     d.batch0 = sh.batch0; d.batch1 = sh.batch1; d.m = sh.m; d.n = sh.n; d.k = sh.k; d.trans_b = sh.trans_b ? 1 : 0;
     d.a_dt = to_dfx_dtype(a_->data_type()); d.b_dt = to_dfx_dtype(b_->data_type()); d.dst_dt = to_dfx_dtype(c_->data_type());
     d.relu = relu ? 1 : 0;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)scales.size();
     d.force_path = -1;
     d.a_s0 = sh.a_s0; d.a_s1 = sh.a_s1; d.lda = sh.lda;
     d.b_s0 = sh.b_s0; d.b_s1 = sh.b_s1; d.ldb = sh.ldb;
     d.c_s0 = sh.c_s0; d.c_s1 = sh.c_s1; d.ldc = sh.ldc;
     if (scales.empty()) error_and_exit("Init MatMul op failed! (scales must hold 1 or n floats)");
-    if (dfx_bmm_create(&d, &h_) != DFX_OK) error_and_exit("Init MatMul op failed! (%s)", dfx_last_error());
-    // every matrix within its tensor: the last row of a and of b up to its valid columns rounded up to 16, which is what
-    // the library may read (the create above has found the sizes positive and the strides non-negative)
-    const long long brows = sh.trans_b ? sh.n : sh.k, bcols = sh.trans_b ? sh.k : sh.n;
-    const long long a_row = std::min<long long>(sh.lda, ((long long)sh.k + 15) / 16 * 16), b_row = std::min<long long>(sh.ldb, (bcols + 15) / 16 * 16);
-    const long long a_end = (sh.batch0 - 1) * sh.a_s0 + (sh.batch1 - 1) * sh.a_s1 + (long long)(sh.m - 1) * sh.lda + a_row;
-    const long long b_end = (sh.batch0 - 1) * sh.b_s0 + (sh.batch1 - 1) * sh.b_s1 + (brows - 1) * sh.ldb + b_row;
-    const long long c_end = (sh.batch0 - 1) * sh.c_s0 + (sh.batch1 - 1) * sh.c_s1 + (long long)(sh.m - 1) * sh.ldc + sh.n;
-    if (a_end > (long long)a_->size() || b_end > (long long)b_->size() || c_end > (long long)c_->size())
-      error_and_exit("Init MatMul op failed! (a matrix reaches beyond its tensor)");
-    if (dfx_bmm_set_scales(h_, scales.data()) != DFX_OK) error_and_exit("Init MatMul op failed! (%s)", dfx_last_error());
-    if (bias) {
-      const dfx_logit_bias_desc bd = logit_bias_desc(*bias, sh.m, sh.n, "MatMul");
-      if (dfx_bmm_set_bias(h_, &bd, bias->table.data()) != DFX_OK) error_and_exit("Init MatMul op failed! (%s)", dfx_last_error());
-    }
-    st_.ensure_stream();
-  }
-  ~op_matmul() override {
-    st_.retire(*c_);
-    dfx_bmm_destroy(h_);
-  }
-
-  void submit() override {
-    run(true);
-    st_.fetch_out(*c_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*c_);
-  }
-  void submit_async() override { run(false); }
-  void wait() override {
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*c_);
+    reads(a_);
+    reads(b_);
+    writes(c_);
+    build(0, [&](int) -> void * {
+      dfx_bmm_t *h = static_cast<dfx_bmm_t *>(create_or_exit(dfx_bmm_create, d, "Init MatMul op failed! (%s)"));
+      // every matrix within its tensor: the last row of a and of b up to its valid columns rounded up to 16, which is what
+      // the library may read (the create above has found the sizes positive and the strides non-negative)
+      const long long brows = sh.trans_b ? sh.n : sh.k, bcols = sh.trans_b ? sh.k : sh.n;
+      const long long a_row = std::min<long long>(sh.lda, ((long long)sh.k + 15) / 16 * 16), b_row = std::min<long long>(sh.ldb, (bcols + 15) / 16 * 16);
+      const long long a_end = (sh.batch0 - 1) * sh.a_s0 + (sh.batch1 - 1) * sh.a_s1 + (long long)(sh.m - 1) * sh.lda + a_row;
+      const long long b_end = (sh.batch0 - 1) * sh.b_s0 + (sh.batch1 - 1) * sh.b_s1 + (brows - 1) * sh.ldb + b_row;
+      const long long c_end = (sh.batch0 - 1) * sh.c_s0 + (sh.batch1 - 1) * sh.c_s1 + (long long)(sh.m - 1) * sh.ldc + sh.n;
+      if (a_end > (long long)a_->size() || b_end > (long long)b_->size() || c_end > (long long)c_->size())
+        error_and_exit("Init MatMul op failed! (a matrix reaches beyond its tensor)");
+      if (dfx_bmm_set_scales(h, scales.data()) != DFX_OK) error_and_exit("Init MatMul op failed! (%s)", dfx_last_error());
+      if (bias) {
+        const dfx_logit_bias_desc bd = logit_bias_desc(*bias, sh.m, sh.n, "MatMul");
+        if (dfx_bmm_set_bias(h, &bd, bias->table.data()) != DFX_OK) error_and_exit("Init MatMul op failed! (%s)", dfx_last_error());
+      }
+      return h;
+    });
   }
 
 protected:
-  void infer() override { run(true); }
-  void run(bool sync_host) {
-    const void *a = st_.sync_in(*a_, sync_host);
-    const void *b = st_.sync_in(*b_, sync_host);
-    void *c = st_.device_out(*c_);
-    st_.profile_begin();
-    check_dfx(dfx_bmm_submit(h_, a, b, c, st_.stream), "bmm submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_bmm_submit(static_cast<dfx_bmm_t *>(h), p[0], p[1], p[2], s), "bmm submit");
   }
   const char *name() override { return "matmul"; }
 
 private:
   memory *a_, *b_, *c_;
-  dfx_bmm_t *h_;
-  detail::op_state st_;
 };
 
 // ---- fused int8 attention (dfx_attn_*): o[g] = requant(softmax(requant(q[g] . k[g]^T)) . v[g]) over matrices that lie in four
 // tensors at the strides of attention_shape.  q, k and v are registered as reads, o as a write (op_state).  One handle on one
 // device, like op_matmul. ----
-class op_attention : public op {
+class op_attention : public op_base {
 public:
   op_attention(memory *q, memory *k, memory *v, const std::array<uint32_t, 256> &table, memory *o, const attention_shape &sh, float logit_scale,
                const std::vector<float> &out_scales, float prob_scale, bool relu, round_mode rm, const logit_bias *bias = nullptr)
-      : q_(q), k_(k), v_(v), o_(o), h_(nullptr) {
+      : op_base(destroy_as<dfx_attn_t, dfx_attn_destroy>), q_(q), k_(k), v_(v), o_(o) {
     if (!q_ || !k_ || !v_ || !o_) error_and_exit("Init Attention op failed! (null tensor)");
     dfx_attn_desc d;
     memset(&d, 0, sizeof(d));
@@ -3243,7 +1905,7 @@ public:
     d.q_dt = to_dfx_dtype(q_->data_type()); d.k_dt = to_dfx_dtype(k_->data_type()); d.v_dt = to_dfx_dtype(v_->data_type());
     d.dst_dt = to_dfx_dtype(o_->data_type());
     d.relu = relu ? 1 : 0;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.nscales = (int)out_scales.size();
     d.force_path = -1;
     d.prob_scale = prob_scale;
@@ -3252,72 +1914,52 @@ public:
     d.v_s0 = sh.v_s0; d.v_s1 = sh.v_s1; d.ldv = sh.ldv;
     d.o_s0 = sh.o_s0; d.o_s1 = sh.o_s1; d.ldo = sh.ldo;
     if (out_scales.empty()) error_and_exit("Init Attention op failed! (out_scales must hold 1 or dv floats)");
-    if (dfx_attn_create(&d, &h_) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
-    // every matrix within its tensor: the last row of q, k and v up to its valid columns rounded up to 16, which is what the
-    // library may read (the create above has found the sizes positive and the strides non-negative)
-    auto end = [&](long long s0, long long s1, long long ld, long long rows, long long cols, bool read) {
-      const long long row = read ? std::min<long long>(ld, (cols + 15) / 16 * 16) : cols;
-      return (sh.batch0 - 1) * s0 + (sh.batch1 - 1) * s1 + (rows - 1) * ld + row;
-    };
-    if (end(sh.q_s0, sh.q_s1, sh.ldq, sh.tq, sh.d, true) > (long long)q_->size() || end(sh.k_s0, sh.k_s1, sh.ldk, sh.tk, sh.d, true) > (long long)k_->size() ||
-        end(sh.v_s0, sh.v_s1, sh.ldv, sh.tk, sh.dv, true) > (long long)v_->size() || end(sh.o_s0, sh.o_s1, sh.ldo, sh.tq, sh.dv, false) > (long long)o_->size())
-      error_and_exit("Init Attention op failed! (a matrix reaches beyond its tensor)");
-    if (dfx_attn_set_table(h_, table.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
-    if (dfx_attn_set_scales(h_, logit_scale, out_scales.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
-    if (bias) {
-      const dfx_logit_bias_desc bd = logit_bias_desc(*bias, sh.tq, sh.tk, "Attention");
-      if (dfx_attn_set_bias(h_, &bd, bias->table.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
-    }
-    st_.ensure_stream();
-  }
-  ~op_attention() override {
-    st_.retire(*o_);
-    dfx_attn_destroy(h_);
-  }
-
-  void submit() override {
-    run(true);
-    st_.fetch_out(*o_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*o_);
-  }
-  void submit_async() override { run(false); }
-  void wait() override {
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*o_);
+    reads(q_);
+    reads(k_);
+    reads(v_);
+    writes(o_);
+    build(0, [&](int) -> void * {
+      dfx_attn_t *h = static_cast<dfx_attn_t *>(create_or_exit(dfx_attn_create, d, "Init Attention op failed! (%s)"));
+      // every matrix within its tensor: the last row of q, k and v up to its valid columns rounded up to 16, which is what the
+      // library may read (the create above has found the sizes positive and the strides non-negative)
+      auto end = [&](long long s0, long long s1, long long ld, long long rows, long long cols, bool read) {
+        const long long row = read ? std::min<long long>(ld, (cols + 15) / 16 * 16) : cols;
+        return (sh.batch0 - 1) * s0 + (sh.batch1 - 1) * s1 + (rows - 1) * ld + row;
+      };
+      if (end(sh.q_s0, sh.q_s1, sh.ldq, sh.tq, sh.d, true) > (long long)q_->size() || end(sh.k_s0, sh.k_s1, sh.ldk, sh.tk, sh.d, true) > (long long)k_->size() ||
+          end(sh.v_s0, sh.v_s1, sh.ldv, sh.tk, sh.dv, true) > (long long)v_->size() || end(sh.o_s0, sh.o_s1, sh.ldo, sh.tq, sh.dv, false) > (long long)o_->size())
+        error_and_exit("Init Attention op failed! (a matrix reaches beyond its tensor)");
+      if (dfx_attn_set_table(h, table.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
+      if (dfx_attn_set_scales(h, logit_scale, out_scales.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
+      if (bias) {
+        const dfx_logit_bias_desc bd = logit_bias_desc(*bias, sh.tq, sh.tk, "Attention");
+        if (dfx_attn_set_bias(h, &bd, bias->table.data()) != DFX_OK) error_and_exit("Init Attention op failed! (%s)", dfx_last_error());
+      }
+      return h;
+    });
   }
 
 protected:
-  void infer() override { run(true); }
-  void run(bool sync_host) {
-    const void *q = st_.sync_in(*q_, sync_host);
-    const void *k = st_.sync_in(*k_, sync_host);
-    const void *v = st_.sync_in(*v_, sync_host);
-    void *o = st_.device_out(*o_);
-    st_.profile_begin();
-    check_dfx(dfx_attn_submit(h_, q, k, v, o, st_.stream), "attn submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_attn_submit(static_cast<dfx_attn_t *>(h), p[0], p[1], p[2], p[3], s), "attn submit");
   }
   const char *name() override { return "attention"; }
 
 private:
   memory *q_, *k_, *v_, *o_;
-  dfx_attn_t *h_;
-  detail::op_state st_;
 };
 
 // ---- squeeze-and-excitation (dfx_se_*) and, with no weights, the global average pooling it starts with.  The two weight
 // tensors are plain oihw {cr, c, 1, 1} and {c, cr, 1, 1}; dst may be src.  Weight hashing and batch sharding are
-// op_depthwise_conv's: the op is per image, so shards are independent. ----
-class op_squeeze_excite : public op {
+// op_base's: the op is per image, so shards are independent. ----
+class op_squeeze_excite : public op_base {
 public:
   op_squeeze_excite(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> *wei1, const std::unique_ptr<memory> *bia1,
                     const std::unique_ptr<memory> *wei2, const std::unique_ptr<memory> *bia2, const std::array<u8, 256> *table,
                     std::unique_ptr<memory> &dst, const std::vector<float> &scales1, const std::vector<float> &scales2,
                     const std::vector<float> &out_scales, round_mode rm)
-      : src_(src.get()), wei1_(wei1 ? wei1->get() : nullptr), bia1_(bia1 ? bia1->get() : nullptr), wei2_(wei2 ? wei2->get() : nullptr),
-        bia2_(bia2 ? bia2->get() : nullptr), dst_(dst.get()), pool_only_(!wei1), scales1_(scales1), scales2_(scales2), out_scales_(out_scales),
-        h_(nullptr), packed_hash_(0), packed_versions_(0) {
+      : op_base(destroy_as<dfx_se_t, dfx_se_destroy>), src_(src.get()), wei1_(wei1 ? wei1->get() : nullptr), bia1_(bia1 ? bia1->get() : nullptr), wei2_(wei2 ? wei2->get() : nullptr),
+        bia2_(bia2 ? bia2->get() : nullptr), dst_(dst.get()), pool_only_(!wei1), scales1_(scales1), scales2_(scales2), out_scales_(out_scales) {
     using fmt = memory::format;
     const char *what = pool_only_ ? "GlobalAvgPool" : "SqueezeExcite";
     if (!src_ || !dst_ || (!pool_only_ && (!wei1_ || !wei2_))) error_and_exit("Init %s op failed! (null tensor)", what);
@@ -3333,7 +1975,7 @@ public:
     d.cr = 1;
     d.nscales1 = d.nscales2 = d.nscales_out = 1;
     d.bia1_dt = d.bia2_dt = DFX_UNDEF;
-    d.round_mode = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode = to_dfx_round(rm);
     d.force_path = -1;
     if (pool_only_) {
       if (o[2] != 1 || o[3] != 1) error_and_exit("Init GlobalAvgPool op failed! (dst must be {bs, c, 1, 1})");
@@ -3358,161 +2000,53 @@ public:
       d.nscales2 = (int)scales2_.size();
       d.nscales_out = (int)out_scales_.size();
     }
-    src_img_ = (size_t)d.ih * d.iw * d.c;
-    dst_img_ = pool_only_ ? (size_t)d.c : src_img_;
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)d.ih * d.iw * d.c, dst_img = pool_only_ ? (size_t)d.c : src_img;
+    reads(src_, src_img);
+    writes(dst_, dst_img);  // (dst may be src)
+    // OPTION: global_avg_pool() borrows nothing, so nothing is hashed and pack() is never called
+    if (!pool_only_) {
+      borrows(wei1_); borrows(wei2_); borrows(bia1_); borrows(bia2_);
+    }
+    build(d.bs, [&](int n) -> void * {
       dfx_se_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_se_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init %s op failed! (%s)", what, dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_se_create(&d, &h_) != DFX_OK) error_and_exit("Init %s op failed! (%s)", what, dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_squeeze_excite() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_se_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_se_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      dfx_se_t *h = nullptr;
+      if (dfx_se_create(&ds, &h) != DFX_OK) error_and_exit("Init %s op failed! (%s)", what, dfx_last_error());
+      return h;
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
-  }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei1_->host_data(), wei1_->buffer_size(), 1469598103934665603ull);
-    v = hash_bytes(wei2_->host_data(), wei2_->buffer_size(), v);
-    if (bia1_) v = hash_bytes(bia1_->host_data(), bia1_->buffer_size(), v);
-    if (bia2_) v = hash_bytes(bia2_->host_data(), bia2_->buffer_size(), v);
-    return v | 1ull;
-  }
-  unsigned long long weights_versions() const {
-    return wei1_->host_version() + wei2_->host_version() + (bia1_ ? bia1_->host_version() : 0) + (bia2_ ? bia2_->host_version() : 0);
-  }
-  void set_weights(dfx_se_t *h) {
-    check_dfx(dfx_se_set_weights(h, (const int8_t *)wei1_->host_data(), bia1_ ? bia1_->host_data() : nullptr, scales1_.data(),
-                                 (const int8_t *)wei2_->host_data(), bia2_ ? bia2_->host_data() : nullptr, scales2_.data(),
+  void pack(void *h) override {
+    check_dfx(dfx_se_set_weights(static_cast<dfx_se_t *>(h), (const int8_t *)wei1_->host_data(), bia1_ ? bia1_->host_data() : nullptr,
+                                 scales1_.data(), (const int8_t *)wei2_->host_data(), bia2_ ? bia2_->host_data() : nullptr, scales2_.data(),
                                  table_.data(), out_scales_.data()),
               "squeeze_excite set_weights");
   }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const unsigned long long v = pool_only_ ? 0 : weights_hash();
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (!pool_only_ && v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        set_weights(sh.h);
-        sh.wei_seen = v;
-      }
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_se_submit(sh.h, sh.src, sh.dst, sh.stream), "squeeze_excite submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = pool_only_ ? 0 : weights_versions();
-    if (!pool_only_ && (sync_host || vers != packed_versions_)) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        set_weights(h_);
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);  // (dst may be src: uploaded, then overwritten in place)
-    st_.profile_begin();
-    check_dfx(dfx_se_submit(h_, in, o, st_.stream), "squeeze_excite submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_se_submit(static_cast<dfx_se_t *>(h), p[0], p[1], s), "squeeze_excite submit");
   }
   const char *name() override { return pool_only_ ? "global_avg_pool" : "squeeze_excite"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_se_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    unsigned long long wei_seen = 0;
-  };
   memory *src_, *wei1_, *bia1_, *wei2_, *bia2_, *dst_;
   bool pool_only_;  // no weights: global_avg_pool()
   std::array<u8, 256> table_;
   std::vector<float> scales1_, scales2_, out_scales_;
-  dfx_se_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 // ---- depthwise + pointwise conv (dfx_dwpw_*): depthwise_conv() with a u8 result followed by a 1x1 conv(), behind one
 // handle.  force_path stays -1 (auto), so the path is the library's choice (dfx.h, AUTO RULE at DFX_DWPW_FUSED).  The depthwise weights are a plain oihw
 // {c, 1, kh, kw} tensor, the pointwise weights OIhw4i16o4i {oc, c, 1, 1}; dst's dims give the output size. ----
-class op_depthwise_separable_conv : public op {
+class op_depthwise_separable_conv : public op_base {
 public:
   op_depthwise_separable_conv(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
                               std::array<int, 2> stride, std::array<int, 2> padding, const std::unique_ptr<memory> &wei_pw,
                               const std::unique_ptr<memory> &bia_pw, std::unique_ptr<memory> &dst, bool relu,
                               const std::vector<float> &scales, const std::vector<float> &scales_pw, round_mode rm,
                               round_mode rm_pw)
-      : src_(src.get()), wei_(wei.get()), bia_(bia.get()), wei_pw_(wei_pw.get()), bia_pw_(bia_pw.get()), dst_(dst.get()),
-        scales_(scales), scales_pw_(scales_pw), h_(nullptr), packed_hash_(0), packed_versions_(0) {
+      : op_base(destroy_as<dfx_dwpw_t, dfx_dwpw_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), wei_pw_(wei_pw.get()), bia_pw_(bia_pw.get()), dst_(dst.get()),
+        scales_(scales), scales_pw_(scales_pw) {
     using fmt = memory::format;
     if (!src_ || !wei_ || !wei_pw_ || !dst_) error_and_exit("Init DepthwiseSeparableConv op failed! (null tensor)");
     if (src_->data_type() != memory::dtype::u8 || wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc ||
@@ -3536,147 +2070,38 @@ public:
     d.bia0_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
     d.bia1_dt = bia_pw_ ? to_dfx_dtype(bia_pw_->data_type()) : DFX_UNDEF;
     d.relu = relu;
-    d.round_mode0 = rm == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
-    d.round_mode1 = rm_pw == round_mode::down ? DFX_ROUND_DOWN : DFX_ROUND_NEAREST;
+    d.round_mode0 = to_dfx_round(rm);
+    d.round_mode1 = to_dfx_round(rm_pw);
     d.nscales0 = (int)scales_.size();
     d.nscales1 = (int)scales_pw_.size();
     d.force_path = -1;
-    src_img_ = (size_t)d.ih * d.iw * d.c;
-    dst_img_ = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
-    for (const detail::shard_range &r : detail::plan_shards(d.bs)) {
-      shard sh;
-      sh.r = r;
+    const size_t src_img = (size_t)d.ih * d.iw * d.c;
+    const size_t dst_img = (size_t)d.oh * d.ow * d.oc * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    borrows(wei_); borrows(bia_); borrows(wei_pw_); borrows(bia_pw_);
+    build(d.bs, [&](int n) -> void * {
       dfx_dwpw_desc ds = d;
-      ds.bs = r.n;
-      check_dfx(dfx_set_device(r.device), "set device");
-      if (dfx_dwpw_create(&ds, &sh.h) != DFX_OK) error_and_exit("Init DepthwiseSeparableConv op failed! (%s)", dfx_last_error());
-      check_dfx(dfx_stream_create(&sh.stream), "stream create");
-      check_dfx(dfx_mem_alloc_device(&sh.src, (size_t)r.n * src_img_), "device alloc");
-      check_dfx(dfx_mem_alloc_device(&sh.dst, (size_t)r.n * dst_img_), "device alloc");
-      shards_.push_back(sh);
-    }
-    if (!shards_.empty()) {
-      check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-      return;
-    }
-    if (dfx_dwpw_create(&d, &h_) != DFX_OK) error_and_exit("Init DepthwiseSeparableConv op failed! (%s)", dfx_last_error());
-    st_.ensure_stream();
-  }
-  ~op_depthwise_separable_conv() override {
-    for (shard &sh : shards_) {
-      dfx_set_device(sh.r.device);
-      dfx_dwpw_destroy(sh.h);
-      dfx_stream_destroy(sh.stream);
-      dfx_mem_free_device(sh.src);
-      dfx_mem_free_device(sh.dst);
-    }
-    if (!shards_.empty()) dfx_set_device(shards_[0].r.device);
-    st_.retire(*dst_);
-    dfx_dwpw_destroy(h_);
-  }
-
-  void submit() override {
-    if (!shards_.empty()) {
-      enqueue_shards();
-      sync_shards();
-      return;
-    }
-    run(true);
-    st_.fetch_out(*dst_);
-    check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-    st_.settled(*dst_);
-  }
-  void submit_async() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(false);
-  }
-  void wait() override {
-    if (!shards_.empty()) {
-      sync_shards();
-    } else {
-      check_dfx(dfx_stream_sync(st_.stream), "stream sync");
-      st_.settled(*dst_);
-    }
+      ds.bs = n;
+      return create_or_exit(dfx_dwpw_create, ds, "Init DepthwiseSeparableConv op failed! (%s)");
+    });
   }
 
 protected:
-  void infer() override {
-    if (!shards_.empty()) enqueue_shards();
-    else run(true);
+  void pack(void *h) override {
+    check_dfx(dfx_dwpw_set_weights(static_cast<dfx_dwpw_t *>(h), (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr,
+                                   scales_.data(), (const int8_t *)wei_pw_->host_data(), bia_pw_ ? bia_pw_->host_data() : nullptr,
+                                   scales_pw_.data()),
+              "depthwise_separable_conv set_weights");
   }
-  unsigned long long weights_hash() {
-    using detail::hash_bytes;
-    unsigned long long v = hash_bytes(wei_->host_data(), wei_->buffer_size(), 1469598103934665603ull);
-    if (bia_) v = hash_bytes(bia_->host_data(), bia_->buffer_size(), v);
-    v = hash_bytes(wei_pw_->host_data(), wei_pw_->buffer_size(), v);
-    if (bia_pw_) v = hash_bytes(bia_pw_->host_data(), bia_pw_->buffer_size(), v);
-    return v | 1ull;
-  }
-  unsigned long long weights_versions() const { return wei_->host_version() + (bia_ ? bia_->host_version() : 0) + wei_pw_->host_version() + (bia_pw_ ? bia_pw_->host_version() : 0);
-  }
-  void enqueue_shards() {  // (see op_conv: host in -> host out per batch shard)
-    const unsigned long long v = weights_hash();
-    const char *hs = static_cast<const char *>(src_->host_data());
-    char *hd = static_cast<char *>(const_cast<void *>(dst_->host_data()));
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      if (v != sh.wei_seen) {
-        check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-        check_dfx(dfx_dwpw_set_weights(sh.h, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data(),
-                                       (const int8_t *)wei_pw_->host_data(), bia_pw_ ? bia_pw_->host_data() : nullptr, scales_pw_.data()),
-                  "depthwise_separable_conv set_weights");
-        sh.wei_seen = v;
-      }
-      check_dfx(dfx_memcpy_h2d(sh.src, hs + sh.r.n0 * src_img_, sh.r.n * src_img_, sh.stream), "H2D copy");
-      check_dfx(dfx_dwpw_submit(sh.h, sh.src, sh.dst, sh.stream), "depthwise_separable_conv submit");
-      check_dfx(dfx_memcpy_d2h(hd + sh.r.n0 * dst_img_, sh.dst, sh.r.n * dst_img_, sh.stream), "D2H copy");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-    detail::op_state::host_is_current(*dst_);
-  }
-  void sync_shards() {
-    for (shard &sh : shards_) {
-      check_dfx(dfx_set_device(sh.r.device), "set device");
-      check_dfx(dfx_stream_sync(sh.stream), "stream sync");
-    }
-    check_dfx(dfx_set_device(shards_[0].r.device), "set device");
-  }
-  void run(bool sync_host) {  // (weights: borrowed host tensors, hashed and re-packed as op_conv::run does)
-    const unsigned long long vers = weights_versions();
-    if (sync_host || vers != packed_versions_) {
-      const unsigned long long hash = weights_hash();
-      if (hash != packed_hash_) {
-        check_dfx(dfx_stream_sync(st_.stream), "stream sync");  // no launch may still read the old copy
-        check_dfx(dfx_dwpw_set_weights(h_, (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr, scales_.data(),
-                                       (const int8_t *)wei_pw_->host_data(), bia_pw_ ? bia_pw_->host_data() : nullptr, scales_pw_.data()),
-                  "depthwise_separable_conv set_weights");
-        packed_hash_ = hash;
-      }
-      packed_versions_ = vers;
-    }
-    const void *in = st_.sync_in(*src_, sync_host);
-    void *o = st_.device_out(*dst_);
-    st_.profile_begin();
-    check_dfx(dfx_dwpw_submit(h_, in, o, st_.stream), "depthwise_separable_conv submit");
-    st_.profile_end(name());
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_dwpw_submit(static_cast<dfx_dwpw_t *>(h), p[0], p[1], s), "depthwise_separable_conv submit");
   }
   const char *name() override { return "depthwise_separable_conv"; }
 
 private:
-  struct shard {
-    detail::shard_range r;
-    dfx_dwpw_t *h = nullptr;
-    dfx_stream_t stream = nullptr;
-    void *src = nullptr, *dst = nullptr;
-    unsigned long long wei_seen = 0;
-  };
   memory *src_, *wei_, *bia_, *wei_pw_, *bia_pw_, *dst_;
   std::vector<float> scales_, scales_pw_;
-  dfx_dwpw_t *h_;
-  unsigned long long packed_hash_, packed_versions_;
-  size_t src_img_, dst_img_;  // bytes per image
-  detail::op_state st_;
-  std::vector<shard> shards_;  // DEEPFUSION_DEVICES > 1 (see op_conv)
 };
 
 }  // namespace

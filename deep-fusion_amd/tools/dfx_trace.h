@@ -1,6 +1,6 @@
 // dfx_trace.h -- what dfx_trace_stub.cc records, for coherence_check.cc.  The stub is a host-only stand-in for
-// libdfx_hip.so: it runs no arithmetic and only writes down, in call order, every entry point of include/dfx.h that
-// touches memory or orders streams.  One host thread makes all the calls, so call order is the host's program order.
+// libdfx_hip.so: it runs no arithmetic and only writes down, in call order, every entry point of include/dfx.h: those
+// that touch memory or order streams with what they touch, the others as a NOTE.  One host thread makes all the calls, so call order is the host's program order.
 #pragma once
 #include <cstddef>
 #include <string>
@@ -14,6 +14,10 @@ enum kind {
   SYNC,            // dfx_stream_sync(stream): the host waits for the stream
   WAIT,            // dfx_stream_wait_stream(stream, other): later work on `stream` waits for what `other` holds now
   STREAM_DESTROY,  // dfx_stream_destroy(stream): no later record may name it
+  NOTE,            // any other entry point (set_device, create / destroy of a handle, alloc / free, stream create, events):
+                   // `name` is the whole line -- entry point, then the device ordinal, "#<allocation id>" (a handle is the id
+                   // of its packed copy), the byte count, "sid <n>" (the n-th stream created; 0 the default stream: not the
+                   // checker's clock number) or "event <n>".  No stream, no ranges: it orders nothing and is only printed.
 };
 
 struct range {

@@ -3,7 +3,10 @@
 // that touches memory or orders streams is appended to an in-process trace (dfx_trace.h) that coherence_check.cc walks
 // with vector clocks.  A *_submit records its src / lateral / dst ranges with the byte sizes of the descriptor given at
 // create time; copies record both sides and do copy (so that a sanitizer build sees a wrong range); set_weights is a
-// host-thread read of the borrowed tensors and a write of the handle's packed copy, which every submit reads.
+// host-thread read of the borrowed tensors and a write of the handle's packed copy, which every submit reads.  Every
+// other entry point -- dfx_set_device, handle create / destroy, dfx_mem_alloc_* / dfx_mem_free_*, dfx_stream_create, the
+// dfx_event_* calls -- leaves a NOTE, so that --dump is the complete call sequence; a NOTE names allocation ids, byte
+// counts and creation indices, never an address.
 //   DFX_TRACE_DEVICES=<n>   what dfx_device_count reports (default 1), so that DEEPFUSION_DEVICES shards can be traced
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +44,10 @@ std::vector<dfx_trace::record> g_trace;
 std::vector<std::string> g_errors;
 std::string g_last_error;
 int g_device = 0;
+int g_events = 0;
+
+void note(const std::string &text) { g_trace.push_back({dfx_trace::NOTE, nullptr, nullptr, text, {}}); }
+int stream_index(dfx_stream_t s) { return s ? static_cast<stream_rec *>(s)->id : 0; }  // creation index; 0: the default stream
 
 int fail(int rc, const std::string &msg) {
   g_last_error = msg;
@@ -53,21 +60,29 @@ void stub_error(const std::string &msg) {
 
 size_t dt_size(int dt) { return dt == DFX_F32 || dt == DFX_S32 ? 4 : 1; }
 
-int new_alloc(void **p, size_t bytes, bool host) {
+// `what`: the entry point, for the NOTE (null: the caller writes its own)
+int new_alloc(void **p, size_t bytes, bool host, const char *what) {
   char *b = static_cast<char *>(malloc(bytes ? bytes : 1));
   if (!b) return fail(DFX_ERR_HIP, "out of memory");
   g_allocs.push_back({b, bytes, host, true});
   *p = b;
+  if (what) note(std::string(what) + " #" + std::to_string(g_allocs.size() - 1) + " " + std::to_string(bytes) + " bytes");
   return DFX_OK;
 }
-int free_alloc(void *p, bool host) {
-  if (!p) return DFX_OK;
-  for (allocation &a : g_allocs)
+int free_alloc(void *p, bool host, const char *what) {
+  if (!p) {
+    if (what) note(std::string(what) + " null");
+    return DFX_OK;
+  }
+  for (size_t i = 0; i < g_allocs.size(); ++i) {
+    allocation &a = g_allocs[i];
     if (a.live && a.base == p && a.host == host) {
       a.live = false;
       free(a.base);
+      if (what) note(std::string(what) + " #" + std::to_string(i));
       return DFX_OK;
     }
+  }
   stub_error("free of a pointer that is no live allocation");
   return DFX_ERR_INVALID;
 }
@@ -107,14 +122,19 @@ handle *new_handle(const char *op) {
   h->op = op;
   h->lat = h->dst = 0;
   void *p = nullptr;
-  new_alloc(&p, 1, false);
+  new_alloc(&p, 1, false, nullptr);
   h->packed = static_cast<int>(g_allocs.size()) - 1;
+  note(std::string("dfx_") + op + "_create #" + std::to_string(h->packed));
   return h;
 }
 int destroy_handle(void *hv) {
   handle *h = static_cast<handle *>(hv);
-  if (!h) return DFX_OK;
-  free_alloc(g_allocs[h->packed].base, false);
+  if (!h) {
+    note("handle destroy null");
+    return DFX_OK;
+  }
+  note(std::string("dfx_") + h->op + "_destroy #" + std::to_string(h->packed));
+  free_alloc(g_allocs[h->packed].base, false, nullptr);
   delete h;
   return DFX_OK;
 }
@@ -178,6 +198,7 @@ int dfx_device_count(int *count) {
   return DFX_OK;
 }
 int dfx_set_device(int ordinal) {
+  note("dfx_set_device " + std::to_string(ordinal));
   int n = 1;
   dfx_device_count(&n);
   if (ordinal < 0 || ordinal >= n) return fail(DFX_ERR_NO_DEVICE, "no such device");
@@ -185,10 +206,10 @@ int dfx_set_device(int ordinal) {
   return DFX_OK;
 }
 
-int dfx_mem_alloc_host(void **p, size_t bytes) { return new_alloc(p, bytes, true); }
-int dfx_mem_free_host(void *p) { return free_alloc(p, true); }
-int dfx_mem_alloc_device(void **p, size_t bytes) { return new_alloc(p, bytes, false); }
-int dfx_mem_free_device(void *p) { return free_alloc(p, false); }
+int dfx_mem_alloc_host(void **p, size_t bytes) { return new_alloc(p, bytes, true, "dfx_mem_alloc_host"); }
+int dfx_mem_free_host(void *p) { return free_alloc(p, true, "dfx_mem_free_host"); }
+int dfx_mem_alloc_device(void **p, size_t bytes) { return new_alloc(p, bytes, false, "dfx_mem_alloc_device"); }
+int dfx_mem_free_device(void *p) { return free_alloc(p, false, "dfx_mem_free_device"); }
 int dfx_memcpy_h2d(void *dst_dev, const void *src_host, size_t bytes, dfx_stream_t s) {
   if (!stream_ok(s, "dfx_memcpy_h2d")) return DFX_ERR_INVALID;
   dfx_trace::record r{dfx_trace::ACCESS, s, nullptr, "dfx_memcpy_h2d", {}};
@@ -210,6 +231,7 @@ int dfx_memcpy_d2h(void *dst_host, const void *src_dev, size_t bytes, dfx_stream
 int dfx_stream_create(dfx_stream_t *s) {
   g_streams.push_back({static_cast<int>(g_streams.size()) + 1, g_device, true});
   *s = &g_streams.back();
+  note("dfx_stream_create sid " + std::to_string(g_streams.back().id) + " device " + std::to_string(g_device));
   return DFX_OK;
 }
 int dfx_stream_destroy(dfx_stream_t s) {
@@ -230,16 +252,24 @@ int dfx_stream_wait_stream(dfx_stream_t waiter, dfx_stream_t producer) {
   g_trace.push_back({dfx_trace::WAIT, waiter, producer, "dfx_stream_wait_stream", {}});
   return DFX_OK;
 }
+// an event is its creation index
 int dfx_event_create(dfx_event_t *e) {
-  *e = new int(0);
+  *e = new int(++g_events);
+  note("dfx_event_create event " + std::to_string(g_events));
   return DFX_OK;
 }
-int dfx_event_record(dfx_event_t, dfx_stream_t s) { return stream_ok(s, "dfx_event_record") ? DFX_OK : DFX_ERR_INVALID; }
-int dfx_event_elapsed_ms(dfx_event_t, dfx_event_t, float *ms) {
+int dfx_event_record(dfx_event_t e, dfx_stream_t s) {
+  if (!stream_ok(s, "dfx_event_record")) return DFX_ERR_INVALID;
+  note("dfx_event_record event " + std::to_string(*static_cast<int *>(e)) + " sid " + std::to_string(stream_index(s)));
+  return DFX_OK;
+}
+int dfx_event_elapsed_ms(dfx_event_t a, dfx_event_t b, float *ms) {
+  note("dfx_event_elapsed_ms event " + std::to_string(*static_cast<int *>(a)) + " event " + std::to_string(*static_cast<int *>(b)));
   *ms = 0.f;
   return DFX_OK;
 }
 int dfx_event_destroy(dfx_event_t e) {
+  if (e) note("dfx_event_destroy event " + std::to_string(*static_cast<int *>(e)));
   delete static_cast<int *>(e);
   return DFX_OK;
 }

@@ -1,6 +1,10 @@
-// pipeline_net.h -- one small network that uses every op class of include/deepfusion.h once, with the tensors staying on
-// the device between the ops.  Shared by coherence_check.cc (a recording fake behind the API, no GPU) and
-// pipeline_check.cc (the real libraries).  Batch 3, so that two batch shards split 2 + 1.
+// pipeline_net.h -- one small network that uses 14 op classes of include/deepfusion.h once -- reorder, image_conv,
+// depthwise_separable_conv, grouped_conv, dilated_conv, depthwise_conv, deconvolution, resize_add, concat_conv, conv,
+// eltwise_sum, conv_relu_pool, concat, inner_product -- with the tensors staying on the device between the ops.  Shared by
+// coherence_check.cc (a recording fake behind the API, no GPU) and pipeline_check.cc (the real libraries, whose numerics
+// reference follows this table: it does not change lightly).  The other ten classes -- scaled_sum, head, layer_norm,
+// linear, select, nms, roialign, matmul, attention, squeeze_excite -- are driven by token_net in coherence_check.cc
+// (scenarios g and h) and by their own GPU tests.  Batch 3, so that two batch shards split 2 + 1.
 //
 //   x_f  f32 nchw {3,3,20,20}   the caller's input of frame f (F of them)
 //   q    = reorder(x_f)                          u8 nhwc {3,3,20,20}     F ops, one per frame

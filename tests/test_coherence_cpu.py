@@ -1,8 +1,11 @@
 """No GPU: the host/device coherence protocol of host/deepfusion.cc is free of data races when every op class is
 chained with the tensors staying on the device.  tools/coherence_check is host/deepfusion.cc over a recording fake of
-the C ABI (tools/dfx_trace_stub.cc): it drives the network of tools/pipeline_net.h through include/deepfusion.h and
-checks the recorded trace with vector clocks -- for every two accesses to overlapping bytes of one buffer, at least one
-of them a write, one must happen-before the other.  One process per scenario (DEEPFUSION_DEVICES is read once)."""
+the C ABI (tools/dfx_trace_stub.cc): it drives two networks through include/deepfusion.h -- the one of
+tools/pipeline_net.h (14 op classes, scenarios a - f) and token_net of tools/coherence_check.cc (the other ten, scenarios
+g and h) -- and checks the recorded trace with vector clocks: for every two accesses to overlapping bytes of one buffer,
+at least one of them a write, one must happen-before the other.  Its --dump, every call of the C ABI in call order, is
+compared with tests/golden/coherence/.  One process per scenario (DEEPFUSION_DEVICES is read once)."""
+import difflib
 import os
 import re
 import subprocess
@@ -21,13 +24,22 @@ SCENARIOS = {
     "d": ({}, 2 * 14),                                                # synchronous and asynchronous submits mixed
     "e": ({}, 18),                                                    # ops destroyed while their launch is in flight
     "f": ({"DEEPFUSION_DEVICES": "2", "DFX_TRACE_DEVICES": "2"}, 2 * (2 * 12 + 2)),   # batch 3 over two shards
+    # token_net is 10 ops = 10 launches.  g: one frame of submit(), two of submit_async(), then scaled_sum, matmul,
+    # squeeze_excite and head once more around the two in-flight destructions
+    "g": ({}, 3 * 10 + 4),
+    # h: a frame of submit() and one of submit_async(); two shards double layer_norm, scaled_sum, squeeze_excite and head
+    "h": ({"DEEPFUSION_DEVICES": "2", "DFX_TRACE_DEVICES": "2"}, 2 * (2 * 4 + 6)),
 }
+GOLDEN = os.path.join(ROOT, "tests", "golden", "coherence")
+# golden file -> (scenario, environment on top of the scenario's own)
+DUMPS = dict({s: (s, {}) for s in SCENARIOS}, a_profile=("a", {"DEEPFUSION_PROFILE": "1"}))
 
 
-def _run(scenario, *args):
+def _run(scenario, *args, **more_env):
     assert os.path.exists(EXE), "run __graft_entry__.build() first"
     env = {k: v for k, v in os.environ.items() if k not in ("DEEPFUSION_DEVICES", "DFX_TRACE_DEVICES", "DEEPFUSION_PROFILE")}
     env.update(SCENARIOS[scenario][0])
+    env.update(more_env)
     p = subprocess.run([EXE, scenario] + list(args), env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
     return p.returncode, p.stdout.decode()
 
@@ -77,6 +89,28 @@ def test_the_trace_names_what_it_orders():
     assert len(set(reorders)) == 4                       # four first ops, four streams
     for s in reorders[1:]:                               # frames 1..3 overwrite q behind image_conv's read of it
         assert any(m.group(1) == s and m.group(2) == imgconv for m in waits), (s, imgconv)
+
+
+@pytest.mark.parametrize("name", sorted(DUMPS))
+def test_dump_equals_the_recorded_call_sequence(name):
+    """--dump is every call host/deepfusion.cc makes into the C ABI, in call order: device switches, creates, allocations,
+    copies, launches, waits, syncs, destroys (and, under DEEPFUSION_PROFILE=1, the event calls and the name() strings).
+    It must equal tests/golden/coherence/<name>.txt byte for byte.  The files were recorded from the commit before the 24
+    op classes of host/deepfusion.cc shared one skeleton (built with make DEEPFUSION_CC=<that revision's file>), so they
+    pin that the shared skeleton calls what the 24 copies called.  A deliberate change of the call sequence regenerates
+    them, one --dump run per file in the file's environment:
+        coherence_check <a..e, g> --dump > tests/golden/coherence/<s>.txt
+        DEEPFUSION_DEVICES=2 DFX_TRACE_DEVICES=2 coherence_check <f, h> --dump > tests/golden/coherence/<s>.txt
+        DEEPFUSION_PROFILE=1 coherence_check a --dump > tests/golden/coherence/a_profile.txt"""
+    scenario, env = DUMPS[name]
+    rc, out = _run(scenario, "--dump", **env)
+    assert rc == 0, out[-2000:]
+    with open(os.path.join(GOLDEN, name + ".txt")) as f:
+        want = f.read()
+    if out != want:
+        diff = list(difflib.unified_diff(want.splitlines(), out.splitlines(), "golden/%s.txt" % name, "coherence_check --dump", lineterm="", n=5))
+        end = next((i for i, ln in enumerate(diff[3:], 3) if ln.startswith("@@")), len(diff))      # the first differing region
+        pytest.fail("the call sequence differs from the recorded one\n" + "\n".join(diff[:min(end, 80)]), pytrace=False)
 
 
 def _selftest(mode):

@@ -27,7 +27,7 @@ static int direct_one(const ConvArgs &a, const DirectGeom &g, int grid, int lds,
 
 int DFX_INST_NAME(const ConvArgs &a, const DirectGeom &g, int nw, int wo, int G, int wo1, int grid, int lds,
                   hipStream_t s, int mode) {
-  // the requant specialisation follows the host's proofs (set_weights_direct): g.m1 is only set together with g.m0
+  // the requant specialisation follows the host's proofs (conv_weights.h, pack_streamed): g.m1 is only set together with g.m0
   const int qm = g.m1 == 3 ? 2 : (g.m1 == 2 ? 1 : 0);
 #define X(NWV, W, GG, W1, NP)                                                                    \
   if (nw == NWV && wo == W && G == GG && wo1 == W1 && g.npb == NP) {                          \

@@ -32,6 +32,12 @@ constexpr int MFMA_LC = 22;         // 16-byte chunks the loader wave holds per 
 // in isolation; the form op_sel_hi:[1,0] and scalar arithmetic never did).
 DFX_GEOM_HD constexpr int mfma_cst_floats(int oc, int oc1) { return oc1 ? 3 * oc + 5 * oc1 : 5 * oc; }
 
+// requant start values (see conv_mfma.cuh's header): bit patterns the accumulators start from
+constexpr int MAGIC0_BITS = 0x4B400000;   // 1.5 * 2^23: ulp 1, room for +-2^22
+constexpr int MAGIC1_BITS = 0x3E22F983;   // 1/(2*pi), an inline constant: ulp 2^-26, mantissa 0x22F983
+constexpr int MAGIC1_LO = -0x22F983;      // most negative / positive integer it can absorb
+constexpr int MAGIC1_HI = 0x7FFFFF - 0x22F983;
+
 struct MfmaGeom {  // unit decomposition chosen by the host (conv_plan.h: pick_geometry, plan_handout)
   int th, tw;      // unit size in output rows / columns
   int uy, ux;      // units per image along y / x
@@ -75,6 +81,18 @@ struct MfmaGeom {  // unit decomposition chosen by the host (conv_plan.h: pick_g
 
 // ---- conv_mfma_roles.cuh: the role-specialised resident kernel
 constexpr int RL_CTRL_BYTES = 512;                   // control block: the words of conv_mfma.cuh + the mid ring's
+#ifndef RL_NA
+#define RL_NA 6
+#endif
+#ifndef RL_NB
+#define RL_NB 8
+#endif
+constexpr int RL_A = RL_NA;                          // conv0 waves
+constexpr int RL_B = RL_NB;                          // conv1 + store waves
+constexpr int RL_C = RL_A + RL_B;                    // waves that stage the weights
+constexpr int RL_WAVES = RL_C + MFMA_TEAMS;          // + 2 loaders
+constexpr int RL_THREADS = 64 * RL_WAVES;            // 1024
+constexpr int MAGIC3_BITS = 0x4B000000;              // 2^23: stage-0 accumulator start of the "fma" mode
 
 // ---- conv_stream.cuh: the streamed-weight kernel
 constexpr int ST_THREADS = 256;

@@ -107,12 +107,8 @@ constexpr int MFMA_CW = 7;          // compute waves per loader
 constexpr int MFMA_SPIN_LIMIT = 1 << 24;  // bound of every flag wait (~seconds): a protocol error ends the launch
                                           // with wrong output (the parity tests catch it) instead of hanging the GPU
 
-// requant start values (see header): bit patterns the accumulators start from
-constexpr int MAGIC0_BITS = 0x4B400000;   // 1.5 * 2^23: ulp 1, room for +-2^22
+// requant start values (see header): MAGIC0_BITS, MAGIC1_BITS / _LO / _HI are in conv_geom.h (the host's proofs read them)
 constexpr float MAGIC0_F = 12582912.0f;
-constexpr int MAGIC1_BITS = 0x3E22F983;   // 1/(2*pi), an inline constant: ulp 2^-26, mantissa 0x22F983
-constexpr int MAGIC1_LO = -0x22F983;      // most negative / positive integer it can absorb
-constexpr int MAGIC1_HI = 0x7FFFFF - 0x22F983;
 
 // control block in LDS (ints)
 constexpr int CTL_NEXT = 0;   // 64 x the next tile claim of this CU (every lane of a claiming wave adds 1)

@@ -70,18 +70,7 @@ namespace dfx {
 #ifndef RL_RING
 #define RL_RING 5  // conv0 fragment prefetch depth of an A wave (k-steps in flight)
 #endif
-#ifndef RL_NA
-#define RL_NA 6
-#endif
-#ifndef RL_NB
-#define RL_NB 8
-#endif
-constexpr int RL_A = RL_NA;                          // conv0 waves
-constexpr int RL_B = RL_NB;                          // conv1 + store waves
-constexpr int RL_C = RL_A + RL_B;                    // waves that stage the weights
-constexpr int RL_WAVES = RL_C + MFMA_TEAMS;          // + 2 loaders
-constexpr int RL_THREADS = 64 * RL_WAVES;            // 768
-constexpr int MAGIC3_BITS = 0x4B000000;              // 2^23: stage-0 accumulator start of the "fma" mode
+// (RL_NA, RL_NB, RL_A .. RL_THREADS and MAGIC3_BITS: conv_geom.h -- the host's weight packing reads them)
 constexpr int RL_SPIN_LIMIT = 1 << 19;               // bound of the s_sleep(4) waits (~0.1 s): a protocol error ends the launch with
                                                      // wrong output (the parity tests catch it) instead of hanging the GPU
 

@@ -32,8 +32,9 @@
 #include "dfx_device.cuh"
 #include "dfx_internal.h"
 #include "requant_host.h"
-#pragma GCC visibility push(hidden)  // (the planner's inline functions are no part of the library's exported symbols)
+#pragma GCC visibility push(hidden)  // (the planner's and packer's inline functions are no part of the library's exported symbols)
 #include "conv_plan.h"
+#include "conv_weights.h"
 #pragma GCC visibility pop
 
 namespace dfx {
@@ -152,7 +153,7 @@ struct dfx_conv : ConvPlan {  // (the plan: kernel family, geometry, grid, LDS, 
   // role-specialised fused kernel (conv_mfma_roles.cuh): roles_ok (ConvPlan) = the SHAPE fits it, roles = the WEIGHTS
   // allow its requant modes (decided by dfx_conv_set_weights); otherwise the op runs on conv_mfma.cuh's kernel
   bool roles;
-  void *d_wei, *d_wei1, *d_consts;
+  void *d_wei;  // ONE buffer [W0 | W1 | constants] (conv_weights.h), allocated by the first dfx_conv_set_weights
   int *d_queue;  // MFMA variant: ring of DFX_QUEUE_RING x {next unit, finished loaders}, one slot per launch in flight
   unsigned launch_seq;
   // In-flight guard of the queue ring.  Launches on ONE stream are ordered by the stream; as soon as a handle
@@ -302,10 +303,7 @@ int dfx_event_destroy(dfx_event_t e) {
 }
 
 size_t dfx_blocked_offset(int o, int i, int kh, int kw, int I, int KH, int KW) {
-  // [o/16][i/16][kh][kw][(i%16)/4][o%16][i%4], jit_conv_kernel.cc:333-338
-  const size_t nb_ic = (size_t)I / 16;
-  return ((((size_t)(o / 16) * nb_ic + (size_t)(i / 16)) * KH + kh) * KW + kw) * 256 +
-         (size_t)((i % 16) / 4) * 64 + (size_t)(o % 16) * 4 + (size_t)(i % 4);
+  return blocked_offset(o, i, kh, kw, I, KH, KW);  // (conv_weights.h)
 }
 
 int dfx_reorder_oihw_to_blocked(const int8_t *oihw, int8_t *blocked, int O, int I, int KH,
@@ -330,7 +328,7 @@ int dfx_reorder_oihw_to_blocked(const int8_t *oihw, int8_t *blocked, int O, int 
 namespace dfx { int launch_conv_pw(const ConvArgs &, const PwGeom &, int, int, int, hipStream_t, int); }
 
 static int direct_dispatch(dfx_conv *h, const ConvArgs &a, hipStream_t s, int mode) {
-  if (h->pw) {  // pointwise unfused conv (conv_pw.cuh); the requant proofs live in dgeom (set_weights_direct)
+  if (h->pw) {  // pointwise unfused conv (conv_pw.cuh); the requant proofs live in dgeom (conv_weights.h, pack_streamed)
     PwGeom pg = h->pwgeom;
     pg.fast = h->dgeom.fast;
     pg.m0 = h->dgeom.m0;
@@ -399,7 +397,7 @@ static void conv_release(dfx_conv *h) {
   if (!h) return;
   DeviceGuard dg(h->device);
   h->host.release();
-  (void)hipFree(h->d_wei); (void)hipFree(h->d_wei1); (void)hipFree(h->d_consts);
+  (void)hipFree(h->d_wei);
   (void)hipFree(h->d_queue);
   (void)hipFree(h->d_prof);
   for (unsigned i = 0; i < DFX_QUEUE_RING; ++i)
@@ -505,253 +503,8 @@ int dfx_conv_create(const dfx_conv_desc *desc, dfx_conv_t **out) {
   return DFX_OK;
 }
 
-// One channel's precondition of the fast requant path (conv_mfma.cuh store_group<FAST>):
-// amax bounds |true accumulator|; comp + bias must fold into ONE exact f32 add (bias
-// integer-valued, |comp + bias| < 2^24, |acc + bias| < 2^24) and nothing may reach +-2^31.
-static bool fast_ok_channel(double amax, double comp, float bias, float scale) {
-  if (!std::isfinite(bias) || !std::isfinite(scale)) return false;
-  const double b = bias;
-  if (b != std::floor(b)) return false;
-  const double lim = 16777216.0;  // 2^24
-  if (std::fabs(comp + b) >= lim || amax + std::fabs(b) >= lim || std::fabs(comp) + amax >= lim) return false;
-  return (amax + std::fabs(b)) * std::fabs((double)scale) * 1.0001 + 2.0 < 2147480000.0;
-}
-
-// The constants of conv_stream.cuh and conv_direct.cuh: comp0 (s32) bias0 scale0 [OCP each] comp1 (s32) bias1 scale1
-// [OC1P each]; padding channels are all-zero (their intermediate is 0 and meets zero 1x1 weights).  fb0 / fb1: the
-// biases as f32.  Returns whether the fast requant path is proven for every channel of both stages; the bias slots
-// then hold comp + bias.
-static bool stream_consts(const dfx_conv_desc &d, int OCP, int OC1P, const int8_t *wei, const void *bia0, const float *scales0,
-                          const int8_t *wei1, const void *bia1, const float *scales1, std::vector<int32_t> &cst,
-                          std::vector<float> &fb0, std::vector<float> &fb1) {
-  const int OC = d.oc, IC = d.ic, OC1 = d.oc1x1, ntap = d.kh * d.kw;
-  cst.assign((size_t)3 * (OCP + OC1P), 0);
-  auto put_f = [&](size_t idx, float v) { memcpy(&cst[idx], &v, 4); };
-  bool fast = d.conv0_round_mode == DFX_ROUND_NEAREST && (OC1 == 0 || d.conv1_round_mode == DFX_ROUND_NEAREST);
-  fb0.assign(OC, 0.0f);
-  fb1.assign(OC1 ? OC1 : 1, 0.0f);
-  for (int c = 0; c < OC; ++c) {
-    int32_t sum = 0, pos = 0, neg = 0;
-    for (int ic = 0; ic < IC; ++ic)
-      for (int tap = 0; tap < ntap; ++tap) {
-        const int w = wei[dfx_blocked_offset(c, ic, tap / d.kw, tap % d.kw, IC, d.kh, d.kw)];
-        sum += w;
-        (w > 0 ? pos : neg) += w;
-      }
-    cst[c] = 128 * sum;
-    fb0[c] = d.bia0_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia0, d.bia0_dt, c);
-    const float sc = scales0[d.conv0_nscales > 1 ? c : 0];
-    put_f((size_t)OCP + c, fb0[c]);
-    put_f((size_t)2 * OCP + c, sc);
-    fast = fast && fast_ok_channel(255.0 * std::max(pos, -neg), 128.0 * sum, fb0[c], sc);
-  }
-  for (int c = 0; c < OC1; ++c) {
-    int32_t sum = 0, pos = 0, neg = 0;
-    for (int oc = 0; oc < OC; ++oc) {
-      const int w = wei1[dfx_blocked_offset(c, oc, 0, 0, OC, 1, 1)];
-      sum += w;
-      (w > 0 ? pos : neg) += w;
-    }
-    cst[(size_t)3 * OCP + c] = 128 * sum;
-    fb1[c] = d.bia1_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia1, d.bia1_dt, c);
-    const float sc = scales1[d.conv1_nscales > 1 ? c : 0];
-    put_f((size_t)3 * OCP + OC1P + c, fb1[c]);
-    put_f((size_t)3 * OCP + 2 * OC1P + c, sc);
-    fast = fast && fast_ok_channel(255.0 * std::max(pos, -neg), 128.0 * sum, fb1[c], sc);
-  }
-  fast = fast && fast_allowed();
-  if (fast) {  // the fast path reads comp + bias (an exact f32) from the bias slot
-    for (int c = 0; c < OC; ++c) put_f((size_t)OCP + c, (float)((double)cst[c] + (double)fb0[c]));
-    for (int c = 0; c < OC1; ++c)
-      put_f((size_t)3 * OCP + OC1P + c, (float)((double)cst[(size_t)3 * OCP + c] + (double)fb1[c]));
-  }
-  return fast;
-}
-
-// Packs weights for conv_stream.cuh: ONE device buffer
-//   [conv0 steps | conv1 steps | consts], a step = 2 k-blocks x (OCC | G) fragments of 1 KB,
-// in the exact order the kernel walks them (oc chunk, ic chunk, step; 1x1 group, step).
-static int set_weights_direct(dfx_conv_t *h, const int8_t *wei, const void *bia0, const float *scales0,
-                              const int8_t *wei1, const void *bia1, const float *scales1);
-
-static int set_weights_stream(dfx_conv_t *h, const int8_t *wei, const void *bia0, const float *scales0,
-                              const int8_t *wei1, const void *bia1, const float *scales1) {
-  if (h->direct) return set_weights_direct(h, wei, bia0, scales0, wei1, bia1, scales1);
-  const dfx_conv_desc &d = h->d;
-  const StreamGeom &g = h->sgeom;
-  const bool fused = d.oc1x1 > 0;
-  const int OCC = h->occ, G = h->G, OC = d.oc, IC = d.ic, OC1 = d.oc1x1;
-  const int OCP = 32 * g.ocb, OC1P = fused ? 32 * G * g.n_g1 : 0;
-  const size_t n0 = (size_t)g.s0_steps * 2 * OCC * 1024;
-  const size_t n1 = fused ? (size_t)g.n_g1 * g.ks2 * 2 * G * 1024 : 0;
-  std::vector<int8_t> pk(n0 + n1, 0);
-  const int ntap = d.kh * d.kw;
-  size_t o = 0;
-  for (int occ = 0; occ < g.n_occ; ++occ)
-    for (int icc = 0; icc < g.n_icc; ++icc) {
-      const int kbn = std::min(2, g.icb - 2 * icc), ns = ntap * kbn;
-      for (int s2 = 0; s2 < (ns + 1) / 2; ++s2)
-        for (int j = 0; j < 2; ++j)
-          for (int r = 0; r < OCC; ++r)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int b = 0; b < 16; ++b, ++o) {
-                const int s = 2 * s2 + j;
-                if (s >= ns) continue;  // padding k-block: zero weights
-                const int tap = s / kbn, icbl = s % kbn;
-                // fused: A operand, row = channel 32*(occ*OCC + r) + rho.  unfused: B operand with
-                // the store stage's channel permutation: column lam of block r = 32*OCC*occ + OCC*lam + r
-                const int oc = fused ? 32 * (occ * OCC + r) + (lane & 31) : 32 * OCC * occ + OCC * (lane & 31) + r;
-                const int ic = 64 * icc + 32 * icbl + 16 * (lane >> 5) + b;
-                if (oc < OC && ic < IC) pk[o] = wei[dfx_blocked_offset(oc, ic, tap / d.kw, tap % d.kw, IC, d.kh, d.kw)];
-              }
-    }
-  if (o != n0) return fail(DFX_ERR_HIP, "internal: conv0 pack size mismatch");
-  for (int g1 = 0; g1 < g.n_g1; ++g1)
-    for (int s2 = 0; s2 < g.ks2; ++s2)
-      for (int j = 0; j < 2; ++j)
-        for (int cc = 0; cc < G; ++cc)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int b = 0; b < 16; ++b, ++o) {
-              const int blk = 2 * s2 + j;
-              if (blk >= g.ocb) continue;
-              const int oc1 = 32 * G * g1 + G * (lane & 31) + cc;
-              const int oc = 32 * blk + 8 * (b >> 2) + 4 * (lane >> 5) + (b & 3);  // mid's k order
-              if (oc1 < OC1 && oc < OC) pk[o] = wei1[dfx_blocked_offset(oc1, oc, 0, 0, OC, 1, 1)];
-            }
-  std::vector<int32_t> cst;
-  std::vector<float> fb0, fb1;
-  const bool fast = stream_consts(d, OCP, OC1P, wei, bia0, scales0, wei1, bia1, scales1, cst, fb0, fb1);
-  h->sgeom.fast = fast ? 1 : 0;
-  if (!h->d_wei) HIP_TRY(hipMalloc(&h->d_wei, pk.size() + cst.size() * 4));
-  char *base = (char *)h->d_wei;
-  HIP_TRY(hipMemcpy(base, pk.data(), pk.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(base + pk.size(), cst.data(), cst.size() * 4, hipMemcpyHostToDevice));
-  h->args.wei = (const int8_t *)base;
-  h->args.wei1 = (const int8_t *)(base + n0);
-  h->args.consts = (const float *)(base + pk.size());
-  h->weights_set = true;
-  return DFX_OK;
-}
-
-// Packs weights for conv_direct.cuh: ONE device buffer [W0d | W1d | consts].
-//   W0d[ob][kb = icb * ntap + tap][lane][16]: byte b of lane = W0[oc = 32 ob + (lane & 31)][ic = 32 icb + 16 (lane >> 5) + b][tap]
-//   W1d[g1][blk][cc][lane][16]: byte b = W1[oc1 = 32 G g1 + G (lane & 31) + cc][oc = 32 blk + 8 (b >> 2) + 4 (lane >> 5) + (b & 3)]
-static int set_weights_direct(dfx_conv_t *h, const int8_t *wei, const void *bia0, const float *scales0,
-                              const int8_t *wei1, const void *bia1, const float *scales1) {
-  const dfx_conv_desc &d = h->d;
-  const DirectGeom &g = h->dgeom;
-  const int G = h->G, OC = d.oc, IC = d.ic, OC1 = d.oc1x1;
-  const int OCP = 32 * g.ocb, OC1P = 32 * G * g.n_g1;
-  const int ntap = d.kh * d.kw, nkb0 = g.icb * ntap;
-  const size_t n0 = (size_t)g.ocb * nkb0 * 1024, n1 = (size_t)g.n_g1 * g.ocb * G * 1024;
-  std::vector<int8_t> pk(n0 + n1, 0);
-  size_t o = 0;
-  for (int ob = 0; ob < g.ocb; ++ob)
-    for (int icb = 0; icb < g.icb; ++icb)
-      for (int tap = 0; tap < ntap; ++tap)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int b = 0; b < 16; ++b, ++o) {
-            const int oc = 32 * ob + (lane & 31), ic = 32 * icb + 16 * (lane >> 5) + b;
-            if (oc < OC && ic < IC) pk[o] = wei[dfx_blocked_offset(oc, ic, tap / d.kw, tap % d.kw, IC, d.kh, d.kw)];
-          }
-  for (int g1 = 0; g1 < g.n_g1; ++g1)
-    for (int blk = 0; blk < g.ocb; ++blk)
-      for (int cc = 0; cc < G; ++cc)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int b = 0; b < 16; ++b, ++o) {
-            const int oc1 = 32 * G * g1 + G * (lane & 31) + cc;
-            const int oc = 32 * blk + 8 * (b >> 2) + 4 * (lane >> 5) + (b & 3);
-            if (oc1 < OC1 && oc < OC) pk[o] = wei1[dfx_blocked_offset(oc1, oc, 0, 0, OC, 1, 1)];
-          }
-  if (o != n0 + n1) return fail(DFX_ERR_HIP, "internal: direct pack size mismatch");
-  std::vector<int32_t> cst;
-  std::vector<float> fb0, fb1;
-  const bool fast = stream_consts(d, OCP, OC1P, wei, bia0, scales0, wei1, bia1, scales1, cst, fb0, fb1);
-  auto put_f = [&](size_t idx, float v) { memcpy(&cst[idx], &v, 4); };
-  h->dgeom.fast = fast ? 1 : 0;
-  // Requant without int -> float conversions (conv_direct.cuh, round 3), proven per channel from the actual
-  // weights like the modes of the resident kernels: with activations stored as u8 - 128 the raw accumulator lies
-  // in [-(128 P + 127 N), 127 P + 128 N] (P / N = sums of the positive / negative weights' magnitudes).
-  //   m0  stage 0 "fma": start value bits(2^23) + comp + bias, t = acc + bias inside (-2^23, 2^23), bias
-  //       integer-valued, scale >= 0: comp slot <- start bits, bias slot <- -2^23 * scale
-  //   m1  stage 1 "magic" (u8 output through the 16-byte store path only): start 1/(2 pi), conditions of
-  //       magic1_ok; bias slot <- (comp + bias - 2^23 - 0x22F983) * 2^-26, scale slot <- scale * 2^26 (m1 = 2),
-  //       or bias slot <- (comp + bias - 2^23 - 0x22F983) * scale where that product is exact for every channel:
-  //       one fma (m1 = 3)
-  h->dgeom.m0 = h->dgeom.m1 = 0;
-  const bool no_magic = tune("DFX_NO_MAGIC") && atoi(tune("DFX_NO_MAGIC")) != 0;
-  if (fast && !no_magic) {
-    auto pn = [&](bool stage1, int c, double &P, double &N) {
-      P = N = 0;
-      if (!stage1) {
-        for (int ic = 0; ic < IC; ++ic)
-          for (int tap = 0; tap < ntap; ++tap) {
-            const int w = wei[dfx_blocked_offset(c, ic, tap / d.kw, tap % d.kw, IC, d.kh, d.kw)];
-            (w > 0 ? P : N) += std::abs(w);
-          }
-      } else {
-        for (int oc = 0; oc < OC; ++oc) {
-          const int w = wei1[dfx_blocked_offset(c, oc, 0, 0, OC, 1, 1)];
-          (w > 0 ? P : N) += std::abs(w);
-        }
-      }
-    };
-    // (stage 0's "fma" route relies on the unsigned saturation of a u8 result: the fused intermediate, or a u8 dst)
-    bool m0 = OC1 > 0 || d.dst_dt == DFX_U8;
-    for (int c = 0; c < OC && m0; ++c) {
-      double P, N;
-      pn(false, c, P, N);
-      const float sc = scales0[d.conv0_nscales > 1 ? c : 0];
-      const double b = fb0[c], cb = 128.0 * (P - N) + b;
-      m0 = b == std::floor(b) && sc >= 0.0f && std::isfinite(sc * 8388608.0f) &&
-           -(128.0 * P + 127.0 * N) + cb > -8388608.0 && 127.0 * P + 128.0 * N + cb < 8388608.0;
-    }
-    if (m0) {
-      for (int c = 0; c < OC; ++c) {
-        const float sc = scales0[d.conv0_nscales > 1 ? c : 0];
-        cst[c] = MAGIC3_BITS + cst[c] + (int32_t)fb0[c];
-        put_f((size_t)OCP + c, -8388608.0f * sc);
-      }
-      h->dgeom.m0 = 1;
-    }
-    bool m1 = d.dst_dt == DFX_U8 && G == 4 && OC1 > 0, fma1 = true;
-    for (int c = 0; c < OC1 && m1; ++c) {
-      double P, N;
-      pn(true, c, P, N);
-      const float sc = scales1[d.conv1_nscales > 1 ? c : 0];
-      const double b = fb1[c], cb = 128.0 * (P - N) + b, lo = -(128.0 * P + 127.0 * N), hi = 127.0 * P + 128.0 * N;
-      const double k = cb - 8388608.0 - (double)0x22F983;
-      m1 = b == std::floor(b) && lo >= (double)MAGIC1_LO && hi <= (double)MAGIC1_HI && std::fabs(k) < 16777216.0 &&
-           std::fabs(lo + cb) < 16777216.0 && std::fabs(hi + cb) < 16777216.0 && std::isfinite(sc * 67108864.0f);
-      const double prod = k * (double)sc;
-      fma1 = fma1 && std::isfinite(prod) && (double)(float)prod == prod;
-    }
-    m1 = m1 && m0;  // (the kernels specialise on "both stages without conversions": conv_direct.cuh, QM)
-    if (m1) {
-      for (int c = 0; c < OC1; ++c) {
-        const float sc = scales1[d.conv1_nscales > 1 ? c : 0];
-        const double k = (double)cst[(size_t)3 * OCP + c] + (double)fb1[c] - 8388608.0 - (double)0x22F983;
-        put_f((size_t)3 * OCP + OC1P + c, fma1 ? (float)(k * (double)sc) : (float)k * 1.4901161193847656e-08f);
-        put_f((size_t)3 * OCP + 2 * OC1P + c, sc * 67108864.0f);
-      }
-      h->dgeom.m1 = fma1 ? 3 : 2;
-    }
-  }
-#ifdef DK_DEBUG
-  h->dgeom.wei_bytes = (long long)n0; h->dgeom.wei1_bytes = (long long)n1; h->dgeom.cst_bytes = (long long)cst.size() * 4;
-#endif
-  if (!h->d_wei) HIP_TRY(hipMalloc(&h->d_wei, pk.size() + cst.size() * 4));
-  char *base = (char *)h->d_wei;
-  HIP_TRY(hipMemcpy(base, pk.data(), pk.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(base + pk.size(), cst.data(), cst.size() * 4, hipMemcpyHostToDevice));
-  h->args.wei = (const int8_t *)base;
-  h->args.wei1 = (const int8_t *)(base + n0);
-  h->args.consts = (const float *)(base + pk.size());
-  h->weights_set = true;
-  if (tune("DFX_DEBUG_PTRS")) fprintf(stderr, "[dfx] direct weights %p..%p (W0 %zu, W1 %zu, consts %zu bytes)\n", (void *)base, (void *)(base + pk.size() + cst.size() * 4), n0, n1, cst.size() * 4);
-  return DFX_OK;
-}
-
+// Weight images and requant-route proofs are conv_weights.h's (no HIP in there); here: the argument checks and the upload
+// of the ONE buffer [W0 | W1 | constants] a handle owns.
 int dfx_conv_set_weights(dfx_conv_t *h, const int8_t *wei, const void *bia0, const float *scales0,
                          const int8_t *wei1, const void *bia1, const float *scales1) {
   if (!h || !wei || !scales0) return fail(DFX_ERR_INVALID, "set_weights: null argument");
@@ -762,237 +515,38 @@ int dfx_conv_set_weights(dfx_conv_t *h, const int8_t *wei, const void *bia0, con
   if ((d.bia0_dt != DFX_UNDEF && !bia0) || (fused && d.bia1_dt != DFX_UNDEF && !bia1))
     return fail(DFX_ERR_INVALID, "set_weights: bias dtype set but pointer is null");
 
-  const int OC = d.oc, OC1 = d.oc1x1, IC = d.ic;
-  const size_t nw0 = (size_t)OC * IC * d.kh * d.kw, nw1 = (size_t)OC1 * OC;
-  std::vector<int8_t> p0(nw0), p1(nw1 ? nw1 : 1);
-  std::vector<float> cst((size_t)3 * (OC + OC1), 0.0f);
-  float *comp0 = cst.data();  // f32: exact, |comp| < 2^24 for K <= 1023
-  float *b0 = cst.data() + OC, *s0 = cst.data() + 2 * OC;
-  float *comp1 = cst.data() + 3 * OC;
-  float *b1 = cst.data() + 3 * OC + OC1, *s1 = cst.data() + 3 * OC + 2 * OC1;
-  for (int c = 0; c < OC; ++c) {
-    b0[c] = d.bia0_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia0, d.bia0_dt, c);
-    s0[c] = scales0[d.conv0_nscales > 1 ? c : 0];  // count 1 = broadcast (intended semantics)
-  }
-  for (int c = 0; c < OC1; ++c) {
-    b1[c] = d.bia1_dt == DFX_UNDEF ? 0.0f : bias_to_f32(bia1, d.bia1_dt, c);
-    s1[c] = scales1[d.conv1_nscales > 1 ? c : 0];
-  }
+  ConvWeights w;
+  const char *why = "";
+  const int rc = conv_pack_weights(d, *h, tune, wei, bia0, scales0, wei1, bia1, scales1, &w, &why);
+  if (rc) return fail(rc, "%s", why);
 
-  if (h->variant == DFX_VARIANT_MFMA_STREAM) return set_weights_stream(h, wei, bia0, scales0, wei1, bia1, scales1);
-
-  if (h->variant != DFX_VARIANT_GENERIC) {
-    const int ICB = h->icb, OCB = h->ocb, G = h->G, NCB = OC1 / 32;
-    // W0 fragments [r][tap][c][lane][16]: lane (rho = lane&31, hh = lane>>5), byte j
-    //   = W0[oc = 32r + rho][ic = 32c + 16hh + j][tap]
-    for (int r = 0; r < OCB; ++r)
-      for (int tap = 0; tap < 9; ++tap)
-        for (int c = 0; c < ICB; ++c)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 16; ++j) {
-              // fused: A operand, row = oc 32r + rho.  unfused: B operand with the channel
-              // permutation of the store stage (G == OCB): column lam of block r = oc G*lam + r
-              const int oc = fused ? 32 * r + (lane & 31) : G * (lane & 31) + r;
-              const int ic = 32 * c + 16 * (lane >> 5) + j;
-              p0[((((size_t)r * 9 + tap) * ICB + c) * 64 + lane) * 16 + j] =
-                  wei[dfx_blocked_offset(oc, ic, tap / 3, tap % 3, IC, 3, 3)];
-            }
-    // W1 fragments [cb][r][lane][16]: cb = cg*G + cc; lane (lam, hh); byte j = 4q + i
-    //   = W1[oc1 = 32G*cg + G*lam + cc][oc = 32r + 8q + 4hh + i]
-    for (int cb = 0; cb < NCB; ++cb)
-      for (int r = 0; r < OCB; ++r)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 16; ++j) {
-            const int cg = cb / G, cc = cb % G, lam = lane & 31, hh = lane >> 5;
-            const int oc1 = 32 * G * cg + G * lam + cc;
-            const int oc = 32 * r + 8 * (j >> 2) + 4 * hh + (j & 3);
-            p1[(((size_t)cb * OCB + r) * 64 + lane) * 16 + j] =
-                wei1[dfx_blocked_offset(oc1, oc, 0, 0, OC, 1, 1)];
-          }
-    // ---- constants and requant mode per stage (conv_mfma.cuh header; emit_group) ----
-    // Per channel, from the ACTUAL weights: P = sum of positive weights, N = -sum of negative
-    // ones.  With activations stored as u8 - 128 in [-128, 127] the raw MFMA accumulator lies in
-    // [-(128 P + 127 N), 127 P + 128 N]; comp = 128 * (P - N) turns it into the reference's s32
-    // accumulator, |true acc| <= 255 * max(P, N).
-    struct Ch { double P, N; };
-    std::vector<Ch> c0(OC), c1(OC1 ? OC1 : 1);
-    for (int oc = 0; oc < OC; ++oc) {
-      double P = 0, N = 0;
-      for (int ic = 0; ic < IC; ++ic)
-        for (int tap = 0; tap < 9; ++tap) {
-          const int w = wei[dfx_blocked_offset(oc, ic, tap / 3, tap % 3, IC, 3, 3)];
-          (w > 0 ? P : N) += std::abs(w);
-        }
-      c0[oc] = {P, N};
-    }
-    for (int o1 = 0; o1 < OC1; ++o1) {
-      double P = 0, N = 0;
-      for (int oc = 0; oc < OC; ++oc) {
-        const int w = wei1[dfx_blocked_offset(o1, oc, 0, 0, OC, 1, 1)];
-        (w > 0 ? P : N) += std::abs(w);
-      }
-      c1[o1] = {P, N};
-    }
-    // "fast": rounding to nearest-even (the caller checks the round mode), every value finite and
-    // |f| < 2^31 so the x86 overflow / NaN results of vcvtps2dq cannot occur
-    auto fast_ok = [](const Ch &c, float bias, float scale) {
-      if (!std::isfinite(bias) || !std::isfinite(scale)) return false;
-      const double amax = 255.0 * std::max(c.P, c.N);
-      return (amax + std::fabs((double)bias)) * std::fabs((double)scale) * 1.0001 + 2.0 < 2147480000.0;
-    };
-    // "magic", accumulator started from bits(1.5 * 2^23) + comp + bias (stage 0 of a fused op):
-    // bias integer-valued and raw + comp + bias inside the binade, i.e. |.| < 2^22
-    auto magic0_ok = [](const Ch &c, float bias) {
-      const double b = bias, cb = 128.0 * (c.P - c.N) + b;
-      if (b != std::floor(b)) return false;
-      return -(128.0 * c.P + 127.0 * c.N) + cb > -4194304.0 && 127.0 * c.P + 128.0 * c.N + cb < 4194304.0;
-    };
-    // "magic", accumulator started from the inline constant 1/(2 pi) = 0x3E22F983 (ulp 2^-26):
-    // raw within the mantissa's room; k = (comp + bias - 2^23 - 0x22F983) exactly representable;
-    // |acc + bias| < 2^24; scale * 2^26 finite
-    auto magic1_ok = [](const Ch &c, float bias, float scale) {
-      const double b = bias, cb = 128.0 * (c.P - c.N) + b;
-      if (b != std::floor(b)) return false;
-      const double lo = -(128.0 * c.P + 127.0 * c.N), hi = 127.0 * c.P + 128.0 * c.N;
-      if (lo < (double)MAGIC1_LO || hi > (double)MAGIC1_HI) return false;
-      if (std::fabs(cb - 8388608.0 - (double)0x22F983) >= 16777216.0) return false;
-      if (std::fabs(lo + cb) >= 16777216.0 || std::fabs(hi + cb) >= 16777216.0) return false;
-      return std::isfinite(scale * 67108864.0f);
-    };
-    const bool no_fast = tune("DFX_NO_FAST") && atoi(tune("DFX_NO_FAST")) != 0;     // testing aid: exact paths
-    const bool no_magic = tune("DFX_NO_MAGIC") && atoi(tune("DFX_NO_MAGIC")) != 0;  // testing aid: no magic paths
-    int mode0 = (d.conv0_round_mode == DFX_ROUND_NEAREST && !no_fast) ? 2 : 0;
-    for (int oc = 0; oc < OC && mode0; ++oc) {
-      if (!fast_ok(c0[oc], b0[oc], s0[oc])) mode0 = 0;
-      else if (mode0 == 2 && !(fused ? magic0_ok(c0[oc], b0[oc]) : magic1_ok(c0[oc], b0[oc], s0[oc]))) mode0 = 1;
-    }
-    int mode1 = (fused && d.conv1_round_mode == DFX_ROUND_NEAREST && !no_fast) ? 2 : 0;
-    for (int o1 = 0; o1 < OC1 && mode1; ++o1) {
-      if (!fast_ok(c1[o1], b1[o1], s1[o1])) mode1 = 0;
-      else if (mode1 == 2 && !magic1_ok(c1[o1], b1[o1], s1[o1])) mode1 = 1;
-    }
-    if (no_magic) { mode0 = std::min(mode0, 1); mode1 = std::min(mode1, 1); }
-    // "fma" (stage 0 of the role-specialised kernel, conv_mfma_roles.cuh): accumulator started from
-    // bits(2^23) + comp + bias.  t = acc + bias must stay inside (-2^23, 2^23): non-negative t then reads as the
-    // float 2^23 + t, negative t as 2^23 - |t|/2; fma(x, s, -2^23 s) = t * s with one rounding (2^23 s is exact)
-    // or something negative that the stage's ReLU + u8 saturation turn into 0 like the reference's negative
-    // product -- which needs s >= 0.  bias integer-valued; |acc| <= 2^24 follows (0 is a possible acc).
-    auto fma0_ok = [](const Ch &c, float bias, float scale) {
-      const double b = bias, cb = 128.0 * (c.P - c.N) + b;
-      if (b != std::floor(b) || !(scale >= 0.0f) || !std::isfinite(scale * 8388608.0f)) return false;
-      return -(128.0 * c.P + 127.0 * c.N) + cb > -8388608.0 && 127.0 * c.P + 128.0 * c.N + cb < 8388608.0;
-    };
-    bool roles = h->roles_ok && fused && mode1 == 2 && d.conv0_round_mode == DFX_ROUND_NEAREST && !no_fast && !no_magic;
-    for (int oc = 0; oc < OC && roles; ++oc)
-      if (!fast_ok(c0[oc], b0[oc], s0[oc]) || !fma0_ok(c0[oc], b0[oc], s0[oc])) roles = false;
-    if (roles) mode0 = 3;
-    h->roles = roles;
-    // "fma" for stage 1 (role-specialised kernel only): (x + B) * C = fma(x, C, B * C) with one rounding when
-    // the addend B * C = (comp + bias - 2^23 - 0x22F983) * scale is exactly representable -- power-of-two scales
-    // and a few others; checked per channel in double (a 24-bit integer times a 24-bit mantissa is exact there)
-    if (roles) {
-      bool fma1 = true;
-      for (int o1 = 0; o1 < OC1 && fma1; ++o1) {
-        const double k = 128.0 * (c1[o1].P - c1[o1].N) + (double)b1[o1] - 8388608.0 - (double)0x22F983;
-        const double prod = k * (double)s1[o1];
-        fma1 = std::isfinite(prod) && (double)(float)prod == prod;
-      }
-      if (fma1) mode1 = 3;
-    }
-    if (h->variant == DFX_VARIANT_MFMA_FUSED) {
-      // (the suffix names stage 1's requant route: "fma" = one v_fma_f32 per value, admitted where the addend is exactly
-      //  representable -- power-of-two scales and a few others; "magic" = v_add_f32 + v_mul_f32)
-      if (roles) snprintf(h->kernel_name, sizeof(h->kernel_name), "conv_mfma_roles_kernel<%d,%d,%d,%d>/%s", ICB, OCB, NCB, d.dst_dt,
-                          mode1 == 3 ? "fma" : "magic");
-      else snprintf(h->kernel_name, sizeof(h->kernel_name), "conv_mfma_fused_kernel<%d,%d,%d,%d>", ICB, OCB, G, d.dst_dt);
-      h->block = roles ? RL_THREADS : MFMA_THREADS;
-    }
-    // slot A is an integer (bit copy into the f32 array), B and C are floats
-    auto put_i = [](float *dst, int32_t v) { memcpy(dst, &v, 4); };
-    auto inline_stage = [&](int mode, const Ch &c, float bias, float scale, float *A, float *B, float *C) {
-      const int32_t comp = (int32_t)(128.0 * (c.P - c.N));
-      put_i(A, comp - MAGIC1_BITS);  // acc bits + A = the reference's s32 accumulator
-      if (mode == 3) {  // fma(x, C, B): B = (comp + bias - 2^23 - 0x22F983) * scale (proven exact), C = scale * 2^26
-        *B = (float)(((double)comp + (double)bias - 8388608.0 - (double)0x22F983) * (double)scale);
-        *C = scale * 67108864.0f;
-      } else if (mode == 2) {
-        *B = (float)((double)comp + (double)bias - 8388608.0 - (double)0x22F983) * 1.4901161193847656e-08f;  // * 2^-26, exact
-        *C = scale * 67108864.0f;                                                                           // * 2^26, exact
-      } else {
-        *B = bias;
-        *C = scale;
-      }
-    };
-    for (int oc = 0; oc < OC; ++oc) {
-      if (fused) {
-        const int32_t comp = (int32_t)(128.0 * (c0[oc].P - c0[oc].N));
-        put_i(comp0 + oc, mode0 == 3 ? MAGIC3_BITS + comp + (int32_t)b0[oc]
-                        : mode0 == 2 ? MAGIC0_BITS + comp + (int32_t)b0[oc] : comp);  // accumulator start value
-        if (mode0 == 3) b0[oc] = -8388608.0f * s0[oc];  // the fma's addend -2^23 * scale (exact)
-      } else {
-        float A, B, C;
-        inline_stage(mode0, c0[oc], b0[oc], s0[oc], &A, &B, &C);
-        comp0[oc] = A; b0[oc] = B; s0[oc] = C;
-      }
-    }
-    for (int o1 = 0; o1 < OC1; ++o1) {
-      float A, B, C;
-      inline_stage(mode1, c1[o1], b1[o1], s1[o1], &A, &B, &C);
-      comp1[o1] = A; b1[o1] = B; s1[o1] = C;
-    }
-    h->geom.mode0 = mode0;
-    h->geom.mode1 = mode1;
-    h->geom.s0_uniform = (fused && d.conv0_nscales == 1) ? 1 : 0;
-    h->geom.s0_value = scales0[0];
-  } else {
-    memcpy(p0.data(), wei, nw0);
-    if (fused) memcpy(p1.data(), wei1, nw1);
+  if (!h->d_wei) HIP_TRY(hipMalloc(&h->d_wei, w.image.size()));  // (the size depends on the plan alone: once per handle)
+  char *base = (char *)h->d_wei;
+  HIP_TRY(hipMemcpy(base, w.image.data(), w.image.size(), hipMemcpyHostToDevice));
+  h->args.wei = (const int8_t *)base;
+  h->args.wei1 = (const int8_t *)(base + w.off_w1);
+  h->args.consts = (const float *)(base + w.off_cst);
+  if (h->variant == DFX_VARIANT_MFMA_STREAM && h->direct) {  // conv_direct.cuh, conv_pw.cuh
+    h->dgeom.fast = w.fast;
+    h->dgeom.m0 = w.m0;
+    h->dgeom.m1 = w.m1;
+#ifdef DK_DEBUG
+    h->dgeom.wei_bytes = (long long)w.n_w0; h->dgeom.wei1_bytes = (long long)w.n_w1; h->dgeom.cst_bytes = (long long)w.n_cst;
+#endif
+  } else if (h->variant == DFX_VARIANT_MFMA_STREAM) {  // conv_stream.cuh
+    h->sgeom.fast = w.fast;
+  } else if (h->variant != DFX_VARIANT_GENERIC) {  // conv_mfma.cuh, conv_mfma_roles.cuh
+    h->geom.mode0 = w.mode0;
+    h->geom.mode1 = w.mode1;
+    h->geom.s0_uniform = w.s0_uniform;
+    h->geom.s0_value = w.s0_value;
   }
-
-  if (h->variant != DFX_VARIANT_GENERIC) {
-    // constants in the kernel's layout: the storing stage's B and C as pairs {k, k} (conv_mfma.cuh,
-    // mfma_cst_floats)
-    {
-      std::vector<float> lay((size_t)mfma_cst_floats(OC, OC1), 0.0f);
-      if (fused) {
-        memcpy(lay.data(), cst.data(), (size_t)(3 * OC + OC1) * 4);  // A0 B0 C0 A1
-        for (int c = 0; c < OC1; ++c) {
-          lay[(size_t)3 * OC + OC1 + 2 * c] = lay[(size_t)3 * OC + OC1 + 2 * c + 1] = b1[c];
-          lay[(size_t)3 * OC + 3 * OC1 + 2 * c] = lay[(size_t)3 * OC + 3 * OC1 + 2 * c + 1] = s1[c];
-        }
-      } else {
-        memcpy(lay.data(), cst.data(), (size_t)OC * 4);  // A0
-        for (int c = 0; c < OC; ++c) {
-          lay[(size_t)OC + 2 * c] = lay[(size_t)OC + 2 * c + 1] = b0[c];
-          lay[(size_t)3 * OC + 2 * c] = lay[(size_t)3 * OC + 2 * c + 1] = s0[c];
-        }
-      }
-      cst.swap(lay);
-    }
-    // one buffer in LDS-image order: [W0 fragments | W1 fragments | constants]
-    const size_t cbytes = round16(cst.size() * 4);
-    if (!h->d_wei) HIP_TRY(hipMalloc(&h->d_wei, nw0 + nw1 + cbytes));
-    char *base = (char *)h->d_wei;
-    HIP_TRY(hipMemcpy(base, p0.data(), nw0, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(base + nw0, p1.data(), nw1, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(base + nw0 + nw1, cst.data(), cst.size() * 4, hipMemcpyHostToDevice));
-    h->args.wei = (const int8_t *)base;
-    h->args.wei1 = (const int8_t *)(base + nw0);
-    h->args.consts = (const float *)(base + nw0 + nw1);
-  } else {
-    if (!h->d_wei) {
-      HIP_TRY(hipMalloc(&h->d_wei, nw0));
-      HIP_TRY(hipMalloc(&h->d_wei1, nw1 ? nw1 : 16));
-      HIP_TRY(hipMalloc(&h->d_consts, cst.size() * 4));
-    }
-    HIP_TRY(hipMemcpy(h->d_wei, p0.data(), nw0, hipMemcpyHostToDevice));
-    if (nw1) HIP_TRY(hipMemcpy(h->d_wei1, p1.data(), nw1, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_consts, cst.data(), cst.size() * 4, hipMemcpyHostToDevice));
-    h->args.wei = (const int8_t *)h->d_wei;
-    h->args.wei1 = (const int8_t *)h->d_wei1;
-    h->args.consts = (const float *)h->d_consts;
-  }
+  // (only the fused resident variant's roles decision changes these three; everywhere else they are the plan's again)
+  h->roles = w.roles;
+  snprintf(h->kernel_name, sizeof(h->kernel_name), "%s", w.kernel_name);
+  h->block = w.block;
   h->weights_set = true;
+  if (h->direct && tune("DFX_DEBUG_PTRS")) fprintf(stderr, "[dfx] direct weights %p..%p (W0 %zu, W1 %zu, consts %zu bytes)\n", (void *)base, (void *)(base + w.image.size()), w.n_w0, w.n_w1, w.n_cst);
   return DFX_OK;
 }
 

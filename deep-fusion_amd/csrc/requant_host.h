@@ -1,6 +1,6 @@
 // requant_host.h -- host-only: the per-channel requantisation constants (compensation, bias as f32, scale) of the ops
 // whose activations are stored as u8 - 128, and the proof of their fast requant route, written once for every op that
-// calls requant_consts() (dfx_api.hip takes the small helpers only: its proof is another one).  No HIP in here, so that
+// calls requant_consts() (the conv op takes the small helpers only: its proofs are others, conv_weights.h).  No HIP in here, so that
 // it can be built and run on its own (tools/requant_host_check.cc, under the host sanitizers).
 #pragma once
 

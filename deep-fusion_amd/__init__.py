@@ -38,6 +38,8 @@ from .capi import (  # noqa: F401
     LNORM_LAYER, LNORM_RMS, LNORM_AUTO, LNORM_ROW, LNORM_GENERIC, LNORM_MAX_C, LNORM_MAX_SHIFT, LnormDesc, LnormInfo, LayerNorm,
     lnorm_launches, lnorm_params,
     LINEAR_AUTO, LINEAR_TILE, LINEAR_GENERIC, LinearDesc, LinearInfo, Linear, linear_launches, gelu_table,
+    PATCHEMBED_AUTO, PATCHEMBED_TILE, PATCHEMBED_GENERIC, PatchEmbedDesc, PatchEmbedInfo, PatchEmbed, patchembed_launches,
+    patch_embed_table, patch_embed_prefix,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

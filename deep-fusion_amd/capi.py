@@ -47,6 +47,7 @@ LNORM_LAYER, LNORM_RMS = 0, 1
 LNORM_AUTO, LNORM_ROW, LNORM_GENERIC = -1, 0, 1
 LNORM_MAX_C, LNORM_MAX_SHIFT = 16384, 7
 LINEAR_AUTO, LINEAR_TILE, LINEAR_GENERIC = -1, 0, 1
+PATCHEMBED_AUTO, PATCHEMBED_TILE, PATCHEMBED_GENERIC = -1, 0, 1
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -322,6 +323,18 @@ class LinearInfo(ctypes.Structure):
                 ("kernel_name", ctypes.c_char * 96)]
 
 
+class PatchEmbedDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bs", "ih", "iw", "ic", "ph", "pw", "th", "tw", "oc", "src_dt", "dst_dt", "bia_dt",
+                                             "relu", "round_mode", "nscales", "table", "tok_offset", "force_path")] + \
+               [("img_rows", ctypes.c_int64), ("dst_ld", ctypes.c_int64)]
+
+
+class PatchEmbedInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "lds_bytes", "device", "granule")] + \
+               [("algorithmic_ops", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("kernel_name", ctypes.c_char * 96)]
+
+
 class DwPwDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t", "pad_l",
                                              "oc", "dst_dt", "bia0_dt", "bia1_dt", "relu", "round_mode0", "round_mode1",
@@ -559,6 +572,16 @@ def lib():
         "dfx_linear_destroy": (i32, [vp]),
         "dfx_debug_linear_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
         "dfx_debug_linear_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_patchembed_create": (i32, [ctypes.POINTER(PatchEmbedDesc), ctypes.POINTER(vp)]),
+        "dfx_patchembed_set_weights": (i32, [vp, vp, vp, vp]),
+        "dfx_patchembed_set_table": (i32, [vp, vp, ctypes.c_int64]),
+        "dfx_patchembed_set_prefix": (i32, [vp, vp]),
+        "dfx_patchembed_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_patchembed_submit_host": (i32, [vp, vp, vp]),
+        "dfx_patchembed_query": (i32, [vp, ctypes.POINTER(PatchEmbedInfo)]),
+        "dfx_patchembed_destroy": (i32, [vp]),
+        "dfx_debug_patchembed_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
+        "dfx_debug_patchembed_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -645,6 +668,45 @@ def linear_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_linear_launches(v))
     return v[LINEAR_TILE], v[LINEAR_GENERIC]
+
+
+def patchembed_launches():
+    """(tile, generic): dfx_patchembed_submit calls of this process that launched each kernel (dfx_debug_patchembed_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_patchembed_launches(v))
+    return v[PATCHEMBED_TILE], v[PATCHEMBED_GENERIC]
+
+
+def patch_embed_table(conv_bias, pos_embed, acc_step):
+    """The f32 {tokens, oc} table of dfa.PatchEmbed(table=True) from what a float model holds: (bias[o] + pos[t][o]) /
+    acc_step[o], the real-valued conv bias (None: 0) and position embedding in accumulator units, acc_step = the input's
+    step times the weights' (a scalar or per oc).  Computed in float64 and rounded once to f32."""
+    pos = np.asarray(pos_embed, dtype=np.float64)
+    if pos.ndim != 2:
+        raise ValueError("pos_embed is {tokens, oc}")
+    step = np.asarray(acc_step, dtype=np.float64).reshape(-1)
+    if step.size not in (1, pos.shape[1]) or not np.all(np.isfinite(step)) or np.any(step == 0):
+        raise ValueError("acc_step holds 1 or oc finite non-zero values")
+    b = np.zeros(pos.shape[1]) if conv_bias is None else np.asarray(conv_bias, dtype=np.float64).reshape(-1)
+    if b.size != pos.shape[1]:
+        raise ValueError("conv_bias holds oc values")
+    with np.errstate(over="ignore"):      # (a value beyond f32 becomes inf, which set_table refuses)
+        return ((b[None, :] + pos) / step[None, :]).astype(np.float32)
+
+
+def patch_embed_prefix(cls_token, pos_rows, out_step, out_dt=np.int8):
+    """The prefix rows of dfa.PatchEmbed.set_prefix: clamp(rint((cls_token + pos_rows) / out_step)) as out_dt (uint8 /
+    int8), ties to even, computed in float64.  cls_token and pos_rows are {t0, oc} (or {oc} for one row); pos_rows None: 0."""
+    out_dt = np.dtype(out_dt)
+    if out_dt not in (np.dtype(np.uint8), np.dtype(np.int8)):
+        raise ValueError("out_dt is uint8 or int8")
+    if not (np.isfinite(float(out_step)) and float(out_step) > 0):
+        raise ValueError("out_step must be finite and positive")
+    v = np.atleast_2d(np.asarray(cls_token, dtype=np.float64))
+    if pos_rows is not None:
+        v = v + np.atleast_2d(np.asarray(pos_rows, dtype=np.float64))
+    lo, hi = (0, 255) if out_dt == np.dtype(np.uint8) else (-128, 127)
+    return np.clip(np.rint(v / float(out_step)), lo, hi).astype(out_dt)
 
 
 def gelu_table(in_step, out_step, in_dt=np.int8, out_dt=np.int8):
@@ -1434,6 +1496,56 @@ class Linear(_Handle):
         t = np.ascontiguousarray(table).view(np.uint8).reshape(-1)
         assert t.size == 256
         _check(lib().dfx_linear_set_table(self._h, _p(t)))
+
+
+class PatchEmbed(_Handle):
+    """dfx_patchembed_* handle: int8 patch embedding (include/dfx.h): a non-overlapping ph x pw conv over an NHWC uint8 / int8
+    image as one GEMM that writes the token matrix {bs * img_rows, dst_ld}: token t of image b at row b * img_rows + tok_offset
+    + t.  Weights plain oihw {oc, ic, ph, pw}.  table=True: a per-(token, channel) f32 table in accumulator units
+    (patch_embed_table()) in the place of the bias; set_prefix(): tok_offset rows of dst's dtype stored in front of every
+    image's tokens (patch_embed_prefix()).  tokens_hw defaults to (ih // ph, iw // pw)."""
+
+    _OP, _INFO, _ROUTES = "dfx_patchembed", PatchEmbedInfo, 1
+
+    def __init__(self, src_shape_nhwc, oc, patch, tokens_hw=None, src_dtype=np.uint8, dst_dtype=np.int8, bia_dt=DFX_UNDEF, relu=False,
+                 rm=ROUND_NEAREST, nscales=1, table=False, tok_offset=0, img_rows=None, dst_ld=None, force_path=PATCHEMBED_AUTO):
+        code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
+        bs, ih, iw, ic = src_shape_nhwc
+        ph, pw = patch
+        th, tw = (ih // ph, iw // pw) if tokens_hw is None else tokens_hw
+        d = PatchEmbedDesc()
+        d.bs, d.ih, d.iw, d.ic, d.ph, d.pw, d.th, d.tw, d.oc = bs, ih, iw, ic, ph, pw, th, tw, oc
+        d.src_dt, d.dst_dt, d.bia_dt = code(src_dtype), code(dst_dtype), code(bia_dt)
+        d.relu, d.round_mode, d.nscales, d.table, d.tok_offset, d.force_path = int(relu), rm, nscales, int(table), tok_offset, force_path
+        d.img_rows = tok_offset + th * tw if img_rows is None else img_rows
+        d.dst_ld = oc if dst_ld is None else dst_ld
+        self.desc = d
+        self.src_shape, self.dst_shape = (bs, ih, iw, ic), (bs * d.img_rows, d.dst_ld)
+        self.src_np_dtype, self.dst_np_dtype = _NP.get(d.src_dt), _NP.get(d.dst_dt)
+        self._create(d)
+
+    def set_weights(self, wei, scales, bia=None):
+        """wei: int8 {oc, ic, ph, pw}; scales: 1 or oc floats; bia: oc entries of the descriptor's bias dtype"""
+        d = self.desc
+        ws = [np.ascontiguousarray(wei, dtype=np.int8), None if bia is None else np.ascontiguousarray(bia),
+              np.ascontiguousarray(scales, dtype=np.float32)]
+        assert ws[0].size == d.oc * d.ic * d.ph * d.pw, ws[0].shape
+        assert ws[2].size == d.nscales and (bia is None or ws[1].size == d.oc)
+        _check(lib().dfx_patchembed_set_weights(self._h, _p(ws[0]), _p(ws[1]), _p(ws[2])))
+
+    def set_table(self, table):
+        """float32 {th * tw, oc}, accumulator units"""
+        d = self.desc
+        t = np.ascontiguousarray(table, dtype=np.float32)
+        assert t.shape == (d.th * d.tw, d.oc), t.shape
+        _check(lib().dfx_patchembed_set_table(self._h, _p(t), d.oc))
+
+    def set_prefix(self, rows):
+        """{tok_offset, oc} of dst's dtype, stored verbatim"""
+        d = self.desc
+        r = np.ascontiguousarray(rows, dtype=self.dst_np_dtype)
+        assert r.size == d.tok_offset * d.oc, r.shape
+        _check(lib().dfx_patchembed_set_prefix(self._h, _p(r)))
 
 
 class TopK(Head):

@@ -1597,6 +1597,77 @@ private:
   std::vector<float> scales_;
 };
 
+// ---- int8 patch embedding (dfx_patchembed_*): a non-overlapping conv over an nhwc u8 / s8 image whose dst is a token matrix,
+// an nhwc tensor {bs, C', H, W} read as bs * H * W rows of C' channels: H * W >= tok_offset + th * tw rows per image, C' >= oc.
+// The kernel leaves alone the pad channels, the rows behind the tokens and, without a prefix, the rows in front of them
+// (undefined on the host afterwards, as op_linear's pad channels).  The weights are a plain oihw {oc, ic, ph, pw} tensor, hashed
+// and re-packed by op_base; table and prefix are copied at construction, into every shard's handle.  Batch sharding is
+// op_base's: both tensors are batch-major and the op is per image. ----
+class op_patch_embed : public op_base {
+public:
+  op_patch_embed(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
+                 std::unique_ptr<memory> &dst, bool relu, const std::vector<float> &scales, round_mode rm, const std::vector<float> &table,
+                 int tok_offset, const std::vector<u8> &prefix)
+      : op_base(destroy_as<dfx_patchembed_t, dfx_patchembed_destroy>), src_(src.get()), wei_(wei.get()), bia_(bia.get()), dst_(dst.get()), scales_(scales) {
+    using fmt = memory::format;
+    if (!src_ || !wei_ || !dst_) error_and_exit("Init PatchEmbed op failed! (null tensor)");
+    if (src_ == dst_) error_and_exit("Init PatchEmbed op failed! (in place is not built)");
+    if (wei_->data_type() != memory::dtype::s8 || src_->dim_format() != fmt::nhwc || dst_->dim_format() != fmt::nhwc ||
+        wei_->dim_format() != fmt::oihw || (bia_ && bia_->dim_format() != fmt::x))
+      error_and_exit("Init PatchEmbed op failed! (data type / format)");
+    auto i = src_->std_dims(), w = wei_->std_dims(), o = dst_->std_dims();
+    if (i[0] != o[0]) error_and_exit("Init PatchEmbed op failed! (Batch size do not equal)");
+    if (w[1] != i[1] || w[2] < 1 || w[3] < 1) error_and_exit("Init PatchEmbed op failed! (weights must be {oc, ic, ph, pw})");
+    if (bia_ && (int)bia_->size() != w[0]) error_and_exit("Init PatchEmbed op failed! (Bias channel do not match)");
+    dfx_patchembed_desc d;
+    memset(&d, 0, sizeof(d));
+    d.bs = i[0]; d.ic = i[1]; d.ih = i[2]; d.iw = i[3];
+    d.ph = w[2]; d.pw = w[3]; d.th = d.ih / d.ph; d.tw = d.iw / d.pw; d.oc = w[0];
+    d.src_dt = to_dfx_dtype(src_->data_type());
+    d.dst_dt = to_dfx_dtype(dst_->data_type());
+    d.bia_dt = bia_ ? to_dfx_dtype(bia_->data_type()) : DFX_UNDEF;
+    d.relu = relu;
+    d.round_mode = to_dfx_round(rm);
+    d.nscales = (int)scales_.size();
+    d.table = table.empty() ? 0 : 1;
+    d.tok_offset = tok_offset;
+    d.force_path = -1;
+    d.img_rows = (long long)o[2] * o[3];
+    d.dst_ld = o[1];
+    if (!table.empty() && table.size() != (size_t)d.th * d.tw * d.oc) error_and_exit("Init PatchEmbed op failed! (the table must be empty or hold th * tw * oc floats)");
+    if (!prefix.empty() && (tok_offset < 1 || prefix.size() != (size_t)tok_offset * d.oc * dtype_size(dst_->data_type())))
+      error_and_exit("Init PatchEmbed op failed! (the prefix must be empty or hold tok_offset * oc elements of dst's type)");
+    const size_t src_img = (size_t)d.ih * d.iw * d.ic;
+    const size_t dst_img = (size_t)d.img_rows * d.dst_ld * dtype_size(dst_->data_type());
+    reads(src_, src_img);
+    writes(dst_, dst_img);
+    borrows(wei_); borrows(bia_);
+    build(d.bs, [&](int n) -> void * {
+      dfx_patchembed_desc ds = d;
+      ds.bs = n;
+      dfx_patchembed_t *h = static_cast<dfx_patchembed_t *>(create_or_exit(dfx_patchembed_create, ds, "Init PatchEmbed op failed! (%s)"));
+      if (!table.empty() && dfx_patchembed_set_table(h, table.data(), d.oc) != DFX_OK) error_and_exit("Init PatchEmbed op failed! (%s)", dfx_last_error());
+      if (!prefix.empty() && dfx_patchembed_set_prefix(h, prefix.data()) != DFX_OK) error_and_exit("Init PatchEmbed op failed! (%s)", dfx_last_error());
+      return h;
+    });
+  }
+
+protected:
+  void pack(void *h) override {
+    check_dfx(dfx_patchembed_set_weights(static_cast<dfx_patchembed_t *>(h), (const int8_t *)wei_->host_data(), bia_ ? bia_->host_data() : nullptr,
+                                         scales_.data()),
+              "patch_embed set_weights");
+  }
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_patchembed_submit(static_cast<dfx_patchembed_t *>(h), p[0], p[1], s), "patch_embed submit");
+  }
+  const char *name() override { return "patch_embed"; }
+
+private:
+  memory *src_, *wei_, *bia_, *dst_;
+  std::vector<float> scales_;
+};
+
 // ---- image-wide top-K with peak filter (dfx_select_*): the k best elements of every image of an nhwc score tensor,
 // optionally only 3x3 local maxima and only elements >= min_val, with whole pixel rows of further nhwc tensors gathered
 // behind it.  src and the gather sources are registered as reads, idx, count, val and the gather destinations as writes
@@ -2192,6 +2263,12 @@ std::unique_ptr<op> linear(const std::unique_ptr<memory> &src, const std::unique
                            std::unique_ptr<memory> &dst, bool relu, std::vector<float> scales, round_mode rm, int k_valid,
                            const std::vector<u8> &table, memory::dtype table_in) {
   return std::unique_ptr<op>(new op_linear(src, wei, bia, dst, relu, scales, rm, k_valid, table, table_in));
+}
+
+std::unique_ptr<op> patch_embed(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei, const std::unique_ptr<memory> &bia,
+                                std::unique_ptr<memory> &dst, bool relu, std::vector<float> scales, round_mode rm, const std::vector<float> &table,
+                                int tok_offset, const std::vector<u8> &prefix) {
+  return std::unique_ptr<op>(new op_patch_embed(src, wei, bia, dst, relu, scales, rm, table, tok_offset, prefix));
 }
 
 std::array<long long, 3> attention_strides(int bs, int heads, int t, int d, long long ld) {

@@ -554,6 +554,24 @@ int dfx_linear_set_table(dfx_linear_t *h, const uint8_t *) { return set_weights(
 int dfx_linear_submit(dfx_linear_t *h, const void *src, void *dst, dfx_stream_t s) { return submit1(h, "dfx_linear_submit", src, dst, s); }
 int dfx_linear_destroy(dfx_linear_t *h) { return destroy_handle(h); }
 
+// ---- patch embedding: one read (the images), one write (the token matrix); set_weights reads the borrowed weights and bias ----
+int dfx_patchembed_create(const dfx_patchembed_desc *d, dfx_patchembed_t **out) {
+  if (!d || !out || d->bs < 1 || d->ih < 1 || d->iw < 1 || d->ic < 1 || d->ph < 1 || d->pw < 1 || d->th < 1 || d->tw < 1 || d->oc < 1 || d->tok_offset < 0 ||
+      d->img_rows < d->tok_offset + (long long)d->th * d->tw || d->dst_ld < d->oc)
+    return fail(DFX_ERR_INVALID, "bad patchembed descriptor");
+  handle *h = new_handle("patchembed");
+  h->src.push_back((size_t)d->bs * d->ih * d->iw * d->ic);
+  h->dst = (((size_t)d->bs * d->img_rows - 1) * d->dst_ld + d->oc) * dt_size(d->dst_dt);
+  h->wei = {(size_t)d->oc * d->ic * d->ph * d->pw, d->bia_dt ? (size_t)d->oc * dt_size(d->bia_dt) : 0};
+  *out = reinterpret_cast<dfx_patchembed_t *>(h);
+  return DFX_OK;
+}
+int dfx_patchembed_set_weights(dfx_patchembed_t *h, const int8_t *w, const void *b, const float *) { return set_weights(h, "dfx_patchembed_set_weights", {w, b}); }
+int dfx_patchembed_set_table(dfx_patchembed_t *h, const float *, int64_t) { return set_weights(h, "dfx_patchembed_set_table", {}); }
+int dfx_patchembed_set_prefix(dfx_patchembed_t *h, const void *) { return set_weights(h, "dfx_patchembed_set_prefix", {}); }
+int dfx_patchembed_submit(dfx_patchembed_t *h, const void *src, void *dst, dfx_stream_t s) { return submit1(h, "dfx_patchembed_submit", src, dst, s); }
+int dfx_patchembed_destroy(dfx_patchembed_t *h) { return destroy_handle(h); }
+
 // ---- image-wide top-K: reads src and the gather sources (`src`); writes idx (`dst`), val when given (`lat`), count and the
 // gather destinations (this op borrows no host tensors: `wei` holds the bytes of count and of each gather destination) ----
 int dfx_select_create(const dfx_select_desc *d, dfx_select_t **out) {

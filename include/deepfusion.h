@@ -477,6 +477,26 @@ std::unique_ptr<op> linear(const std::unique_ptr<memory> &src, const std::unique
                            int k_valid = 0, const std::vector<u8> &table = {},
                            memory::dtype table_in = memory::dtype::undef);
 
+// ---- extension: int8 patch embedding (dfx_patchembed_* in dfx.h): the non-overlapping convolution (window == stride) that a ViT /
+// DeiT / Swin / ConvNeXt / PVT starts or downsamples with, as one matrix product that writes the tokens layer_norm(), linear()
+// and attention() consume.  src: nhwc u8 / s8 {bs, ic, ih, iw}, any ic; wei: plain oihw s8 {oc, ic, ph, pw}: the window, which
+// is the stride, 1 .. 255 each way with ph * pw * ic <= 65025; th = ih / ph by tw = iw / pw patches per image, pixels beyond them
+// are not read.  dst: nhwc {bs, C', H, W} of u8 / s8 / s32 / f32 read as bs * H * W rows of C' >= oc channels: token ty * tw + tx of
+// an image is its row tok_offset + ty * tw + tx, and H * W >= tok_offset + th * tw.  bia: format x, oc entries, or null.  table:
+// empty, or th * tw * oc floats in accumulator units added per (token, channel) in the bias's place (conv bias + position
+// embedding; bia must then be null).  prefix: empty, or tok_offset * oc elements of dst's type (class / distillation / register
+// tokens, already quantised), stored into rows 0 .. tok_offset-1 of every image by the same launch.  What the kernel does not
+// write -- channels from oc on, rows behind the tokens, rows in front of them without a prefix -- is UNDEFINED on the host
+// afterwards, as linear()'s pad channels.  Arithmetic, scales, ReLU and rounding are image_conv()'s: without table and prefix,
+// with tok_offset 0 and C' = oc, dst holds bit for bit what image_conv() with stride = window and no padding gives.  Weight
+// hashing, submit / submit_async / wait and DEEPFUSION_DEVICES sharding over the batch are depthwise_conv()'s; table and prefix
+// are copied at construction. ----
+std::unique_ptr<op> patch_embed(const std::unique_ptr<memory> &src, const std::unique_ptr<memory> &wei,
+                                const std::unique_ptr<memory> &bia, std::unique_ptr<memory> &dst,
+                                bool relu = false, std::vector<float> scales = {1.f}, round_mode rm = round_mode::nearest,
+                                const std::vector<float> &table = {}, int tok_offset = 0,
+                                const std::vector<u8> &prefix = {});
+
 // ---- extension: batched int8 matrix product of two DEVICE tensors (dfx_bmm_* in dfx.h): the multiply whose second operand is
 // not a weight -- Q.K^T and P.V of an attention / non-local block, a correlation layer.  a (u8 / s8), b (s8) and c (u8 / s8 /
 // s32 / f32) are tensors of any dims; `shape` says where the matrices lie in them, in ELEMENTS from each tensor's first:

@@ -1397,6 +1397,98 @@ typedef struct dfx_linear_info {
 } dfx_linear_info;
 typedef struct dfx_linear dfx_linear_t;
 
+/* ---- int8 patch embedding: the non-overlapping convolution (window == stride) every ViT / DeiT / Swin / ConvNeXt / PVT starts
+ *      or downsamples with, as ONE GEMM that writes a TOKEN MATRIX: rows = bs * th * tw, K = ph * pw * ic, n = oc.  It adds a
+ *      per-(token, channel) table (conv bias + position embedding) and leaves / fills rows in front of every image's tokens
+ *      (class token, DeiT's distillation token, register tokens).
+ *
+ *      Operands.  src is NHWC {bs, ih, iw, ic}, u8 or s8, ic >= 1, at any byte address.  Patches are ph x pw (1 .. 255 each),
+ *      th x tw of them per image, 1 <= th <= ih / ph, 1 <= tw <= iw / pw: pixels beyond th * ph rows / tw * pw columns are
+ *      never read; there is no padding.  K = ph * pw * ic <= 65025.  wei is s8 {oc, ic, ph, pw}, plain oihw, a HOST pointer at
+ *      set_weights (dfx_imgconv's layout).  dst is a row matrix of bs * img_rows rows, dst_ld >= oc elements apart, u8 / s8 /
+ *      s32 / f32: token t = ty * tw + tx of image b is row b * img_rows + tok_offset + t, elements 0 .. oc-1.  Elements
+ *      oc .. dst_ld-1 are NOT written; rows tok_offset + th * tw .. img_rows-1 are NOT written.
+ *
+ *      Arithmetic: dfx_imgconv's, and therefore dfx_fc's, word for word.  acc = the exact s32 sum over (i, ky, kx); then
+ *        f = float(acc); f = f + bias[o]  or  f = f + table[t][o]  (one separately rounded add; skipped where neither exists);
+ *        f = f * scale[o or 0]; ReLU (asked for, or dst is u8); store
+ *      with the x86 conversion and saturations of csrc/dfx_device.cuh, never an FMA.
+ *
+ *      Table (table = 1; dfx_patchembed_set_table): f32 {th * tw, oc} in ACCUMULATOR units, a host pointer with a leading
+ *      dimension; entries must be finite.  table = 1 with bia_dt != DFX_UNDEF is DFX_ERR_INVALID: the caller folds the conv
+ *      bias into the table (Python: dfa.patch_embed_table), so there is one add on every route.  The padded device copy
+ *      {th * tw, oc rounded up to 4} f32 must not exceed 2^30 bytes.
+ *
+ *      Prefix (dfx_patchembed_set_prefix): tok_offset * oc elements of dst's dtype from the host, already quantised (Python:
+ *      dfa.patch_embed_prefix).  The launch that computes the tokens stores them verbatim into rows 0 .. tok_offset-1 of every
+ *      image; every element is written exactly once.  Without a prefix those rows are not written.
+ *
+ *      Requant route: "fast" / "exact", proved per channel from the actual weights as dfx_linear proves it, with
+ *      max_t |table[t][o]| in the place of |bias[o]|; proved again whenever weights or table change.  The generic kernel is
+ *      always exact and defines the bits.
+ *
+ *      Not built: overlapping windows or padding (dfx_imgconv); runs pw * ic that are not multiples of 4 bytes on the tile
+ *      kernel (ViT /14 on RGB); f32 / NCHW images (dfx_reorder first); Swin's patch merging; a fused layer norm behind the
+ *      embedding; split-K; a device-resident table; interpolated position embeddings.
+ *      Parity unpinned: the reference has no such op. ---- */
+typedef struct dfx_patchembed_desc {
+  int32_t bs, ih, iw, ic;      /* src NHWC; bs * ih * iw * ic <= 2^40; ph * iw * ic < 2^31 */
+  int32_t ph, pw;              /* 1 .. 255; K = ph * pw * ic <= 65025 */
+  int32_t th, tw;              /* tokens per axis: 1 <= th <= ih / ph, 1 <= tw <= iw / pw */
+  int32_t oc;                  /* 1 .. 2^31 - 128 */
+  int32_t src_dt;              /* DFX_U8 | DFX_S8 */
+  int32_t dst_dt;              /* DFX_F32 | DFX_S32 | DFX_S8 | DFX_U8 */
+  int32_t bia_dt;              /* DFX_UNDEF = none; must be DFX_UNDEF with a table */
+  int32_t relu, round_mode, nscales /* 1 | oc */;
+  int32_t table;               /* 0 | 1: a per-(token, channel) f32 table, dfx_patchembed_set_table */
+  int32_t tok_offset;          /* t0 >= 0: dst rows in front of every image's tokens */
+  int32_t force_path;          /* -1 auto | DFX_PATCHEMBED_TILE | DFX_PATCHEMBED_GENERIC */
+  int64_t img_rows;            /* dst rows per image, >= tok_offset + th * tw; bs * img_rows * dst_ld <= 2^40 */
+  int64_t dst_ld;              /* elements between dst rows, >= oc */
+} dfx_patchembed_desc;
+enum {  /* dfx_patchembed_info.path */
+  DFX_PATCHEMBED_TILE = 0,     /* patchembed_tile_kernel<BM, DST, FAST, G> (patchembed.cuh): dfx_linear's tile kernel (256 lanes, a
+                                  BM x 128 tile, K in slabs of 64 through two LDS buffers, v_mfma_i32_32x32x32_i8 on conflict-free
+                                  16-byte LDS reads, linear_pack.h's weight image in K order (ky, kx, i)) whose token loader
+                                  GATHERS: a 16-byte piece of a token's K comes from the image through a per-granule offset table
+                                  the host computed, so the kernel divides nothing per slab.  Class: G = 16 where pw * ic and
+                                  iw * ic are multiples of 16, G = 4 where both are multiples of 4; src aligned to G (checked per
+                                  submit: others take the generic kernel for that submit). */
+  DFX_PATCHEMBED_GENERIC = 1   /* one thread per dst element, grid-stride, any shape and alignment, exact requant.  It defines
+                                  the bits. */
+};
+/* DFX_PATCHEMBED_AUTO_NOTE: measured with tools/bench_patchembed on one MI355X (profiles/patchembed/bench_patchembed.txt: s8 out, a
+ * token table, forced legs alternating in one process, buffer sets in rotation beyond the Infinity Cache, windows of at least
+ * 3 ms, median of 5 rounds; the rounds' extremes are in the file: most legs stay within 1 % of their median, the widest reaches
+ * + 9 %).  The yardsticks are the generic kernel and (a) dfx_imgconv on auto with k = s on the same image, which is
+ * what a caller had before (imgconv_generic_kernel at every point).  At the tile height the plan takes, us per submit, tile /
+ * generic / (a):
+ *   ViT-B/16 224  bs 1: 14.2 / 140 / 486      bs 8: 14.9 / 872 / 3545     bs 64: 37.6 / 6485 / 27208
+ *   ViT-L/16 224  bs 1: 14.1 / 184 / 587      bs 8: 15.0 / 1122 / 4369    bs 64: 40.2 / 8614 / 33519
+ *   ViT-B/16 384  bs 1: 14.3 / 366 / 1295     bs 8: 15.9 / 2385 / 10024   bs 64: 75.9 / 19013 / 79944
+ *   ViT-L/16 384  bs 1: 14.4 / 454 / 1551     bs 8: 21.6 / 3300 / 12354   bs 64: 99.7 / 25379 / 99739
+ *   ViT-B/32 224  bs 1: 35.0 / 247 / 612      bs 8: 36.2 / 896 / 3668     bs 64: 38.1 / 6699 / 28005
+ *   Swin-T stem   bs 1: 7.51 / 17.6 / 19.3    bs 8: 8.71 / 115 / 145      bs 64: 48.7 / 826 / 1101
+ *   ConvNeXt 2x2 96->192 s8 (no (a): ic > 4)  bs 1: 9.49 / 71.9   bs 8: 10.1 / 447   bs 64: 29.7 / 3379
+ * AUTO RULE: DFX_PATCHEMBED_TILE in its class from the smallest of each size that was measured -- rows >= 49, oc >= 96, K >= 48
+ * and 3136 * 96 * 48 multiply-adds -- and DFX_PATCHEMBED_GENERIC everywhere else: nothing smaller was timed.  The tile kernel won
+ * at all 21 points, by 2.3x at the least (the Swin-T stem at bs 1), far beyond the rounds' spread.  Where it LOSES: to (b)
+ * dfx_linear's tile kernel on a patch matrix gathered beforehand (the gather not timed, no table), at every point, by 1.23x to
+ * 1.41x on the ViT points (ViT-B/16 224 bs 64: 37.6 us against 28.9), 1.35x to 1.37x on the ConvNeXt downsample and 1.46x to 1.88x
+ * on the Swin-T stem (bs 64: 48.7 against 25.8): that is what the in-kernel gather and the table cost today.  Best: 582 TOP/s (12.6 % of the 4600 TOP/s int8 matrix
+ * peak, ViT-L/16 384 bs 64) and 1.0 TB/s (12 % of the HBM peak, the ConvNeXt downsample at bs 64).  DESIGN.md section 4.25. */
+typedef struct dfx_patchembed_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t grid, block, lds_bytes;
+  int32_t device;
+  int32_t granule;             /* the tile class of the descriptor: 16, 4, or 0 (outside it) */
+  uint64_t algorithmic_ops;    /* 2 * bs * th * tw * oc * K */
+  uint64_t algorithmic_bytes;  /* the patches' bytes + oc * K weights + the tokens' dst elements + table / bias (as f32) + scales +
+                                  the prefix rows written */
+  char kernel_name[96];        /* "patchembed_tile<u8,s8,bm128,g16> fast +table", "patchembed_generic<u8,f32>" */
+} dfx_patchembed_info;
+typedef struct dfx_patchembed dfx_patchembed_t;
+
 /* ---- depthwise conv + pointwise conv: the depthwise-separable block of MobileNet / EfficientNet / Xception with the
  *      u8 tensor between its two convs kept on chip.  src NHWC u8 {bs,ih,iw,c}.
  *        stage 0: the depthwise conv of dfx_dwconv_desc (kh x kw, stride, padding, oh / ow given by the caller) with
@@ -1978,6 +2070,35 @@ int dfx_linear_submit_host(dfx_linear_t *h, const void *src_host, void *dst_host
 int dfx_linear_query(const dfx_linear_t *h, dfx_linear_info *info);
 int dfx_linear_destroy(dfx_linear_t *h);
 
+/* ---- int8 patch embedding (dfx_patchembed_desc above).  The descriptor is validated before anything touches a device, in
+ *      this order: DFX_ERR_INVALID for bs / ih / iw / ic < 1, ph or pw outside 1 .. 255, th outside 1 .. ih / ph, tw outside
+ *      1 .. iw / pw, K > 65025, oc outside 1 .. 2^31 - 128, a src dtype other than u8 / s8, a bad dst dtype, bias dtype, round
+ *      mode, a scales count other than 1 or oc, table other than 0 / 1, a table together with a bias, tok_offset < 0, a bad
+ *      force_path, img_rows < tok_offset + th * tw, dst_ld < oc, bs * ih * iw * ic > 2^40, ph * iw * ic >= 2^31,
+ *      bs * img_rows * dst_ld > 2^40, a table image beyond 2^30 bytes; then DFX_ERR_UNSUPPORTED only for force_path =
+ *      DFX_PATCHEMBED_TILE outside that class.  "No HIP device" is reported only for a valid descriptor.
+ *      set_weights: host pointers, copied: wei s8 {oc, ic, ph, pw}, bia oc entries of bia_dt (NULL when DFX_UNDEF), scales
+ *      nscales floats.  set_table: th * tw rows of oc floats, `ld` >= oc floats apart, copied; DFX_ERR_INVALID on a handle
+ *      created without a table and for a non-finite entry.  set_prefix: tok_offset * oc elements of dst's dtype, copied;
+ *      DFX_ERR_INVALID where tok_offset is 0.  Each may be called again and in any order (not while a submit of the handle is
+ *      in flight); the requant route is proved again from the weights and the table the handle then holds.
+ *      submit: asynchronous on `s`; ONE launch with its own arguments; it never writes to the handle: one handle serves
+ *      several streams and host threads at once.  DFX_ERR_STATE, with nothing launched, before set_weights and, on a handle
+ *      created with a table, before set_table.  DFX_ERR_INVALID, with nothing launched, for a null pointer, a dst that is not
+ *      aligned to its element and a dst that overlaps src.  A src that is not aligned to the class's granule takes the
+ *      generic kernel for that submit.  submit_host: synchronous, densely packed host tensors (src {bs, ih, iw, ic}, dst
+ *      {bs * img_rows, dst_ld}); dst's bytes that the op does not write come back as the staging buffer holds them.
+ *      Tuning switches: DFX_PATCHEMBED_GRID=n caps the grid of either kernel; DFX_PATCHEMBED_BM=64|128 fixes the tile height.
+ *      No CPU fallback.  Auto: DFX_PATCHEMBED_AUTO_NOTE. ---- */
+int dfx_patchembed_create(const dfx_patchembed_desc *desc, dfx_patchembed_t **out);
+int dfx_patchembed_set_weights(dfx_patchembed_t *h, const int8_t *wei, const void *bia, const float *scales);
+int dfx_patchembed_set_table(dfx_patchembed_t *h, const float *table, int64_t ld);
+int dfx_patchembed_set_prefix(dfx_patchembed_t *h, const void *rows);
+int dfx_patchembed_submit(dfx_patchembed_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_patchembed_submit_host(dfx_patchembed_t *h, const void *src_host, void *dst_host); /* synchronous */
+int dfx_patchembed_query(const dfx_patchembed_t *h, dfx_patchembed_info *info);
+int dfx_patchembed_destroy(dfx_patchembed_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -2093,6 +2214,11 @@ int dfx_debug_linear_launches(int64_t out[2]);
 /* the token linear op's one stage as the last dfx_linear_set_weights proved it, same numbering (0 exact, 1 fast; the generic
  * path is always exact).  DFX_ERR_STATE before set_weights. */
 int dfx_debug_linear_requant(const dfx_linear_t *h, int32_t out[1]);
+/* the same for dfx_patchembed_submit: out[DFX_PATCHEMBED_TILE], out[DFX_PATCHEMBED_GENERIC] */
+int dfx_debug_patchembed_launches(int64_t out[2]);
+/* the patch embedding's one stage as the handle's weights and table prove it now, same numbering (0 exact, 1 fast; the generic
+ * path is always exact).  DFX_ERR_STATE before set_weights. */
+int dfx_debug_patchembed_requant(const dfx_patchembed_t *h, int32_t out[1]);
 
 #ifdef __cplusplus
 }

@@ -169,6 +169,24 @@ int main(int argc, char **argv) {
     d = dense(1, 1, tq_edge - 1, 65025, 1, 1); EXPECT(rc(d) == DFX_OK);
     d = dense(1, 1, 2147483647 - 31, 1, 1, 2147483647 - 31); d.ldv = d.ldo = d.dv; d.o_s1 = d.o_s0 = 0;
     EXPECT(rc(d) == DFX_ERR_INVALID);  // (O's index range)
+    // all three strides of every operand near their limit at once: 1024 x 1024 matrices, 2^30 / 2^20 apart, rows 2^10 (Q, O) and
+    // 2^16 (K, V) apart: the extents the overlap check takes, the strips and the chain's descriptors at that range
+    d = dense(1024, 1024, 1024, 16, 16, 16);
+    d.dst_dt = DFX_F32; d.force_path = DFX_ATTN_FUSED;
+    d.q_s0 = d.k_s0 = d.v_s0 = d.o_s0 = 1ll << 30; d.q_s1 = d.k_s1 = d.v_s1 = d.o_s1 = 1ll << 20; d.ldq = d.ldo = 1ll << 10; d.ldk = d.ldv = 1ll << 16;
+    EXPECT(rc(d) == DFX_OK && attn_fused_class(d) && chain_ok(d));
+    {
+      const dfx_bmm_desc bl = attn_bmm_logits(d), bo = attn_bmm_context(d);
+      EXPECT(bmm_a_elems(bl) == (1ull << 40) - 1024 + 16 && bmm_c_elems(bo) == (1ull << 40) - 1024 + 16);
+      EXPECT(bmm_b_elems(bl) == 1023ull * (1ull << 30) + 1023ull * (1ull << 20) + 15ull * (1ull << 16) + 16 && bmm_b_elems(bo) == bmm_b_elems(bl));
+      const uintptr_t far = (uintptr_t)1 << 47;
+      const unsigned long long ob = 4 * bmm_c_elems(bo);
+      EXPECT(bmm_overlap(far, ob, far + ob - 1, 1) && !bmm_overlap(far, ob, far + ob, 16) && !bmm_overlap(far, ob, far - 16, 16) && bmm_overlap(far, ob, far - 16, 17));
+    }
+    EXPECT(attn_strips(d) == 1ll << 25 && attn_grid(d, 256, 0) == 2048 && attn_grid(d, 256, 1ll << 40) == 2048);
+    EXPECT(attn_algorithmic_ops(d) == 2ull * (1ull << 38) * 2);
+    d.ldq += 1008; EXPECT(rc(d) == DFX_ERR_INVALID);  // Q's index range beyond 2^40 (the step keeps the class)
+    d.ldq -= 1008; d.o_s1 -= 1; EXPECT(rc(d) == DFX_ERR_INVALID);  // (O's matrices would meet)
   }
   // ---- the fused class, its LDS plan, the forced path outside it
   {

@@ -161,6 +161,23 @@ int main(int argc, char **argv) {
     d = dense(2, 2, 2, 16, 16, 1); d.a_s0 = big; d.a_s1 = big; d.lda = big; EXPECT(rc(d) == DFX_ERR_INVALID);
     d = dense(2, 2, 2, 16, 16, 1); d.c_s0 = big; d.c_s1 = big / 2; d.ldc = big / 8; EXPECT(rc(d) == DFX_ERR_INVALID);
     d = dense(1, 1, 1, 16, 16, 1); d.a_s0 = big; d.b_s1 = big; d.c_s0 = big; EXPECT(rc(d) == DFX_OK);  // extents of 1: never used
+    // all three strides of every operand near their limit at once: 1024 x 1024 matrices of 1024 rows, 2^30 / 2^20 / 2^10 apart;
+    // the extents, tiles, items and grids at that range, and the overlap of operands of 2^40 elements
+    d = dense(1024, 1024, 1024, 16, 16, 1);
+    d.dst_dt = DFX_S32; d.force_path = DFX_BMM_MFMA;
+    d.a_s0 = d.c_s0 = d.b_s0 = 1ll << 30; d.a_s1 = d.c_s1 = d.b_s1 = 1ll << 20; d.lda = d.ldc = 1ll << 10; d.ldb = 1ll << 16;
+    EXPECT(rc(d) == DFX_OK && bmm_mfma_class(d) && bmm_c_disjoint(d));
+    EXPECT(bmm_a_elems(d) == (1ull << 40) - 1024 + 16 && bmm_c_elems(d) == (1ull << 40) - 1024 + 16);
+    EXPECT(bmm_b_elems(d) == 1023ull * (1ull << 30) + 1023ull * (1ull << 20) + 15ull * (1ull << 16) + 16);
+    EXPECT(bmm_matrices(d) == 1ll << 20 && bmm_tiles(d) == 1ll << 25 && bmm_units(d) == 1ll << 23 && bmm_items(d) == 1ll << 34);
+    EXPECT(bmm_grid(d, DFX_BMM_MFMA, 256, 0) == 4096 && bmm_grid(d, DFX_BMM_GENERIC, 256, 0) == 4096 && bmm_grid(d, DFX_BMM_MFMA, 256, 1ll << 40) == 4096);
+    EXPECT(bmm_algorithmic_ops(d) == 1ull << 39 && bmm_algorithmic_bytes(d) == (1ull << 34) + (1ull << 28) + (1ull << 36));
+    d.lda += 1008; d.ldc += 1008; EXPECT(rc(d) == DFX_ERR_INVALID);  // beyond 2^40 (the step keeps the class)
+    d.ldc -= 1008; EXPECT(rc(d) == DFX_ERR_INVALID);
+    d.lda -= 1008; d.c_s1 -= 1; EXPECT(rc(d) == DFX_ERR_INVALID);    // (C's matrices would meet)
+    const uintptr_t far = (uintptr_t)1 << 47;
+    const unsigned long long cb = 4 * ((1ull << 40) - 1024 + 16);
+    EXPECT(bmm_overlap(far, cb, far + cb - 1, 1) && !bmm_overlap(far, cb, far + cb, 16) && !bmm_overlap(far, cb, far - 16, 16) && bmm_overlap(far, cb, far - 16, 17));
   }
   // ---- INVALID before UNSUPPORTED; the MFMA class
   {

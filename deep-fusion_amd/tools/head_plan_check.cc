@@ -177,6 +177,15 @@ int main() {
   // ---- extents, overlap, bytes
   EXPECT(head_extent(1, 32, 21, 1) == 21 && head_extent(3, 32, 21, 4) == (2 * 32 + 21) * 4);
   EXPECT(head_extent(1ll << 35, 32, 32, 4) == (1ull << 42));
+  // the documented maximum rows * ld = 2^40 at both ends of the pitch's range, 4-byte elements; the pitches of tests/far_offsets.py
+  EXPECT(head_extent(1ll << 40, 1, 1, 4) == (1ull << 42) && head_extent(513, 2147483647, 65535, 4) == (512ull * 2147483647ull + 65535) * 4);
+  EXPECT(head_extent(5, (1 << 30) + 4160, 21, 1) == (1ull << 32) + 4 * 4160 + 21 && head_extent(3, (1 << 29) + 1040, 5, 4) == (1ull << 32) + 8320 + 20);
+  EXPECT(head_algorithmic_bytes(topk(1ll << 40, 1, 1, DFX_F32, 1, DFX_S32)) == 8 * (1ull << 40));
+  {
+    const uintptr_t far = (uintptr_t)1 << 47;  // an operand of 2^42 bytes against a neighbour on either side
+    EXPECT(head_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !head_overlap(far, 1ull << 42, far + (1ull << 42), 16) &&
+           !head_overlap(far, 1ull << 42, far - 16, 16) && head_overlap(far, 1ull << 42, far - 16, 17));
+  }
   EXPECT(head_overlap(100, 10, 109, 5) && !head_overlap(100, 10, 110, 5) && !head_overlap(110, 5, 100, 10) && head_overlap(100, 10, 90, 11));
   EXPECT(head_algorithmic_bytes(topk(70, 21, 32, DFX_U8, 1, DFX_U8)) == 70 * 21 + 70);
   EXPECT(head_algorithmic_bytes(topk(3, 1000, 1000, DFX_F32, 5, DFX_S32)) == 3 * 1000 * 4 + 3 * 5 * 4);

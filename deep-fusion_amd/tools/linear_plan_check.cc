@@ -209,6 +209,20 @@ int main(int argc, char **argv) {
     EXPECT(lin_algorithmic_bytes(f) == 10 * 20 + 30 * 20 + 10 * 30 + 4 * 30 + 4 * 30 + 256);
     EXPECT(lin_extent(10, 32, 20, 1) == 9 * 32 + 20 && lin_extent(10, 40, 30, 4) == (9 * 40 + 30) * 4);
     EXPECT(lin_overlap(100, 10, 109, 1) && !lin_overlap(100, 10, 110, 1) && !lin_overlap(110, 1, 100, 10) && lin_overlap(105, 1, 100, 10));
+    // the documented maximum, rows * ld = 2^40: extents (4-byte elements: 2^42 bytes), tiles, items and grids at full range
+    EXPECT(lin_extent(1ll << 20, 1ll << 20, 1ll << 20, 4) == 1ull << 42 && lin_extent(1ll << 40, 1, 1, 4) == 1ull << 42);
+    EXPECT(lin_extent(2, 1ll << 39, 40, 4) == ((1ull << 39) + 40) * 4 && lin_extent(1ll << 33, 128, 40, 1) == (1ull << 40) - 128 + 40);
+    EXPECT(lin_extent(3, (1ll << 31) + 4160, 72, 1) == (1ull << 32) + 8320 + 72);  // (the pitches of tests/far_offsets.py)
+    const uintptr_t far = (uintptr_t)1 << 47;  // an operand of 2^42 bytes against a neighbour on either side
+    EXPECT(lin_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !lin_overlap(far, 1ull << 42, far + (1ull << 42), 8) &&
+           !lin_overlap(far, 1ull << 42, far - 8, 8) && lin_overlap(far, 1ull << 42, far - 8, 9) && lin_overlap(far + (1ull << 32) + 64, 408, far, (1ull << 32) + 8392));
+    const dfx_linear_desc most = desc(1ll << 40, 1, 1, 1, 1), wide = desc(1ll << 33, 96, 128, 96, 128);
+    EXPECT(rc(most) == DFX_OK && rc(wide) == DFX_OK);
+    EXPECT(lin_mtiles(1ll << 40, 64) == 1ll << 34 && lin_mtiles(1ll << 40, 128) == 1ll << 33 && lin_mtiles((1ll << 40) - 1, 128) == 1ll << 33);
+    EXPECT(lin_tiles(most, 64) == 1ll << 34 && lin_tiles(wide, 128) == 1ll << 26 && lin_items(most) == 1ll << 40 && lin_items(wide) == 1ll << 40);
+    EXPECT(lin_grid(most, DFX_LINEAR_TILE, 64, 256, 0) == 512 && lin_grid(most, DFX_LINEAR_GENERIC, 64, 256, 0) == 4096 &&
+           lin_grid(wide, DFX_LINEAR_GENERIC, 128, 256, 0) == 4096 && lin_grid(most, DFX_LINEAR_TILE, 64, 256, 1ll << 40) == 512);
+    EXPECT(lin_algorithmic_ops(wide) == 2ull * 96 << 40 && lin_algorithmic_bytes(wide) == (96ull << 33) + 128 * 96 + (1ull << 40) + 4);
   }
   // ---- the image's sections
   for (int n : {1, 127, 128, 129, 264})

@@ -298,6 +298,19 @@ int main(int argc, char **argv) {
     d.tok_offset = 1; d.img_rows = 7; d.dst_ld = 12; d.dst_dt = DFX_S32;
     EXPECT(rc(d) == DFX_OK && pe_src_extent(d) == 2 * 8 * 8 * 4 && pe_dst_extent(d) == ((7 + 1 + 4 - 1) * 12 + 10) * 4ull);
     EXPECT(pe_image(d).bytes == pe_image(d).off_prefix + 48);
+    // the documented maxima: bs * ih * iw * ic = 2^40 and bs * img_rows * dst_ld = 2^40 with 4-byte elements; rows, tiles and grids
+    d = desc(1 << 16, 4096, 4096, 1, 4, 4, 8);
+    d.dst_dt = DFX_F32; d.img_rows = 1 << 20; d.dst_ld = 16;
+    EXPECT(rc(d) == DFX_OK && pe_src_extent(d) == 1ull << 40 && pe_rows(d) == 1ll << 36);
+    EXPECT(pe_dst_extent(d) == ((((1ull << 16) - 1) * (1ull << 20) + (1ull << 20) - 1) * 16 + 8) * 4);
+    EXPECT(pe_grid(d, DFX_PATCHEMBED_TILE, 64, 256, 0) == 512 && pe_grid(d, DFX_PATCHEMBED_GENERIC, 64, 256, 0) == 4096);
+    EXPECT(lin_tiles(pe_gemm(d, false), 64) == 1ll << 30 && lin_items(pe_gemm(d, false)) == 1ll << 39);
+    d.bs += 1; EXPECT(rc(d) == DFX_ERR_INVALID);
+    // the shapes of tests/far_offsets.py: 258 images of 2^24 bytes; three images whose rows lie 2^31 + 4160 bytes apart
+    d = desc(258, 2048, 2048, 4, 4, 4, 40); d.th = d.tw = 2; d.img_rows = 4; d.dst_ld = 40;
+    EXPECT(rc(d) == DFX_OK && pe_src_extent(d) == 258ull << 24 && pe_granule(d) == 16);
+    d = desc(3, 8, 8, 4, 4, 4, 40); d.tok_offset = 2; d.dst_ld = 64; d.img_rows = ((1ll << 31) + 4160) / 64;
+    EXPECT(rc(d) == DFX_OK && pe_dst_extent(d) == (2 * d.img_rows + 5) * 64ull + 40);
   }
   if (g_bad) {
     printf("patchembed_plan_check: %d check(s) failed\n", g_bad);

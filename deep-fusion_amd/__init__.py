@@ -40,6 +40,9 @@ from .capi import (  # noqa: F401
     LINEAR_AUTO, LINEAR_TILE, LINEAR_GENERIC, LinearDesc, LinearInfo, Linear, linear_launches, gelu_table,
     PATCHEMBED_AUTO, PATCHEMBED_TILE, PATCHEMBED_GENERIC, PatchEmbedDesc, PatchEmbedInfo, PatchEmbed, patchembed_launches,
     patch_embed_table, patch_embed_prefix,
+    WINDOW_PARTITION, WINDOW_REVERSE, WINDOW_ROW_MAJOR, WINDOW_COL_MAJOR, WINDOW_AUTO, WINDOW_ROW, WINDOW_GENERIC,
+    WINDOW_MAX_HW, WINDOW_MAX_WIN, WINDOW_MAX_PADDED, WindowDesc, WindowInfo, WindowOp, window_launches, swin_shift_mask,
+    swin_relative_bias,
     DWPW_AUTO, DWPW_FUSED, DWPW_TWO_LAUNCH, DwPwDesc, DwPwInfo, DwPwConv,
     lib, lib_path, build, reorder_oihw_to_blocked, declared_symbols,
 )

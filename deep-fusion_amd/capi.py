@@ -48,6 +48,10 @@ LNORM_AUTO, LNORM_ROW, LNORM_GENERIC = -1, 0, 1
 LNORM_MAX_C, LNORM_MAX_SHIFT = 16384, 7
 LINEAR_AUTO, LINEAR_TILE, LINEAR_GENERIC = -1, 0, 1
 PATCHEMBED_AUTO, PATCHEMBED_TILE, PATCHEMBED_GENERIC = -1, 0, 1
+WINDOW_PARTITION, WINDOW_REVERSE = 0, 1
+WINDOW_ROW_MAJOR, WINDOW_COL_MAJOR = 0, 1
+WINDOW_AUTO, WINDOW_ROW, WINDOW_GENERIC = -1, 0, 1
+WINDOW_MAX_HW, WINDOW_MAX_WIN, WINDOW_MAX_PADDED = 65535, 255, 1 << 22
 VARIANT_GENERIC, VARIANT_MFMA_FUSED, VARIANT_MFMA_CONV, VARIANT_MFMA_STREAM = 0, 1, 2, 3
 _NP = {DFX_F32: np.float32, DFX_S32: np.int32, DFX_S8: np.int8, DFX_U8: np.uint8}
 _DT = {np.dtype(np.float32): DFX_F32, np.dtype(np.int32): DFX_S32,
@@ -335,6 +339,16 @@ class PatchEmbedInfo(ctypes.Structure):
                 ("kernel_name", ctypes.c_char * 96)]
 
 
+class WindowDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("dir", "dt", "bs", "h", "w", "c", "wh", "ww", "shift_y", "shift_x", "order")] + \
+               [("grid_ld", ctypes.c_int64), ("win_ld", ctypes.c_int64), ("pad_value", ctypes.c_uint32), ("force_path", ctypes.c_int32)]
+
+
+class WindowInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "grid", "block", "device")] + \
+               [("algorithmic_bytes", ctypes.c_uint64), ("kernel_name", ctypes.c_char * 96)]
+
+
 class DwPwDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("bs", "c", "ih", "iw", "oh", "ow", "kh", "kw", "sh", "sw", "pad_t", "pad_l",
                                              "oc", "dst_dt", "bia0_dt", "bia1_dt", "relu", "round_mode0", "round_mode1",
@@ -582,6 +596,11 @@ def lib():
         "dfx_patchembed_destroy": (i32, [vp]),
         "dfx_debug_patchembed_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
         "dfx_debug_patchembed_requant": (i32, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "dfx_window_create": (i32, [ctypes.POINTER(WindowDesc), ctypes.POINTER(vp)]),
+        "dfx_window_submit": (i32, [vp, vp, vp, vp]),
+        "dfx_window_query": (i32, [vp, ctypes.POINTER(WindowInfo)]),
+        "dfx_window_destroy": (i32, [vp]),
+        "dfx_debug_window_launches": (i32, [ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -675,6 +694,56 @@ def patchembed_launches():
     v = (ctypes.c_int64 * 2)()
     _check(lib().dfx_debug_patchembed_launches(v))
     return v[PATCHEMBED_TILE], v[PATCHEMBED_GENERIC]
+
+
+def window_launches():
+    """(row, generic): dfx_window_submit calls of this process that launched each kernel (dfx_debug_window_launches)"""
+    v = (ctypes.c_int64 * 2)()
+    _check(lib().dfx_debug_window_launches(v))
+    return v[WINDOW_ROW], v[WINDOW_GENERIC]
+
+
+def _pair(v):
+    return (int(v), int(v)) if np.ndim(v) == 0 else (int(v[0]), int(v[1]))
+
+
+def swin_shift_mask(h, w, window, shift):
+    """The boolean {nW, wh * ww, wh * ww} attention mask of a shifted-window block, True = masked, for attention_bias(mask=...):
+    official Swin's img_mask construction over the PADDED hp x wp map -- each axis is cut into the slices [0, -window),
+    [-window, -shift), [-shift, end), the nine regions are labelled, the label map is partitioned into windows and two tokens
+    of a window may attend to each other only where their labels agree.  An axis with shift 0 is one region; shift (0, 0) gives
+    all False.  window and shift: an int or (y, x); the windows and their tokens are in dfa.WindowOp's row-major order."""
+    wh, ww = _pair(window)
+    sy, sx = _pair(shift)
+    if min(int(h), int(w), wh, ww) < 1:
+        raise ValueError("h, w and the window must be positive")
+    hp, wp = -(-int(h) // wh) * wh, -(-int(w) // ww) * ww
+    if not (0 <= sy < hp and 0 <= sx < wp):
+        raise ValueError("the shift must lie within the padded map")
+
+    def labels(n, win, s):
+        lab = np.zeros(n, dtype=np.int64)
+        if s:
+            lab[max(n - win, 0):n - s] = 1     # (slice(-win, -s) of the official code; an empty slice when s >= win)
+            lab[n - s:] = 2
+        return lab
+
+    img = labels(hp, wh, sy)[:, None] * 3 + labels(wp, ww, sx)[None, :]
+    win = img.reshape(hp // wh, wh, wp // ww, ww).transpose(0, 2, 1, 3).reshape(-1, wh * ww)
+    return np.ascontiguousarray(win[:, None, :] != win[:, :, None])
+
+
+def swin_relative_bias(table, window):
+    """Expands Swin's relative-position table {(2 wh - 1) * (2 ww - 1), heads} to {heads, wh * ww, wh * ww} for
+    attention_bias(rel_bias=...): entry [head, i, j] = table[(yi - yj + wh - 1) * (2 ww - 1) + (xi - xj + ww - 1), head] with
+    token i = yi * ww + xi (official Swin's relative_position_index).  The table's dtype is kept."""
+    wh, ww = _pair(window)
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape[0] != (2 * wh - 1) * (2 * ww - 1):
+        raise ValueError("the table is {(2 wh - 1) * (2 ww - 1), heads}")
+    ys, xs = np.divmod(np.arange(wh * ww), ww)
+    idx = (ys[:, None] - ys[None, :] + wh - 1) * (2 * ww - 1) + (xs[:, None] - xs[None, :] + ww - 1)
+    return np.ascontiguousarray(t[idx].transpose(2, 0, 1))
 
 
 def patch_embed_table(conv_bias, pos_embed, acc_step):
@@ -1457,6 +1526,34 @@ class LayerNorm(_Handle):
         s = None if shift is None else np.ascontiguousarray(shift, dtype=np.uint8).reshape(-1)
         assert g.size == c and (b is None or b.size == c) and (s is None or s.size == c)
         _check(lib().dfx_lnorm_set_params(self._h, _p(g), _p(b), _p(s)))
+
+
+class WindowOp(_Handle):
+    """dfx_window_* handle: window partition (dir WINDOW_PARTITION, grid -> windows) or reverse (WINDOW_REVERSE) of an NHWC token
+    grid {bs, h, w, c} (include/dfx.h): rows grid_ld elements apart on the grid side, win_ld on the window side, one dtype on
+    both, bytes moved as they are.  window and shift: an int or (y, x).  The window side holds bs * n_windows matrices of
+    wh * ww rows (win_rows rows in all); pad tokens of a partition are filled with pad_value.  submit(src, dst): src is the grid
+    for a partition, the windows for a reverse."""
+
+    _OP, _INFO = "dfx_window", WindowInfo
+
+    def __init__(self, dir, bs, h, w, c, window, shift=(0, 0), order=WINDOW_ROW_MAJOR, dtype=np.int8, grid_ld=None, win_ld=None,
+                 pad_value=0, force_path=WINDOW_AUTO):
+        code = lambda t: t if isinstance(t, int) else _DT[np.dtype(t)]  # noqa: E731
+        d = WindowDesc()
+        d.dir, d.dt, d.bs, d.h, d.w, d.c = dir, code(dtype), bs, h, w, c
+        d.wh, d.ww = _pair(window)
+        d.shift_y, d.shift_x = _pair(shift)
+        d.order = order
+        d.grid_ld = c if grid_ld is None else grid_ld
+        d.win_ld = c if win_ld is None else win_ld
+        d.pad_value, d.force_path = int(pad_value) & 0xffffffff, force_path
+        self.desc = d
+        if d.wh >= 1 and d.ww >= 1:            # (the library refuses the rest)
+            self.hp, self.wp = -(-h // d.wh) * d.wh, -(-w // d.ww) * d.ww
+            self.n_windows = (self.hp // d.wh) * (self.wp // d.ww)
+            self.win_rows = bs * self.hp * self.wp
+        self._create(d)
 
 
 class Linear(_Handle):

@@ -94,7 +94,7 @@ int dfx::fail(int code, const char *fmt, ...) {  // (declared in dfx_internal.h)
 namespace {
 const char *const kTuningKeys[] = {"DFX_MAX_TH", "DFX_FORCE_GEOM", "DFX_UNIT_PX", "DFX_STATIC_ROUNDS", "DFX_NO_FAST", "DFX_NO_MAGIC", "DFX_NO_LAZY", "DFX_HALF_UNITS", "DFX_NO_ROLES", "DFX_STORE_BOUND_BYTES",
                                    "DFX_STREAM_PXB", "DFX_STREAM_BLOCKING", "DFX_STREAM_PLANES", "DFX_STREAM_OCC_PAR",
-                                   "DFX_STREAM_DIRECT", "DFX_STREAM_PW", "DFX_DIRECT_NPB", "DFX_DIRECT_NW", "DFX_DIRECT_WO1", "DFX_STREAM_GRID", "DFX_DEBUG_PTRS", "DFX_DWCONV_GRID", "DFX_DWCONV_BAND", "DFX_DWPW_GRID", "DFX_DWPW_TH", "DFX_GCONV_GRID", "DFX_GCONV_TILE", "DFX_FC_SPLITK", "DFX_FC_GRID", "DFX_IMGCONV_GRID", "DFX_DECONV_GRID", "DFX_DILCONV_GRID", "DFX_DILCONV_SLAB", "DFX_DILCONV_STRIPS", "DFX_RESIZE_ROWS", "DFX_RESIZE_MAX_GRID", "DFX_SE_SLICES", "DFX_SE_GRID", "DFX_WSUM_GRID", "DFX_HEAD_GRID", "DFX_SELECT_CHUNK", "DFX_BMM_GRID", "DFX_ATTN_GRID", "DFX_LNORM_GRID", "DFX_LINEAR_GRID", "DFX_LINEAR_BM", "DFX_PATCHEMBED_GRID", "DFX_PATCHEMBED_BM",
+                                   "DFX_STREAM_DIRECT", "DFX_STREAM_PW", "DFX_DIRECT_NPB", "DFX_DIRECT_NW", "DFX_DIRECT_WO1", "DFX_STREAM_GRID", "DFX_DEBUG_PTRS", "DFX_DWCONV_GRID", "DFX_DWCONV_BAND", "DFX_DWPW_GRID", "DFX_DWPW_TH", "DFX_GCONV_GRID", "DFX_GCONV_TILE", "DFX_FC_SPLITK", "DFX_FC_GRID", "DFX_IMGCONV_GRID", "DFX_DECONV_GRID", "DFX_DILCONV_GRID", "DFX_DILCONV_SLAB", "DFX_DILCONV_STRIPS", "DFX_RESIZE_ROWS", "DFX_RESIZE_MAX_GRID", "DFX_SE_SLICES", "DFX_SE_GRID", "DFX_WSUM_GRID", "DFX_HEAD_GRID", "DFX_SELECT_CHUNK", "DFX_BMM_GRID", "DFX_ATTN_GRID", "DFX_LNORM_GRID", "DFX_LINEAR_GRID", "DFX_LINEAR_BM", "DFX_PATCHEMBED_GRID", "DFX_PATCHEMBED_BM", "DFX_WINDOW_GRID",
                                    "DEEPFUSION_PROFILE"};
 struct Tuning {
   std::mutex mu;

@@ -1668,6 +1668,61 @@ private:
   std::vector<float> scales_;
 };
 
+// ---- window partition / reverse (dfx_window_*): the tokens of an nhwc grid {bs, C, h, w} gathered into the rows of an nhwc
+// tensor {bs, C', H, W} with H * W = hp * wp (bs * nW windows of wh * ww rows), or back.  Data movement only: no weights, nothing
+// to pack.  Channels from c on are neither read nor written (undefined on the host afterwards, as op_layer_norm's pad channels).
+// src is registered as a read, dst as a write (op_state).  Batch sharding is op_base's: both tensors are batch-major and the
+// row map is per image. ----
+class op_window : public op_base {
+public:
+  op_window(int dir, memory *grid, memory *windows, const window_shape &ws, uint32_t pad_value, int c_valid)
+      : op_base(destroy_as<dfx_window_t, dfx_window_destroy>) {
+    using fmt = memory::format;
+    const char *who = dir == DFX_WINDOW_PARTITION ? "WindowPartition" : "WindowReverse";
+    if (!grid || !windows) error_and_exit("Init %s op failed! (null tensor)", who);
+    if (grid == windows) error_and_exit("Init %s op failed! (in place is not built)", who);
+    if (grid->dim_format() != fmt::nhwc || windows->dim_format() != fmt::nhwc || grid->data_type() != windows->data_type())
+      error_and_exit("Init %s op failed! (data type / format)", who);
+    auto g = grid->std_dims(), w = windows->std_dims();
+    if (g[0] != w[0]) error_and_exit("Init %s op failed! (Batch size do not equal)", who);
+    dfx_window_desc d;
+    memset(&d, 0, sizeof(d));
+    d.dir = dir;
+    d.dt = to_dfx_dtype(grid->data_type());
+    d.bs = g[0]; d.h = g[2]; d.w = g[3];
+    d.c = c_valid > 0 ? c_valid : (g[1] < w[1] ? g[1] : w[1]);
+    d.wh = ws.wh; d.ww = ws.ww; d.shift_y = ws.shift_y; d.shift_x = ws.shift_x;
+    d.order = ws.col_major ? DFX_WINDOW_COL_MAJOR : DFX_WINDOW_ROW_MAJOR;
+    d.grid_ld = g[1];
+    d.win_ld = w[1];
+    d.pad_value = pad_value;
+    d.force_path = -1;
+    if (ws.wh < 1 || ws.ww < 1) error_and_exit("Init %s op failed! (the window must be positive)", who);
+    const long long hp = ((long long)d.h + ws.wh - 1) / ws.wh * ws.wh, wp = ((long long)d.w + ws.ww - 1) / ws.ww * ws.ww;
+    if ((long long)w[2] * w[3] != hp * wp) error_and_exit("Init %s op failed! (the window side must hold hp * wp rows per image)", who);
+    const size_t es = dtype_size(grid->data_type());
+    const size_t grid_img = (size_t)d.h * d.w * g[1] * es, win_img = (size_t)(hp * wp) * w[1] * es;
+    if (dir == DFX_WINDOW_PARTITION) {
+      reads(grid, grid_img);
+      writes(windows, win_img);
+    } else {
+      reads(windows, win_img);
+      writes(grid, grid_img);
+    }
+    build(d.bs, [&](int n) -> void * {
+      dfx_window_desc ds = d;
+      ds.bs = n;
+      return create_or_exit(dfx_window_create, ds, dir == DFX_WINDOW_PARTITION ? "Init WindowPartition op failed! (%s)" : "Init WindowReverse op failed! (%s)");
+    });
+  }
+
+protected:
+  void launch(void *h, void *const *p, dfx_stream_t s) override {
+    check_dfx(dfx_window_submit(static_cast<dfx_window_t *>(h), p[0], p[1], s), "window submit");
+  }
+  const char *name() override { return "window"; }
+};
+
 // ---- image-wide top-K with peak filter (dfx_select_*): the k best elements of every image of an nhwc score tensor,
 // optionally only 3x3 local maxima and only elements >= min_val, with whole pixel rows of further nhwc tensors gathered
 // behind it.  src and the gather sources are registered as reads, idx, count, val and the gather destinations as writes
@@ -2269,6 +2324,15 @@ std::unique_ptr<op> patch_embed(const std::unique_ptr<memory> &src, const std::u
                                 std::unique_ptr<memory> &dst, bool relu, std::vector<float> scales, round_mode rm, const std::vector<float> &table,
                                 int tok_offset, const std::vector<u8> &prefix) {
   return std::unique_ptr<op>(new op_patch_embed(src, wei, bia, dst, relu, scales, rm, table, tok_offset, prefix));
+}
+
+std::unique_ptr<op> window_partition(const std::unique_ptr<memory> &grid, std::unique_ptr<memory> &windows, window_shape shape,
+                                     uint32_t pad_value, int c_valid) {
+  return std::unique_ptr<op>(new op_window(DFX_WINDOW_PARTITION, grid.get(), windows.get(), shape, pad_value, c_valid));
+}
+
+std::unique_ptr<op> window_reverse(const std::unique_ptr<memory> &windows, std::unique_ptr<memory> &grid, window_shape shape, int c_valid) {
+  return std::unique_ptr<op>(new op_window(DFX_WINDOW_REVERSE, grid.get(), windows.get(), shape, 0, c_valid));
 }
 
 std::array<long long, 3> attention_strides(int bs, int heads, int t, int d, long long ld) {

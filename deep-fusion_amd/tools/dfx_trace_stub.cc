@@ -538,6 +538,22 @@ int dfx_lnorm_submit(dfx_lnorm_t *hv, const void *src, void *dst, dfx_stream_t s
 }
 int dfx_lnorm_destroy(dfx_lnorm_t *h) { return destroy_handle(h); }
 
+// ---- window partition / reverse: one read (src), one write (dst); the row map is the handle's own ----
+int dfx_window_create(const dfx_window_desc *d, dfx_window_t **out) {
+  if (!d || !out || d->bs < 1 || d->h < 1 || d->w < 1 || d->c < 1 || d->wh < 1 || d->ww < 1 || d->grid_ld < d->c || d->win_ld < d->c)
+    return fail(DFX_ERR_INVALID, "bad window descriptor");
+  handle *h = new_handle("window");
+  const size_t hp = ((size_t)d->h + d->wh - 1) / d->wh * d->wh, wp = ((size_t)d->w + d->ww - 1) / d->ww * d->ww;
+  const size_t grid = (((size_t)d->bs * d->h * d->w - 1) * d->grid_ld + d->c) * dt_size(d->dt);
+  const size_t win = (((size_t)d->bs * hp * wp - 1) * d->win_ld + d->c) * dt_size(d->dt);
+  h->src.push_back(d->dir == DFX_WINDOW_PARTITION ? grid : win);
+  h->dst = d->dir == DFX_WINDOW_PARTITION ? win : grid;
+  *out = reinterpret_cast<dfx_window_t *>(h);
+  return DFX_OK;
+}
+int dfx_window_submit(dfx_window_t *h, const void *src, void *dst, dfx_stream_t s) { return submit1(h, "dfx_window_submit", src, dst, s); }
+int dfx_window_destroy(dfx_window_t *h) { return destroy_handle(h); }
+
 // ---- token linear layer: one read (src), one write (dst); set_weights reads the borrowed weights and bias ----
 int dfx_linear_create(const dfx_linear_desc *d, dfx_linear_t **out) {
   if (!d || !out || d->rows < 1 || d->k < 1 || d->n < 1 || d->src_ld < d->k || d->dst_ld < d->n) return fail(DFX_ERR_INVALID, "bad linear descriptor");

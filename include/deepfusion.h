@@ -497,6 +497,28 @@ std::unique_ptr<op> patch_embed(const std::unique_ptr<memory> &src, const std::u
                                 const std::vector<float> &table = {}, int tok_offset = 0,
                                 const std::vector<u8> &prefix = {});
 
+// ---- extension: window partition / reverse of a token grid (dfx_window_* in dfx.h): what a Swin block needs around its
+// attention(), and the gather of Swin's patch merging.  grid: an nhwc tensor {bs, C, h, w} of any of the four data types, every
+// pixel a token of C channels of which the first c_valid take part (0: all of the narrower tensor).  windows: an nhwc tensor
+// {bs, C', H, W} of the same data type with H * W = hp * wp, hp = ceil(h / wh) * wh, wp = ceil(w / ww) * ww, read as bs * nW * wh *
+// ww rows of C' channels: window (wy, wx) of an image is its matrix wy * (wp / ww) + wx, in-window token (iy, ix) its row iy * ww
+// + ix, or ix * wh + iy with col_major (patch merging's x0, x1, x2, x3 order: a 2 x 2 col_major partition into C' = C reads as one
+// row of 4 C per window).  Official Swin's mapping: pad to hp x wp, roll by (-shift_y, -shift_x), cut; window_partition() fills
+// the pad tokens with pad_value (a 32-bit pattern, its low byte for u8 / s8), window_reverse() is the exact inverse and reads
+// no pad token.  Bytes are moved, never converted; channels from c_valid on are neither read nor written (UNDEFINED on the
+// host afterwards, as layer_norm()'s pad channels).  src must not be dst.  submit / submit_async / wait and
+// DEEPFUSION_DEVICES sharding over the batch are patch_embed()'s.  Not built: a fused residual add on reverse, nchw, data
+// type conversion, overlapping windows. ----
+struct window_shape {
+  int wh, ww;
+  int shift_y, shift_x;
+  bool col_major;
+};
+std::unique_ptr<op> window_partition(const std::unique_ptr<memory> &grid, std::unique_ptr<memory> &windows,
+                                     window_shape shape, uint32_t pad_value = 0, int c_valid = 0);
+std::unique_ptr<op> window_reverse(const std::unique_ptr<memory> &windows, std::unique_ptr<memory> &grid,
+                                   window_shape shape, int c_valid = 0);
+
 // ---- extension: batched int8 matrix product of two DEVICE tensors (dfx_bmm_* in dfx.h): the multiply whose second operand is
 // not a weight -- Q.K^T and P.V of an attention / non-local block, a correlation layer.  a (u8 / s8), b (s8) and c (u8 / s8 /
 // s32 / f32) are tensors of any dims; `shape` says where the matrices lie in them, in ELEMENTS from each tensor's first:

@@ -1316,6 +1316,71 @@ typedef struct dfx_lnorm_info {
 } dfx_lnorm_info;
 typedef struct dfx_lnorm dfx_lnorm_t;
 
+/* ---- window partition / reverse of an NHWC token grid: what turns a {bs, h, w, C} map into the windows a Swin block attends
+ *      over and back (with the cyclic shift of SW-MSA and the padding of maps that are no multiple of the window), Swin's patch
+ *      merging gather (a 2 x 2 partition, column-major), depth-to-space (Swin-UNet's patch expanding) and space-to-depth (YOLO's
+ *      reorg / Focus).  Data movement only: bytes are moved, never converted; no arithmetic, no requant route.
+ *
+ *      Two row matrices of ONE dtype (u8 / s8 / s32 / f32):
+ *        grid side    bs * h * w tokens of c valid elements; token (b, y, x) is row (b * h + y) * w + x; rows grid_ld >= c
+ *                     elements apart.
+ *        window side  bs * nW * wh * ww tokens, rows win_ld >= c elements apart, with hp = ceil(h / wh) * wh,
+ *                     wp = ceil(w / ww) * ww, nW = (hp / wh) * (wp / ww).  Window (b, wy, wx) is matrix b * nW + wy * (wp / ww)
+ *                     + wx: what attention_strides(bs * nW, heads, wh * ww, d, ld) and a logit bias of period0 = nW expect.
+ *                     In-window token (iy, ix) is row iy * ww + ix for DFX_WINDOW_ROW_MAJOR and ix * wh + iy for
+ *                     DFX_WINDOW_COL_MAJOR (patch merging's x0, x1, x2, x3 order: with wh = ww = 2 and win_ld = c the four rows
+ *                     of a window read as one row of 4 c).
+ *      The mapping is official Swin's: pad to hp x wp, then torch.roll(-shift).  The window-side token at padded coordinates
+ *      (Y, X) = (wy * wh + iy, wx * ww + ix) corresponds to grid (y, x) = ((Y + shift_y) mod hp, (X + shift_x) mod wp); it is a
+ *      PAD TOKEN when y >= h or x >= w.
+ *        DFX_WINDOW_PARTITION (grid -> window): the c elements of every window-side token are written exactly once; pad tokens
+ *                     get pad_value, a 32-bit pattern whose low byte is used for 1-byte dtypes (a u8 zero point).
+ *        DFX_WINDOW_REVERSE (window -> grid): the exact inverse; every grid token is written exactly once, pad tokens are not
+ *                     read and pad_value is ignored.
+ *      On either side columns c .. ld-1 are never read or written.  Limits: bs >= 1; h, w in 1 .. 65535; wh, ww in 1 .. 255 (a
+ *      window larger than the image is all padding beyond the image); 0 <= shift_y < hp, 0 <= shift_x < wp; hp * wp <= 2^22;
+ *      bs * hp * wp * max(grid_ld, win_ld) <= 2^40.  All byte offsets are 64-bit.
+ *      Shift, padding, order and direction exist only in ONE int32 table of the destination's rows within one image, built on the
+ *      host with exact integer arithmetic (csrc/window_plan.h) and uploaded at create: both kernels are row gathers with contiguous
+ *      stores, dst row (b, r) <- src row b * src_rows_per_image + map[r].
+ *      Not built: a fused scaled residual add on reverse, a row map inside dfx_attn / dfx_linear that would make the two passes
+ *      disappear, NCHW, dtype conversion, overlapping windows (neighbourhood attention), hp * wp > 2^22.  Parity unpinned: the
+ *      reference has no such op. ---- */
+enum { DFX_WINDOW_PARTITION = 0, DFX_WINDOW_REVERSE = 1 };
+enum { DFX_WINDOW_ROW_MAJOR = 0, DFX_WINDOW_COL_MAJOR = 1 };
+enum { DFX_WINDOW_MAX_HW = 65535, DFX_WINDOW_MAX_WIN = 255, DFX_WINDOW_MAX_PADDED = 1 << 22 };
+typedef struct dfx_window_desc {
+  int32_t dir;                 /* DFX_WINDOW_PARTITION | DFX_WINDOW_REVERSE */
+  int32_t dt;                  /* U8 | S8 | S32 | F32, of both sides */
+  int32_t bs, h, w, c;
+  int32_t wh, ww, shift_y, shift_x;
+  int32_t order;               /* DFX_WINDOW_ROW_MAJOR | DFX_WINDOW_COL_MAJOR */
+  int64_t grid_ld, win_ld;     /* >= c, in elements */
+  uint32_t pad_value;          /* PARTITION: what pad tokens are filled with */
+  int32_t force_path;          /* -1 auto | DFX_WINDOW_ROW | DFX_WINDOW_GENERIC */
+} dfx_window_desc;
+enum {  /* dfx_window_info.path */
+  DFX_WINDOW_ROW = 0,          /* window_row_kernel (window.cuh): a lane moves one 16-byte group, c * esize / 16 consecutive lanes
+                                  per token (any count: 96 channels -> 6), consecutive lanes run on into the next destination row,
+                                  so stores are contiguous and loads contiguous in runs of at least one token; four groups per
+                                  lane and trip, all loaded before the first store; no LDS.  Class: c * esize, grid_ld * esize and
+                                  win_ld * esize multiples of 16; pointers 16-byte aligned (checked per submit: others take the
+                                  generic kernel for that submit). */
+  DFX_WINDOW_GENERIC = 1       /* one thread per element, any alignment and pitch, grid-stride.  It defines the bits. */
+};
+/* DFX_WINDOW_AUTO_NOTE: UNMEASURED.  The row kernel has not been timed on an MI355X yet (tools/bench_window is the
+ * instrument; profiles/window/README.md), so auto takes DFX_WINDOW_GENERIC everywhere and DFX_WINDOW_ROW runs only where
+ * force_path asks for it -- dfx_lnorm's precedent: no path is on auto before a measurement puts it there. */
+typedef struct dfx_window_info {
+  int32_t path;                /* the handle's plan (a misaligned submit falls back without changing it) */
+  int32_t grid, block;
+  int32_t device;
+  uint64_t algorithmic_bytes;  /* valid bytes read + valid bytes written + the map: PARTITION bs * (h * w + hp * wp) * c * esize +
+                                  4 * hp * wp, REVERSE 2 * bs * h * w * c * esize + 4 * h * w */
+  char kernel_name[96];        /* direction, dtype, lanes per token: "window_row<partition,s8,l6>", "window_generic<reverse,f32>" */
+} dfx_window_info;
+typedef struct dfx_window dfx_window_t;
+
 /* ---- int8 token linear layer over a ROW MATRIX: the four weight multiplies of a transformer block (QKV projection, output
  *      projection, fc1 + GELU, fc2) between dfx_lnorm, dfx_attn and dfx_wsum, weight-stationary.
  *
@@ -2099,6 +2164,23 @@ int dfx_patchembed_submit_host(dfx_patchembed_t *h, const void *src_host, void *
 int dfx_patchembed_query(const dfx_patchembed_t *h, dfx_patchembed_info *info);
 int dfx_patchembed_destroy(dfx_patchembed_t *h);
 
+/* ---- window partition / reverse (dfx_window_desc above).  The descriptor is validated before anything touches a device, in
+ *      this order: DFX_ERR_INVALID for a bad dir, a bad dtype, bs < 1, h or w outside 1 .. 65535, c < 1, wh or ww outside
+ *      1 .. 255, a bad order, shift_y outside 0 .. hp-1, shift_x outside 0 .. wp-1, grid_ld < c, win_ld < c, a bad force_path,
+ *      hp * wp > 2^22, bs * hp * wp * max(grid_ld, win_ld) > 2^40; then DFX_ERR_UNSUPPORTED only for force_path =
+ *      DFX_WINDOW_ROW outside that class.  "No HIP device" is reported only for a valid descriptor.  create builds the row map
+ *      on the host and uploads it.
+ *      submit: src is the grid side and dst the window side for PARTITION, the other way round for REVERSE.  Asynchronous on
+ *      `s`; ONE launch with its own arguments; it never writes to the handle: one handle serves several streams and host
+ *      threads at once.  DFX_ERR_INVALID, with nothing launched, for a null pointer, a pointer of a 4-byte dtype that is not
+ *      4-byte aligned and a dst whose extent overlaps src's (a permutation cannot run in place).  Pointers that are not 16-byte
+ *      aligned take the generic kernel for that submit.
+ *      Tuning switch: DFX_WINDOW_GRID=n caps the grid of either kernel.  No CPU fallback.  Auto: DFX_WINDOW_AUTO_NOTE. ---- */
+int dfx_window_create(const dfx_window_desc *desc, dfx_window_t **out);
+int dfx_window_submit(dfx_window_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s);
+int dfx_window_query(const dfx_window_t *h, dfx_window_info *info);
+int dfx_window_destroy(dfx_window_t *h);
+
 /* ---- depthwise + pointwise conv (dfx_dwpw_desc above).  The descriptor is validated before anything touches a
  *      device: DFX_ERR_INVALID for what dfx_dwconv_create rejects for stage 0 (sizes, strides, padding, window,
  *      output size, pixel count), a non-positive oc, a bad dtype / round mode / nscales0 / nscales1 / force_path, and
@@ -2219,6 +2301,8 @@ int dfx_debug_patchembed_launches(int64_t out[2]);
 /* the patch embedding's one stage as the handle's weights and table prove it now, same numbering (0 exact, 1 fast; the generic
  * path is always exact).  DFX_ERR_STATE before set_weights. */
 int dfx_debug_patchembed_requant(const dfx_patchembed_t *h, int32_t out[1]);
+/* the same for dfx_window_submit: out[DFX_WINDOW_ROW], out[DFX_WINDOW_GENERIC] */
+int dfx_debug_window_launches(int64_t out[2]);
 
 #ifdef __cplusplus
 }

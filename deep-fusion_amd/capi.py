@@ -619,88 +619,71 @@ def set_tuning(key, value):
     _check(lib().dfx_debug_set_tuning(key.encode(), None if value is None else str(value).encode()))
 
 
+def _launches(op, *paths):
+    """dfx_debug_<op>_launches' counters in the order of `paths` (the op's path constants index them)"""
+    v = (ctypes.c_int64 * len(paths))()
+    _check(getattr(lib(), "dfx_debug_%s_launches" % op)(v))
+    return tuple(v[p] for p in paths)
+
+
 def resize_launches():
     """(band, generic): dfx_resize_submit calls of this process that launched each kernel (dfx_debug_resize_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_resize_launches(v))
-    return v[RESIZE_BAND], v[RESIZE_GENERIC]
+    return _launches("resize", RESIZE_BAND, RESIZE_GENERIC)
 
 
 def wsum_launches():
     """(vec, generic): dfx_wsum_submit calls of this process that launched each kernel (dfx_debug_wsum_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_wsum_launches(v))
-    return v[WSUM_VEC], v[WSUM_GENERIC]
+    return _launches("wsum", WSUM_VEC, WSUM_GENERIC)
 
 
 def head_launches():
     """(pixel, row, generic): dfx_head_submit calls of this process that launched each kernel (dfx_debug_head_launches)"""
-    v = (ctypes.c_int64 * 3)()
-    _check(lib().dfx_debug_head_launches(v))
-    return v[HEAD_PIXEL], v[HEAD_ROW], v[HEAD_GENERIC]
+    return _launches("head", HEAD_PIXEL, HEAD_ROW, HEAD_GENERIC)
 
 
 def select_launches():
     """(hist, generic): dfx_select_submit calls of this process that ran on each path (dfx_debug_select_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_select_launches(v))
-    return v[SELECT_HIST], v[SELECT_GENERIC]
+    return _launches("select", SELECT_HIST, SELECT_GENERIC)
 
 
 def nms_launches():
     """(mask, generic): dfx_nms_submit calls of this process that ran on each path (dfx_debug_nms_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_nms_launches(v))
-    return v[NMS_MASK], v[NMS_GENERIC]
+    return _launches("nms", NMS_MASK, NMS_GENERIC)
 
 
 def roialign_launches():
     """(tile, generic): dfx_roialign_submit calls of this process that launched each kernel (dfx_debug_roialign_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_roialign_launches(v))
-    return v[ROIALIGN_TILE], v[ROIALIGN_GENERIC]
+    return _launches("roialign", ROIALIGN_TILE, ROIALIGN_GENERIC)
 
 
 def bmm_launches():
     """(mfma, generic): dfx_bmm_submit calls of this process that launched each kernel (dfx_debug_bmm_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_bmm_launches(v))
-    return v[BMM_MFMA], v[BMM_GENERIC]
+    return _launches("bmm", BMM_MFMA, BMM_GENERIC)
 
 
 def attn_launches():
     """(fused, chain): dfx_attn_submit calls of this process that ran on each path (dfx_debug_attn_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_attn_launches(v))
-    return v[ATTN_FUSED], v[ATTN_CHAIN]
+    return _launches("attn", ATTN_FUSED, ATTN_CHAIN)
 
 
 def lnorm_launches():
     """(row, generic): dfx_lnorm_submit calls of this process that launched each kernel (dfx_debug_lnorm_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_lnorm_launches(v))
-    return v[LNORM_ROW], v[LNORM_GENERIC]
+    return _launches("lnorm", LNORM_ROW, LNORM_GENERIC)
 
 
 def linear_launches():
     """(tile, generic): dfx_linear_submit calls of this process that launched each kernel (dfx_debug_linear_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_linear_launches(v))
-    return v[LINEAR_TILE], v[LINEAR_GENERIC]
+    return _launches("linear", LINEAR_TILE, LINEAR_GENERIC)
 
 
 def patchembed_launches():
     """(tile, generic): dfx_patchembed_submit calls of this process that launched each kernel (dfx_debug_patchembed_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_patchembed_launches(v))
-    return v[PATCHEMBED_TILE], v[PATCHEMBED_GENERIC]
+    return _launches("patchembed", PATCHEMBED_TILE, PATCHEMBED_GENERIC)
 
 
 def window_launches():
     """(row, generic): dfx_window_submit calls of this process that launched each kernel (dfx_debug_window_launches)"""
-    v = (ctypes.c_int64 * 2)()
-    _check(lib().dfx_debug_window_launches(v))
-    return v[WINDOW_ROW], v[WINDOW_GENERIC]
+    return _launches("window", WINDOW_ROW, WINDOW_GENERIC)
 
 
 def _pair(v):

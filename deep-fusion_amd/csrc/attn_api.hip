@@ -11,11 +11,10 @@
 #include <new>
 #include <vector>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "attn.cuh"
 #include "attn_plan.h"
 #include "bias_plan.h"
-#include "requant_host.h"
 
 namespace dfx {
 int launch_attn_fused(const AttnArgs &a, int grid, int lds, hipStream_t s, int mode, bool fast_logits, bool fast_context, bool bias);
@@ -58,12 +57,7 @@ struct dfx_attn {
 namespace {
 
 // submits since the library was loaded, by the path that ran; process-wide (dfx_debug_attn_launches)
-std::atomic<long long> g_launches[2];
-
-long long grid_cap() {
-  const char *e = tuning_value("DFX_ATTN_GRID");  // testing aid
-  return e ? std::max(1ll, atoll(e)) : 0;
-}
+LaunchCounts<2> g_launches;
 
 // (AUTO RULE with a logit bias -- include/dfx.h DFX_ATTN_AUTO_NOTE, DESIGN.md section 4.22, profiles/attn/bench_attn_bias.txt: the
 // biased fused kernel beat the biased chain at every point of the unbiased rule's box and lost where the unbiased one loses,
@@ -98,6 +92,17 @@ void drop_chain(dfx_attn *h) {
   h->scratch = nullptr;
 }
 
+void release(dfx_attn *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  drop_chain(h);
+  (void)hipFree(h->d_table);
+  (void)hipFree(h->d_oscale);
+  (void)hipFree(h->d_bias);
+  h->order.destroy();
+  delete h;
+}
+
 // the three ops and the scratch for L and P, with the table and the scales the handle has been given so far.  At create, or
 // with order.mu held.  (attn_validate has found the three descriptors valid: tools/attn_plan_check holds it to that.)
 int ensure_chain(dfx_attn *h) {
@@ -129,43 +134,20 @@ int ensure_chain(dfx_attn *h) {
   return DFX_OK;
 }
 
-void release(dfx_attn *h) {
-  drop_chain(h);
-  (void)hipFree(h->d_table);
-  (void)hipFree(h->d_oscale);
-  (void)hipFree(h->d_bias);
-  h->order.destroy();
-  delete h;
-}
-
 }  // namespace
 
 extern "C" {
 
 int dfx_attn_create(const dfx_attn_desc *desc, dfx_attn_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "attn_create: null argument");
-  *out = nullptr;
+  dfx_attn *h = nullptr;
+  int cus = 0;
+  int rc = open_create("attn", desc, out, &h, [](const dfx_attn_desc &d) { return validated("attn", attn_validate, d); }, &cus, release);
+  if (rc) return rc;
   const dfx_attn_desc &d = *desc;
-  const char *why = "";
-  int rc = attn_validate(d, &why);
-  if (rc) return fail(rc, "attn: %s", why);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "attn_create: no HIP device (this library has no CPU path)");
-  dfx_attn *h = new (std::nothrow) dfx_attn();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
-    release(h);
-    return fail(DFX_ERR_HIP, "attn_create: cannot query the device");
-  }
-  const int cus = std::max(1, prop.multiProcessorCount);
   // AUTO RULE (include/dfx.h DFX_ATTN_AUTO_NOTE)
   h->path = attn_path(d);
   h->fused_ok = attn_fused_class(d);
-  h->grid = attn_grid(d, cus, grid_cap());
+  h->grid = attn_grid(d, cus, grid_cap("DFX_ATTN_GRID"));
   h->lds = (int)std::min<long long>(attn_lds_bytes(d), ATTN_LDS_MAX);
   h->dv_pad = (int)(((long long)d.dv + 31) / 32 * 32);
   // the chain where it is the plan; a fused handle makes it at the first submit that falls back (a misaligned q, k or v),
@@ -318,12 +300,12 @@ int dfx_attn_submit(dfx_attn_t *h, const void *q_dev, const void *k_dev, const v
   if (!h->table_set.load()) return fail(DFX_ERR_STATE, "attn_submit: dfx_attn_set_table not called");
   if (!h->scales_set.load()) return fail(DFX_ERR_STATE, "attn_submit: dfx_attn_set_scales not called");
   const dfx_attn_desc &d = h->d;
-  const unsigned esz = (unsigned)bmm_dt_size(d.dst_dt);
+  const unsigned esz = (unsigned)plan_dt_size(d.dst_dt);
   const uintptr_t pq = (uintptr_t)q_dev, pk = (uintptr_t)k_dev, pv = (uintptr_t)v_dev, po = (uintptr_t)o_dev;
   if (po % esz) return fail(DFX_ERR_INVALID, "attn_submit: o is not aligned to its element");
   const dfx_bmm_desc bl = attn_bmm_logits(d), bo = attn_bmm_context(d);
   const unsigned long long qbytes = bmm_a_elems(bl), kbytes = bmm_b_elems(bl), vbytes = bmm_b_elems(bo), obytes = bmm_c_elems(bo) * esz;
-  if (bmm_overlap(po, obytes, pq, qbytes) || bmm_overlap(po, obytes, pk, kbytes) || bmm_overlap(po, obytes, pv, vbytes))
+  if (plan_overlap(po, obytes, pq, qbytes) || plan_overlap(po, obytes, pk, kbytes) || plan_overlap(po, obytes, pv, vbytes))
     return fail(DFX_ERR_INVALID, "attn_submit: o overlaps q, k or v");
   DeviceGuard dg(h->device);
   // 16-byte loads need aligned operands: others take the chain for this submit
@@ -351,38 +333,28 @@ int dfx_attn_submit(dfx_attn_t *h, const void *q_dev, const void *k_dev, const v
     if (rc == DFX_OK) rc = h->order.leave((hipStream_t)s);
     if (rc) return rc;
   }
-  g_launches[path].fetch_add(1, std::memory_order_relaxed);
+  g_launches.hit(path);
   return DFX_OK;
 }
 
 // test hook: how many submits have run on each path so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_attn_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_attn_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_attn_launches(int64_t out[2]) { return g_launches.read("attn", out); }
 
 int dfx_attn_query(const dfx_attn_t *h, dfx_attn_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "attn_query: null argument");
-  memset(info, 0, sizeof(*info));
+  if (const int rc = open_query("attn", h, info)) return rc;
   const bool fused = h->path == DFX_ATTN_FUSED;
-  info->path = h->path;
   info->grid = fused ? h->grid : 0;
   info->block = fused ? ATTN_THREADS : 0;
   info->lds_bytes = fused ? h->lds : 0;
-  info->device = h->device;
   info->route_logits = h->scales_set.load() ? h->route_l : -1;
   info->route_context = h->scales_set.load() ? h->route_o : -1;
   info->scratch_bytes = h->chain_ready.load() ? attn_scratch_bytes(h->d) : 0;
   info->algorithmic_ops = attn_algorithmic_ops(h->d);
   info->algorithmic_bytes = attn_algorithmic_bytes(h->d) + (h->bias_set ? bias_distinct_bytes(attn_bmm_logits(h->d), h->bias) : 0);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_attn_destroy(dfx_attn_t *h) {
-  if (!h) return DFX_OK;
-  DeviceGuard dg(h->device);
   release(h);
   return DFX_OK;
 }

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "bmm_plan.h"
+#include "plan_common.h"
 #include "head_plan.h"
 
 namespace dfx {
@@ -24,11 +25,10 @@ constexpr int ATTN_GRID_PER_CU = 8;              // workgroups per CU at most; t
 constexpr int ATTN_V_LDS = BMM_NN_LDS;           // the four waves' transposed V images (bmm.cuh's), reused for the split-key sums
 constexpr int ATTN_LDS_MAX = 160 * 1024;
 
-inline long long attn_up16(long long x) { return (x + 15) / 16 * 16; }
 inline long long attn_matrices(const dfx_attn_desc &d) { return (long long)d.batch0 * d.batch1; }
 // leading dimension (bytes = elements) of the chain's L and P scratch; the fused strip's rows are 16 longer
-inline long long attn_ldl(const dfx_attn_desc &d) { return attn_up16(d.tk); }
-inline long long attn_pitch(const dfx_attn_desc &d) { return attn_up16(d.tk) + 16; }
+inline long long attn_ldl(const dfx_attn_desc &d) { return plan_up16(d.tk); }
+inline long long attn_pitch(const dfx_attn_desc &d) { return plan_up16(d.tk) + 16; }
 inline unsigned long long attn_scratch_bytes(const dfx_attn_desc &d) {  // L and P together
   return 2ull * (unsigned long long)attn_matrices(d) * (unsigned long long)d.tq * (unsigned long long)attn_ldl(d);
 }
@@ -166,7 +166,7 @@ inline unsigned long long attn_algorithmic_bytes(const dfx_attn_desc &d) {
   const unsigned long long gk = (unsigned long long)(d.k_s0 == 0 ? 1 : d.batch0) * (unsigned long long)(d.k_s1 == 0 ? 1 : d.batch1);
   const unsigned long long gv = (unsigned long long)(d.v_s0 == 0 ? 1 : d.batch0) * (unsigned long long)(d.v_s1 == 0 ? 1 : d.batch1);
   return gq * (unsigned long long)d.tq * d.d + gk * (unsigned long long)d.tk * d.d + gv * (unsigned long long)d.tk * d.dv +
-         (unsigned long long)attn_matrices(d) * d.tq * d.dv * (unsigned)bmm_dt_size(d.dst_dt);
+         (unsigned long long)attn_matrices(d) * d.tq * d.dv * (unsigned)plan_dt_size(d.dst_dt);
 }
 
 }  // namespace dfx

@@ -4,18 +4,15 @@
 // choice of the kernel per submit, launches.  The kernels are in bmm.cuh / bmm.hip.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <atomic>
 #include <cstdio>
-#include <cstring>
 #include <new>
 #include <vector>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "bmm.cuh"
 #include "bmm_plan.h"
 #include "bias_plan.h"
-#include "requant_host.h"
 
 namespace dfx {
 int launch_bmm_mfma(const BmmArgs &a, const BmmBiasArgs *bias, int grid, hipStream_t s, bool fast);
@@ -45,14 +42,17 @@ struct dfx_bmm {
 
 namespace {
 
+void release(dfx_bmm *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  (void)hipFree(h->d_scale);
+  (void)hipFree(h->d_bias);
+  delete h;
+}
+
 // launches since the library was loaded, by the kernel that ran; process-wide, because submit does not write to the
 // handle (dfx_debug_bmm_launches)
-std::atomic<long long> g_launches[2];
-
-long long grid_cap() {
-  const char *e = tuning_value("DFX_BMM_GRID");  // testing aid
-  return e ? std::max(1ll, atoll(e)) : 0;
-}
+LaunchCounts<2> g_launches;
 
 void set_name(dfx_bmm *h) {
   const dfx_bmm_desc &d = h->d;
@@ -77,34 +77,20 @@ void prove_route(dfx_bmm *h) {
 extern "C" {
 
 int dfx_bmm_create(const dfx_bmm_desc *desc, dfx_bmm_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "bmm_create: null argument");
-  *out = nullptr;
+  dfx_bmm *h = nullptr;
+  int cus = 0;
+  const int rc = open_create("bmm", desc, out, &h, [](const dfx_bmm_desc &d) { return validated("bmm", bmm_validate, d); }, &cus, release);
+  if (rc) return rc;
   const dfx_bmm_desc &d = *desc;
-  const char *why = "";
-  const int rc = bmm_validate(d, &why);
-  if (rc) return fail(rc, "bmm: %s", why);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "bmm_create: no HIP device (this library has no CPU path)");
-  dfx_bmm *h = new (std::nothrow) dfx_bmm();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
-    delete h;
-    return fail(DFX_ERR_HIP, "bmm_create: cannot query the device");
-  }
-  const int cus = std::max(1, prop.multiProcessorCount);
   // AUTO RULE (include/dfx.h DFX_BMM_AUTO_NOTE)
   h->path = bmm_path(d);
-  const long long cap = grid_cap();
+  const long long cap = grid_cap("DFX_BMM_GRID");
   h->grid[h->path] = bmm_grid(d, h->path, cus, cap);
   h->grid[DFX_BMM_GENERIC] = bmm_grid(d, DFX_BMM_GENERIC, cus, cap);
   h->n_pad = (int)(((long long)d.n + 31) / 32 * 32);  // (n <= 2^31 - 32: bmm_validate)
   const hipError_t e = hipMalloc((void **)&h->d_scale, (size_t)h->n_pad * sizeof(float));
   if (e != hipSuccess) {
-    delete h;
+    release(h);
     return fail(DFX_ERR_HIP, "bmm_create: scales: %s", hipGetErrorString(e));
   }
   BmmArgs &a = h->args;
@@ -185,11 +171,11 @@ int dfx_bmm_submit(dfx_bmm_t *h, const void *a_dev, const void *b_dev, void *c_d
   if (!h || !a_dev || !b_dev || !c_dev) return fail(DFX_ERR_INVALID, "bmm_submit: null argument");
   if (!h->scales_set.load()) return fail(DFX_ERR_STATE, "bmm_submit: dfx_bmm_set_scales not called");
   const dfx_bmm_desc &d = h->d;
-  const unsigned esz = (unsigned)bmm_dt_size(d.dst_dt);
+  const unsigned esz = (unsigned)plan_dt_size(d.dst_dt);
   const uintptr_t pa = (uintptr_t)a_dev, pb = (uintptr_t)b_dev, pc = (uintptr_t)c_dev;
   if (pc % esz) return fail(DFX_ERR_INVALID, "bmm_submit: c is not aligned to its element");
   const unsigned long long abytes = bmm_a_elems(d), bbytes = bmm_b_elems(d), cbytes = bmm_c_elems(d) * esz;
-  if (bmm_overlap(pc, cbytes, pa, abytes) || bmm_overlap(pc, cbytes, pb, bbytes))
+  if (plan_overlap(pc, cbytes, pa, abytes) || plan_overlap(pc, cbytes, pb, bbytes))
     return fail(DFX_ERR_INVALID, "bmm_submit: c overlaps a or b");
   DeviceGuard dg(h->device);
   // 16-byte loads need aligned operands: others take the generic kernel for this submit, as resize and head do
@@ -203,18 +189,11 @@ int dfx_bmm_submit(dfx_bmm_t *h, const void *a_dev, const void *b_dev, void *c_d
   const BmmBiasArgs *const bp = h->bias_set ? &bias : nullptr;
   const int rc = path == DFX_BMM_MFMA ? launch_bmm_mfma(a, bp, h->grid[path], (hipStream_t)s, h->route != 0)
                                       : launch_bmm_generic(a, bp, h->grid[path], (hipStream_t)s);
-  if (rc != 0) return fail(DFX_ERR_UNSUPPORTED, "bmm_submit: no kernel instance for this op");
-  HIP_TRY(hipGetLastError());
-  g_launches[path].fetch_add(1, std::memory_order_relaxed);
-  return DFX_OK;
+  return g_launches.launched("bmm", rc, path);
 }
 
 // test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_bmm_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_bmm_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_bmm_launches(int64_t out[2]) { return g_launches.read("bmm", out); }
 
 // test hook: the requant route the last dfx_bmm_set_scales proved (numbering of dfx_debug_conv_requant)
 int dfx_debug_bmm_requant(const dfx_bmm_t *h, int32_t out[1]) {
@@ -225,25 +204,17 @@ int dfx_debug_bmm_requant(const dfx_bmm_t *h, int32_t out[1]) {
 }
 
 int dfx_bmm_query(const dfx_bmm_t *h, dfx_bmm_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "bmm_query: null argument");
-  memset(info, 0, sizeof(*info));
-  info->path = h->path;
+  if (const int rc = open_query("bmm", h, info)) return rc;
   info->grid = h->grid[h->path];
   info->block = BMM_THREADS;
   info->lds_bytes = bmm_lds_bytes(h->d, h->path);
-  info->device = h->device;
   info->algorithmic_ops = bmm_algorithmic_ops(h->d);
   info->algorithmic_bytes = bmm_algorithmic_bytes(h->d) + (h->bias_set ? bias_distinct_bytes(h->d, h->bias) : 0);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_bmm_destroy(dfx_bmm_t *h) {
-  if (!h) return DFX_OK;
-  DeviceGuard dg(h->device);
-  (void)hipFree(h->d_scale);
-  (void)hipFree(h->d_bias);
-  delete h;
+  release(h);
   return DFX_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "../../include/dfx.h"
+#include "plan_common.h"
 
 namespace dfx {
 
@@ -24,7 +25,6 @@ constexpr int BMM_NN_PITCH = 48;                 // bytes per transposed B row i
 constexpr int BMM_NN_LDS = BMM_WAVES * 2 * 32 * BMM_NN_PITCH;   // two buffers per wave
 
 inline bool bmm_dt_ok(int dt) { return dt == DFX_F32 || dt == DFX_S32 || dt == DFX_S8 || dt == DFX_U8; }
-inline int bmm_dt_size(int dt) { return (dt == DFX_F32 || dt == DFX_S32) ? 4 : 1; }
 inline long long bmm_b_rows(const dfx_bmm_desc &d) { return d.trans_b ? d.n : d.k; }
 inline long long bmm_b_cols(const dfx_bmm_desc &d) { return d.trans_b ? d.k : d.n; }
 
@@ -162,11 +162,8 @@ inline unsigned long long bmm_algorithmic_bytes(const dfx_bmm_desc &d) {
   const unsigned long long ga = (unsigned long long)(d.a_s0 == 0 ? 1 : d.batch0) * (unsigned long long)(d.a_s1 == 0 ? 1 : d.batch1);
   const unsigned long long gb = (unsigned long long)(d.b_s0 == 0 ? 1 : d.batch0) * (unsigned long long)(d.b_s1 == 0 ? 1 : d.batch1);
   return ga * (unsigned long long)d.m * d.k + gb * (unsigned long long)d.k * d.n +
-         (unsigned long long)bmm_matrices(d) * d.m * d.n * (unsigned)bmm_dt_size(d.dst_dt);
+         (unsigned long long)bmm_matrices(d) * d.m * d.n * (unsigned)plan_dt_size(d.dst_dt);
 }
 
-inline bool bmm_overlap(uintptr_t a, unsigned long long abytes, uintptr_t b, unsigned long long bbytes) {
-  return a < b + bbytes && b < a + abytes;
-}
 
 }  // namespace dfx

@@ -1,5 +1,6 @@
 // dfx_internal.h -- the few host-side helpers the translation units behind include/dfx.h share (every *_api.hip includes
-// it, directly or through weighted_op.h).  Not installed, not part of the C ABI.  What needs no HIP is in requant_host.h.
+// it, directly or through weighted_op.h or path_op.h).  Not installed, not part of the C ABI.  What needs no HIP is in
+// requant_host.h and plan_common.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

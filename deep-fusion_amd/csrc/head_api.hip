@@ -3,14 +3,10 @@
 // per submit (all planned in head_plan.h), launches.  The kernels are in head.cuh.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
 #include <cstdio>
-#include <cstring>
-#include <new>
 #include <string>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "head.cuh"
 #include "head_plan.h"
 
@@ -31,48 +27,42 @@ struct dfx_head {
 
 namespace {
 
+void release(dfx_head *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  (void)hipFree(h->d_table);
+  delete h;
+}
+
 // launches since the library was loaded, by the kernel that ran; process-wide, because submit does not write to the
 // handle (dfx_debug_head_launches)
-std::atomic<long long> g_launches[3];
-
-const char *dt_name(int dt) { return dt == DFX_F32 ? "f32" : dt == DFX_S32 ? "s32" : dt == DFX_S8 ? "s8" : "u8"; }
-
-long long grid_cap() {
-  const char *e = tuning_value("DFX_HEAD_GRID");  // testing aid
-  return e ? std::max(1ll, atoll(e)) : 0;
-}
+LaunchCounts<3> g_launches;
 
 }  // namespace
 
 extern "C" {
 
 int dfx_head_create(const dfx_head_desc *desc, dfx_head_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "head_create: null argument");
-  *out = nullptr;
+  dfx_head *h = nullptr;
+  const int rc = open_create("head", desc, out, &h, [](const dfx_head_desc &d) {
+    if (const int bad = validated("head", head_validate, d)) return bad;
+    if (d.force_path != -1 && !head_in_class(d, d.force_path))
+      return fail(DFX_ERR_UNSUPPORTED, "head_create: descriptor outside the forced path's class (pixel: 1-byte src, k = 1 or softmax, "
+                                       "src_ld a multiple of 16 up to 160; row: src_ld * element size a multiple of 16)");
+    return (int)DFX_OK;
+  });
+  if (rc) return rc;
   const dfx_head_desc &d = *desc;
-  const char *why = "";
-  int rc = head_validate(d, &why);
-  if (rc) return fail(rc, "head: %s", why);
-  if (d.force_path != -1 && !head_in_class(d, d.force_path))
-    return fail(DFX_ERR_UNSUPPORTED, "head_create: descriptor outside the forced path's class (pixel: 1-byte src, k = 1 or softmax, "
-                                     "src_ld a multiple of 16 up to 160; row: src_ld * element size a multiple of 16)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "head_create: no HIP device (this library has no CPU path)");
-  dfx_head *h = new (std::nothrow) dfx_head();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   // AUTO RULE (include/dfx.h DFX_HEAD_AUTO_NOTE)
   h->path = head_path(d);
   if (d.mode == DFX_HEAD_SOFTMAX) {
     const hipError_t e = hipMalloc((void **)&h->d_table, HEAD_TABLE_BYTES);
     if (e != hipSuccess) {
-      delete h;
+      release(h);
       return fail(DFX_ERR_HIP, "head_create: table: %s", hipGetErrorString(e));
     }
   }
-  const long long cap = grid_cap();
+  const long long cap = grid_cap("DFX_HEAD_GRID");
   h->grid[h->path] = head_grid(d.rows, h->path, cap);
   h->grid[DFX_HEAD_GENERIC] = head_grid(d.rows, DFX_HEAD_GENERIC, cap);
   std::string name = h->path == DFX_HEAD_PIXEL ? "head_pixel<" : h->path == DFX_HEAD_ROW ? "head_row<" : "head_generic<";
@@ -101,13 +91,13 @@ int dfx_head_submit(dfx_head_t *h, const void *src_dev, void *idx_or_dst_dev, vo
   const bool softmax = d.mode == DFX_HEAD_SOFTMAX;
   if (softmax && !h->table_set) return fail(DFX_ERR_STATE, "head_submit: dfx_head_set_table not called");
   if (softmax && val_or_null_dev) return fail(DFX_ERR_INVALID, "head_submit: a softmax has no val");
-  const int ssz = head_dt_size(d.src_dt), osz = head_dt_size(d.dst_dt);
+  const int ssz = plan_dt_size(d.src_dt), osz = plan_dt_size(d.dst_dt);
   const uintptr_t src = (uintptr_t)src_dev, out = (uintptr_t)idx_or_dst_dev, val = (uintptr_t)val_or_null_dev;
   if (src % ssz || out % osz || val % ssz) return fail(DFX_ERR_INVALID, "head_submit: a pointer is not aligned to its element");
-  const unsigned long long sbytes = head_extent(d.rows, d.src_ld, d.c, ssz);
-  const unsigned long long obytes = head_extent(d.rows, head_out_ld(d), head_out_cols(d), osz);
-  const unsigned long long vbytes = val ? head_extent(d.rows, d.idx_ld, d.k, ssz) : 0;
-  if (head_overlap(src, sbytes, out, obytes) || (val && (head_overlap(src, sbytes, val, vbytes) || head_overlap(out, obytes, val, vbytes))))
+  const unsigned long long sbytes = plan_extent(d.rows, d.src_ld, d.c, ssz);
+  const unsigned long long obytes = plan_extent(d.rows, head_out_ld(d), head_out_cols(d), osz);
+  const unsigned long long vbytes = val ? plan_extent(d.rows, d.idx_ld, d.k, ssz) : 0;
+  if (plan_overlap(src, sbytes, out, obytes) || (val && (plan_overlap(src, sbytes, val, vbytes) || plan_overlap(out, obytes, val, vbytes))))
     return fail(DFX_ERR_INVALID, "head_submit: an output overlaps src or the other output");
   DeviceGuard dg(h->device);
   // 16-byte loads need aligned buffers: others take the generic kernel for this submit, as wsum does
@@ -122,37 +112,23 @@ int dfx_head_submit(dfx_head_t *h, const void *src_dev, void *idx_or_dst_dev, vo
   a.src_dt = d.src_dt; a.out_dt = d.dst_dt;
   a.out_vec = softmax && out % 16 == 0 && ((long long)d.dst_ld * osz) % 16 == 0;
   a.out_scale = d.out_scale;
-  if (launch_head(a, path, softmax, h->grid[path], (hipStream_t)s) != 0) return fail(DFX_ERR_UNSUPPORTED, "head_submit: no kernel instance for this op");
-  HIP_TRY(hipGetLastError());
-  g_launches[path].fetch_add(1, std::memory_order_relaxed);
-  return DFX_OK;
+  return g_launches.launched("head", launch_head(a, path, softmax, h->grid[path], (hipStream_t)s), path);
 }
 
 // test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_head_launches(int64_t out[3]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_head_launches: null argument");
-  for (int k = 0; k < 3; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_head_launches(int64_t out[3]) { return g_launches.read("head", out); }
 
 int dfx_head_query(const dfx_head_t *h, dfx_head_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "head_query: null argument");
-  memset(info, 0, sizeof(*info));
-  info->path = h->path;
+  if (const int rc = open_query("head", h, info)) return rc;
   info->grid = h->grid[h->path];
   info->block = HEAD_THREADS;
   info->lds_bytes = head_lds_bytes(h->d, h->path);
-  info->device = h->device;
   info->algorithmic_bytes = head_algorithmic_bytes(h->d);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_head_destroy(dfx_head_t *h) {
-  if (!h) return DFX_OK;
-  DeviceGuard dg(h->device);
-  (void)hipFree(h->d_table);
-  delete h;
+  release(h);
   return DFX_OK;
 }
 

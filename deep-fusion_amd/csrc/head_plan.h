@@ -1,6 +1,6 @@
 // head_plan.h -- host-only, plain C++: what the net head (dfx_head_* of include/dfx.h: channel top-k / argmax and softmax
 // over a row matrix) decides before a kernel runs: the descriptor's validation, which kernel classes a descriptor is in,
-// the auto rule, whether a softmax table is admitted, the extent of every buffer (for the overlap check) and the grid.
+// the auto rule, whether a softmax table is admitted and the grid (buffer extents and the overlap test: plan_common.h).
 // No HIP in here, so that it can be built and run on its own (tools/head_plan_check.cc, under the host sanitizers).
 #pragma once
 
@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/dfx.h"
+#include "plan_common.h"
 
 namespace dfx {
 
@@ -20,7 +21,6 @@ constexpr int HEAD_TABLE_BYTES = 256 * 4;
 constexpr int HEAD_ROW_AUTO_MIN_BYTES = 160;        // auto takes the row path from rows of this many bytes on
 
 inline bool head_src_dt_ok(int dt) { return dt == DFX_F32 || dt == DFX_S32 || dt == DFX_S8 || dt == DFX_U8; }
-inline int head_dt_size(int dt) { return (dt == DFX_F32 || dt == DFX_S32) ? 4 : 1; }
 inline bool head_path_ok(int p) { return p == DFX_HEAD_PIXEL || p == DFX_HEAD_ROW || p == DFX_HEAD_GENERIC; }
 
 // elements between rows of the first output (idx or dst) and the elements of a row that are written
@@ -54,16 +54,16 @@ inline int head_validate(const dfx_head_desc &d, const char **why) {
   if (d.force_path != -1 && !head_path_ok(d.force_path)) return *why = "bad force_path", DFX_ERR_INVALID;
   const long long ld = d.src_ld > head_out_ld(d) ? d.src_ld : head_out_ld(d);  // < 2^31: the quotient is exact
   if (d.rows > HEAD_MAX_ELEMS / ld) return *why = "more than 2^40 elements", DFX_ERR_INVALID;
-  if (d.mode == DFX_HEAD_SOFTMAX && head_dt_size(d.src_dt) != 1)
+  if (d.mode == DFX_HEAD_SOFTMAX && plan_dt_size(d.src_dt) != 1)
     return *why = "softmax of a 4-byte src (reorder it to u8 / s8 first)", DFX_ERR_UNSUPPORTED;
   return DFX_OK;
 }
 
 // the class of a path, as far as the descriptor decides it (pointer alignment is checked per submit)
 inline bool head_pixel_class(const dfx_head_desc &d) {
-  return head_dt_size(d.src_dt) == 1 && (d.mode == DFX_HEAD_SOFTMAX || d.k == 1) && d.src_ld % 16 == 0 && d.src_ld <= HEAD_PIXEL_MAX_LD;
+  return plan_dt_size(d.src_dt) == 1 && (d.mode == DFX_HEAD_SOFTMAX || d.k == 1) && d.src_ld % 16 == 0 && d.src_ld <= HEAD_PIXEL_MAX_LD;
 }
-inline bool head_row_class(const dfx_head_desc &d) { return ((long long)d.src_ld * head_dt_size(d.src_dt)) % 16 == 0; }
+inline bool head_row_class(const dfx_head_desc &d) { return ((long long)d.src_ld * plan_dt_size(d.src_dt)) % 16 == 0; }
 inline bool head_in_class(const dfx_head_desc &d, int path) {
   return path == DFX_HEAD_PIXEL ? head_pixel_class(d) : path == DFX_HEAD_ROW ? head_row_class(d) : path == DFX_HEAD_GENERIC;
 }
@@ -74,7 +74,7 @@ inline bool head_in_class(const dfx_head_desc &d, int path) {
 // wave per row loses 7 to 39 times); the generic kernel everywhere else.
 inline int head_path(const dfx_head_desc &d) {
   if (d.force_path != -1) return d.force_path;
-  const bool long_row = head_row_class(d) && (long long)d.src_ld * head_dt_size(d.src_dt) >= HEAD_ROW_AUTO_MIN_BYTES;
+  const bool long_row = head_row_class(d) && (long long)d.src_ld * plan_dt_size(d.src_dt) >= HEAD_ROW_AUTO_MIN_BYTES;
   if (d.mode == DFX_HEAD_SOFTMAX && long_row) return DFX_HEAD_ROW;
   if (head_pixel_class(d)) return DFX_HEAD_PIXEL;
   return long_row ? DFX_HEAD_ROW : DFX_HEAD_GENERIC;
@@ -104,18 +104,10 @@ inline int head_table_ok(const uint32_t *e, int c, const char **why) {
   return DFX_OK;
 }
 
-// bytes from a buffer's first to behind its last touched byte: rows `ld` elements apart, `cols` touched per row
-inline unsigned long long head_extent(long long rows, int ld, int cols, int esize) {
-  return ((unsigned long long)(rows - 1) * (unsigned)ld + (unsigned)cols) * (unsigned)esize;
-}
-inline bool head_overlap(uintptr_t a, unsigned long long abytes, uintptr_t b, unsigned long long bbytes) {
-  return a < b + bbytes && b < a + abytes;
-}
-
 // what one submit must read and write (without val, which submit may or may not be given)
 inline unsigned long long head_algorithmic_bytes(const dfx_head_desc &d) {
-  const unsigned long long in = (unsigned long long)d.rows * d.c * head_dt_size(d.src_dt);
-  return in + (unsigned long long)d.rows * head_out_cols(d) * head_dt_size(d.dst_dt);
+  const unsigned long long in = (unsigned long long)d.rows * d.c * plan_dt_size(d.src_dt);
+  return in + (unsigned long long)d.rows * head_out_cols(d) * plan_dt_size(d.dst_dt);
 }
 
 }  // namespace dfx

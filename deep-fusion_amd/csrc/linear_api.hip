@@ -4,14 +4,12 @@
 // linear.hip.  The op has its own handle: weighted_op.h's skeleton has no src dtype, no pitches and no table.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <atomic>
 #include <cstdio>
-#include <cstring>
 #include <new>
 #include <vector>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "linear.cuh"
 #include "linear_pack.h"
 #include "linear_plan.h"
@@ -39,14 +37,17 @@ struct dfx_linear {
 
 namespace {
 
+void release(dfx_linear *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  h->host.release();
+  (void)hipFree(h->d_img);
+  delete h;
+}
+
 // launches since the library was loaded, by the kernel that ran; process-wide, because submit does not write to the
 // handle (dfx_debug_linear_launches)
-std::atomic<long long> g_launches[2];
-
-long long grid_cap() {
-  const char *e = tuning_value("DFX_LINEAR_GRID");  // testing aid
-  return e ? std::max(1ll, atoll(e)) : 0;
-}
+LaunchCounts<2> g_launches;
 
 void set_name(dfx_linear *h) {
   const dfx_linear_desc &d = h->d;
@@ -58,48 +59,27 @@ void set_name(dfx_linear *h) {
     snprintf(h->kernel_name, sizeof(h->kernel_name), "linear_generic<%s,%s>%s", dt_name(d.src_dt), dt_name(d.dst_dt), lut);
 }
 
-void release(dfx_linear *h) {
-  DeviceGuard dg(h->device);
-  h->host.release();
-  (void)hipFree(h->d_img);
-  delete h;
-}
-
 }  // namespace
 
 extern "C" {
 
 int dfx_linear_create(const dfx_linear_desc *desc, dfx_linear_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "linear_create: null argument");
-  *out = nullptr;
+  dfx_linear *h = nullptr;
+  int cus = 0;
+  const int rc = open_create("linear", desc, out, &h, [](const dfx_linear_desc &d) { return validated("linear", lin_validate, d); }, &cus, release);
+  if (rc) return rc;
   const dfx_linear_desc &d = *desc;
-  const char *why = "";
-  const int rc = lin_validate(d, &why);
-  if (rc) return fail(rc, "linear: %s", why);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "linear_create: no HIP device (this library has no CPU path)");
-  dfx_linear *h = new (std::nothrow) dfx_linear();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
-    delete h;
-    return fail(DFX_ERR_HIP, "linear_create: cannot query the device");
-  }
-  const int cus = std::max(1, prop.multiProcessorCount);
   // AUTO RULE (include/dfx.h DFX_LINEAR_AUTO_NOTE)
   h->path = lin_path(d);
   const char *fb = tuning_value("DFX_LINEAR_BM");  // testing / tuning aid: 64 | 128, anything else is ignored
   h->bm = lin_bm(d, cus, fb ? atoi(fb) : 0);
-  const long long cap = grid_cap();
+  const long long cap = grid_cap("DFX_LINEAR_GRID");
   h->grid[h->path] = lin_grid(d, h->path, h->bm, cus, cap);
   h->grid[DFX_LINEAR_GENERIC] = lin_grid(d, DFX_LINEAR_GENERIC, h->bm, cus, cap);
   h->im = lin_image(d.n, d.k);
   const hipError_t e = hipMalloc((void **)&h->d_img, h->im.bytes);
   if (e != hipSuccess) {
-    delete h;
+    release(h);
     return fail(DFX_ERR_HIP, "linear_create: weight image: %s", hipGetErrorString(e));
   }
   LinArgs &a = h->args;
@@ -154,10 +134,10 @@ int dfx_linear_submit(dfx_linear_t *h, const void *src_dev, void *dst_dev, dfx_s
   const dfx_linear_desc &d = h->d;
   if (!h->weights_set.load()) return fail(DFX_ERR_STATE, "linear_submit: dfx_linear_set_weights not called");
   if (lin_has_table(d) && !h->table_set.load()) return fail(DFX_ERR_STATE, "linear_submit: dfx_linear_set_table not called");
-  const unsigned esz = (unsigned)lin_dt_size(d.dst_dt);
+  const unsigned esz = (unsigned)plan_dt_size(d.dst_dt);
   const uintptr_t src = (uintptr_t)src_dev, dst = (uintptr_t)dst_dev;
   if (dst % esz) return fail(DFX_ERR_INVALID, "linear_submit: dst is not aligned to its element");
-  if (lin_overlap(src, lin_extent(d.rows, d.src_ld, d.k, 1), dst, lin_extent(d.rows, d.dst_ld, d.n, (int)esz)))
+  if (plan_overlap(src, plan_extent(d.rows, d.src_ld, d.k, 1), dst, plan_extent(d.rows, d.dst_ld, d.n, (int)esz)))
     return fail(DFX_ERR_INVALID, "linear_submit: dst overlaps src");
   DeviceGuard dg(h->device);
   // 16-byte loads need an aligned src: others take the generic kernel for this submit, as lnorm and bmm do
@@ -168,10 +148,7 @@ int dfx_linear_submit(dfx_linear_t *h, const void *src_dev, void *dst_dev, dfx_s
   a.vec = dst % (4 * esz) == 0 && d.dst_ld % 4 == 0;
   const int rc = path == DFX_LINEAR_TILE ? launch_linear_tile(a, h->bm, h->grid[path], lin_lds_bytes(path, h->bm), (hipStream_t)s, h->route != 0)
                                          : launch_linear_generic(a, h->grid[path], (hipStream_t)s);
-  if (rc != 0) return fail(DFX_ERR_UNSUPPORTED, "linear_submit: no kernel instance for this op");
-  HIP_TRY(hipGetLastError());
-  g_launches[path].fetch_add(1, std::memory_order_relaxed);
-  return DFX_OK;
+  return g_launches.launched("linear", rc, path);
 }
 
 int dfx_linear_submit_host(dfx_linear_t *h, const void *src_host, void *dst_host) {
@@ -181,16 +158,12 @@ int dfx_linear_submit_host(dfx_linear_t *h, const void *src_host, void *dst_host
   if (lin_has_table(d) && !h->table_set.load()) return fail(DFX_ERR_STATE, "linear_submit_host: dfx_linear_set_table not called");
   if (d.src_ld != d.k || d.dst_ld != d.n) return fail(DFX_ERR_UNSUPPORTED, "linear_submit_host: densely packed operands only (src_ld == k, dst_ld == n)");
   DeviceGuard dg(h->device);
-  return h->host.run(src_host, (size_t)d.rows * (size_t)d.k, dst_host, (size_t)d.rows * (size_t)d.n * (size_t)lin_dt_size(d.dst_dt),
+  return h->host.run(src_host, (size_t)d.rows * (size_t)d.k, dst_host, (size_t)d.rows * (size_t)d.n * (size_t)plan_dt_size(d.dst_dt),
                      [h](const void *sp, void *dp, dfx_stream_t st) { return dfx_linear_submit(h, sp, dp, st); });
 }
 
 // test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_linear_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_linear_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_linear_launches(int64_t out[2]) { return g_launches.read("linear", out); }
 
 // test hook: the requant route the last dfx_linear_set_weights proved (numbering of dfx_debug_conv_requant)
 int dfx_debug_linear_requant(const dfx_linear_t *h, int32_t out[1]) {
@@ -201,21 +174,16 @@ int dfx_debug_linear_requant(const dfx_linear_t *h, int32_t out[1]) {
 }
 
 int dfx_linear_query(const dfx_linear_t *h, dfx_linear_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "linear_query: null argument");
-  memset(info, 0, sizeof(*info));
-  info->path = h->path;
+  if (const int rc = open_query("linear", h, info)) return rc;
   info->grid = h->grid[h->path];
   info->block = LIN_THREADS;
   info->lds_bytes = lin_lds_bytes(h->path, h->bm);
-  info->device = h->device;
   info->algorithmic_ops = lin_algorithmic_ops(h->d);
   info->algorithmic_bytes = lin_algorithmic_bytes(h->d);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_linear_destroy(dfx_linear_t *h) {
-  if (!h) return DFX_OK;
   release(h);
   return DFX_OK;
 }

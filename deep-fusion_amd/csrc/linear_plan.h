@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/dfx.h"
+#include "plan_common.h"
 
 namespace dfx {
 
@@ -23,7 +24,6 @@ constexpr int LIN_TILE_GRID_PER_CU = 2;           // workgroups per CU at most; 
 constexpr int LIN_GEN_GRID_PER_CU = 16;
 
 inline bool lin_dt_ok(int dt) { return dt == DFX_F32 || dt == DFX_S32 || dt == DFX_S8 || dt == DFX_U8; }
-inline int lin_dt_size(int dt) { return (dt == DFX_F32 || dt == DFX_S32) ? 4 : 1; }
 inline bool lin_has_table(const dfx_linear_desc &d) { return d.lut_in_dt != DFX_UNDEF; }
 // the type the requant produces: dst's, or the table's index type
 inline int lin_requant_dt(const dfx_linear_desc &d) { return lin_has_table(d) ? d.lut_in_dt : d.dst_dt; }
@@ -128,16 +128,9 @@ inline unsigned long long lin_algorithmic_ops(const dfx_linear_desc &d) {
 // src's valid bytes + the weights + dst's elements + bias (as f32) and scales as given + the table
 inline unsigned long long lin_algorithmic_bytes(const dfx_linear_desc &d) {
   return (unsigned long long)d.rows * d.k + (unsigned long long)d.n * d.k +
-         (unsigned long long)d.rows * d.n * (unsigned)lin_dt_size(d.dst_dt) + (d.bia_dt != DFX_UNDEF ? 4ull * d.n : 0) + 4ull * d.nscales +
+         (unsigned long long)d.rows * d.n * (unsigned)plan_dt_size(d.dst_dt) + (d.bia_dt != DFX_UNDEF ? 4ull * d.n : 0) + 4ull * d.nscales +
          (lin_has_table(d) ? 256 : 0);
 }
 
-// extents in bytes of an operand of `rows` rows of `valid` elements, `ld` apart
-inline unsigned long long lin_extent(long long rows, long long ld, long long valid, int esz) {
-  return (unsigned long long)((rows - 1) * ld + valid) * (unsigned)esz;
-}
-inline bool lin_overlap(uintptr_t a, unsigned long long abytes, uintptr_t b, unsigned long long bbytes) {
-  return a < b + bbytes && b < a + abytes;
-}
 
 }  // namespace dfx

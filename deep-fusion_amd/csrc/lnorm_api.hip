@@ -3,15 +3,12 @@
 // lnorm_plan.h), launches.  The kernels are in lnorm.cuh.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "lnorm.cuh"
 #include "lnorm_plan.h"
 
@@ -33,16 +30,16 @@ struct dfx_lnorm {
 
 namespace {
 
+void release(dfx_lnorm *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  (void)hipFree(h->d_params);
+  delete h;
+}
+
 // launches since the library was loaded, by the kernel that ran; process-wide, because submit does not write to the
 // handle (dfx_debug_lnorm_launches)
-std::atomic<long long> g_launches[2];
-
-const char *dt_name(int dt) { return dt == DFX_F32 ? "f32" : dt == DFX_S8 ? "s8" : "u8"; }
-
-long long grid_cap() {
-  const char *e = tuning_value("DFX_LNORM_GRID");  // testing aid
-  return e ? std::max(1ll, atoll(e)) : 0;
-}
+LaunchCounts<2> g_launches;
 
 void set_name(dfx_lnorm *h) {
   const dfx_lnorm_desc &d = h->d;
@@ -60,31 +57,25 @@ void set_name(dfx_lnorm *h) {
 extern "C" {
 
 int dfx_lnorm_create(const dfx_lnorm_desc *desc, dfx_lnorm_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "lnorm_create: null argument");
-  *out = nullptr;
+  dfx_lnorm *h = nullptr;
+  const int rc = open_create("lnorm", desc, out, &h, [](const dfx_lnorm_desc &d) {
+    if (const int bad = validated("lnorm", lnorm_validate, d)) return bad;
+    if (d.force_path != -1 && !lnorm_in_class(d, d.force_path))
+      return fail(DFX_ERR_UNSUPPORTED, "lnorm_create: descriptor outside the forced path's class (row: src_ld and dst_ld * element size "
+                                       "multiples of 16)");
+    return (int)DFX_OK;
+  });
+  if (rc) return rc;
   const dfx_lnorm_desc &d = *desc;
-  const char *why = "";
-  int rc = lnorm_validate(d, &why);
-  if (rc) return fail(rc, "lnorm: %s", why);
-  if (d.force_path != -1 && !lnorm_in_class(d, d.force_path))
-    return fail(DFX_ERR_UNSUPPORTED, "lnorm_create: descriptor outside the forced path's class (row: src_ld and dst_ld * element size "
-                                     "multiples of 16)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "lnorm_create: no HIP device (this library has no CPU path)");
-  dfx_lnorm *h = new (std::nothrow) dfx_lnorm();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   // AUTO RULE (include/dfx.h DFX_LNORM_AUTO_NOTE)
   h->path = lnorm_path(d);
   h->lanes = lnorm_lanes(d.c);
   const hipError_t e = hipMalloc((void **)&h->d_params, lnorm_param_bytes(d.c));
   if (e != hipSuccess) {
-    delete h;
+    release(h);
     return fail(DFX_ERR_HIP, "lnorm_create: parameters: %s", hipGetErrorString(e));
   }
-  const long long cap = grid_cap();
+  const long long cap = grid_cap("DFX_LNORM_GRID");
   h->grid[h->path] = lnorm_grid(d.rows, d.c, h->path, cap);
   h->grid[DFX_LNORM_GENERIC] = lnorm_grid(d.rows, d.c, DFX_LNORM_GENERIC, cap);
   set_name(h);
@@ -94,7 +85,7 @@ int dfx_lnorm_create(const dfx_lnorm_desc *desc, dfx_lnorm_t **out) {
 
 int dfx_lnorm_set_params(dfx_lnorm_t *h, const float *gamma, const float *beta_or_null, const uint8_t *shift_or_null) {
   if (!h || !gamma) return fail(DFX_ERR_INVALID, "lnorm_set_params: null argument");
-  const int c = h->d.c, cp = lnorm_up16(c);
+  const int c = h->d.c, cp = plan_up16(c);
   if (shift_or_null)
     for (int k = 0; k < c; ++k)
       if (shift_or_null[k] > DFX_LNORM_MAX_SHIFT) return fail(DFX_ERR_INVALID, "lnorm_set_params: shift[%d] = %d is above 7", k, (int)shift_or_null[k]);
@@ -114,15 +105,15 @@ int dfx_lnorm_submit(dfx_lnorm_t *h, const void *src_dev, void *dst_dev, dfx_str
   if (!h || !src_dev || !dst_dev) return fail(DFX_ERR_INVALID, "lnorm_submit: null argument");
   const dfx_lnorm_desc &d = h->d;
   if (!h->params_set) return fail(DFX_ERR_STATE, "lnorm_submit: dfx_lnorm_set_params not called");
-  const int osz = lnorm_dt_size(d.dst_dt);
+  const int osz = plan_dt_size(d.dst_dt);
   const uintptr_t src = (uintptr_t)src_dev, dst = (uintptr_t)dst_dev;
   if (dst % osz) return fail(DFX_ERR_INVALID, "lnorm_submit: an f32 dst is not 4-byte aligned");
-  if (lnorm_overlap(src, lnorm_extent(d.rows, d.src_ld, d.c, 1), dst, lnorm_extent(d.rows, d.dst_ld, d.c, osz)))
+  if (plan_overlap(src, plan_extent(d.rows, d.src_ld, d.c, 1), dst, plan_extent(d.rows, d.dst_ld, d.c, osz)))
     return fail(DFX_ERR_INVALID, "lnorm_submit: dst overlaps src (in place is not built)");
   DeviceGuard dg(h->device);
   // 16-byte loads and stores need aligned buffers: others take the generic kernel for this submit, as head does
   const int path = (src | dst) % 16 == 0 ? h->path : DFX_LNORM_GENERIC;
-  const int cp = lnorm_up16(d.c);
+  const int cp = plan_up16(d.c);
   LnormArgs a = {};  // per launch: concurrent submits on several streams are independent
   a.src = (const unsigned char *)src_dev;
   a.dst = (unsigned char *)dst_dev;
@@ -135,37 +126,23 @@ int dfx_lnorm_submit(dfx_lnorm_t *h, const void *src_dev, void *dst_dev, dfx_str
   const int lds = lnorm_lds_bytes(d, path);
   a.stage = lds > 0;
   a.eps = d.eps;
-  if (launch_lnorm(a, path, h->lanes, h->grid[path], lds, (hipStream_t)s) != 0) return fail(DFX_ERR_UNSUPPORTED, "lnorm_submit: no kernel instance for this op");
-  HIP_TRY(hipGetLastError());
-  g_launches[path].fetch_add(1, std::memory_order_relaxed);
-  return DFX_OK;
+  return g_launches.launched("lnorm", launch_lnorm(a, path, h->lanes, h->grid[path], lds, (hipStream_t)s), path);
 }
 
 // test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_lnorm_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_lnorm_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_lnorm_launches(int64_t out[2]) { return g_launches.read("lnorm", out); }
 
 int dfx_lnorm_query(const dfx_lnorm_t *h, dfx_lnorm_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "lnorm_query: null argument");
-  memset(info, 0, sizeof(*info));
-  info->path = h->path;
+  if (const int rc = open_query("lnorm", h, info)) return rc;
   info->grid = h->grid[h->path];
   info->block = LNORM_THREADS;
   info->lds_bytes = lnorm_lds_bytes(h->d, h->path);
-  info->device = h->device;
   info->algorithmic_bytes = lnorm_algorithmic_bytes(h->d, h->has_shift);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_lnorm_destroy(dfx_lnorm_t *h) {
-  if (!h) return DFX_OK;
-  DeviceGuard dg(h->device);
-  (void)hipFree(h->d_params);
-  delete h;
+  release(h);
   return DFX_OK;
 }
 

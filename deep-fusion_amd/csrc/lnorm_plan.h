@@ -1,6 +1,6 @@
 // lnorm_plan.h -- host-only, plain C++: what the int8 layer norm / RMS norm (dfx_lnorm_* of include/dfx.h) decides before a
 // kernel runs: the descriptor's validation, the bounds that make its integer statistics exact, the class of the row kernel,
-// the lanes per row, the auto rule, the extent of both buffers (for the overlap check), the grid and the LDS plan.
+// the lanes per row, the auto rule, the grid and the LDS plan (buffer extents and the overlap test: plan_common.h).
 // No HIP in here, so that it can be built and run on its own (tools/lnorm_plan_check.cc, under the host sanitizers).
 #pragma once
 
@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/dfx.h"
+#include "plan_common.h"
 
 namespace dfx {
 
@@ -36,9 +37,7 @@ static_assert((unsigned long long)DFX_LNORM_MAX_C * 255 * 255 < (1ull << 32), "a
 
 inline bool lnorm_src_dt_ok(int dt) { return dt == DFX_S8 || dt == DFX_U8; }
 inline bool lnorm_dst_dt_ok(int dt) { return dt == DFX_S8 || dt == DFX_U8 || dt == DFX_F32; }
-inline int lnorm_dt_size(int dt) { return dt == DFX_F32 ? 4 : 1; }
 inline bool lnorm_path_ok(int p) { return p == DFX_LNORM_ROW || p == DFX_LNORM_GENERIC; }
-inline int lnorm_up16(int c) { return (c + 15) / 16 * 16; }
 
 // DFX_OK, or the code dfx_lnorm_create returns with *why set to the reason.  Everything DFX_ERR_INVALID is found before
 // anything DFX_ERR_UNSUPPORTED (the class of a forced path is lnorm_create's business: lnorm_in_class below).
@@ -63,7 +62,7 @@ inline int lnorm_validate(const dfx_lnorm_desc &d, const char **why) {
 
 // the class of a path, as far as the descriptor decides it (pointer alignment is checked per submit)
 inline bool lnorm_row_class(const dfx_lnorm_desc &d) {
-  return d.src_ld % 16 == 0 && ((long long)d.dst_ld * lnorm_dt_size(d.dst_dt)) % 16 == 0;
+  return d.src_ld % 16 == 0 && ((long long)d.dst_ld * plan_dt_size(d.dst_dt)) % 16 == 0;
 }
 inline bool lnorm_in_class(const dfx_lnorm_desc &d, int path) {
   return path == DFX_LNORM_ROW ? lnorm_row_class(d) : path == DFX_LNORM_GENERIC;
@@ -98,23 +97,15 @@ inline int lnorm_grid(long long rows, int c, int path, long long cap) {
 }
 // row kernel: gamma and beta of whole 16-channel groups (the pad reads as 0), staged once per workgroup; 0: read from global
 inline int lnorm_lds_bytes(const dfx_lnorm_desc &d, int path) {
-  const int bytes = 8 * lnorm_up16(d.c);
+  const int bytes = 8 * plan_up16(d.c);
   return path == DFX_LNORM_ROW && bytes <= LNORM_LDS_MAX ? bytes : 0;
 }
 // the device image of the parameters: gamma[up16(c)] f32, beta[up16(c)] f32, shift[up16(c)] u8; pads are 0
-inline size_t lnorm_param_bytes(int c) { return (size_t)9 * lnorm_up16(c); }
-
-// bytes from a buffer's first to behind its last touched byte: rows `ld` elements apart, `cols` touched per row
-inline unsigned long long lnorm_extent(long long rows, int ld, int cols, int esize) {
-  return ((unsigned long long)(rows - 1) * (unsigned)ld + (unsigned)cols) * (unsigned)esize;
-}
-inline bool lnorm_overlap(uintptr_t a, unsigned long long abytes, uintptr_t b, unsigned long long bbytes) {
-  return a < b + bbytes && b < a + abytes;
-}
+inline size_t lnorm_param_bytes(int c) { return (size_t)9 * plan_up16(c); }
 
 // what one submit must read and write
 inline unsigned long long lnorm_algorithmic_bytes(const dfx_lnorm_desc &d, bool has_shift) {
-  const unsigned long long io = (unsigned long long)d.rows * d.c * (1 + lnorm_dt_size(d.dst_dt));
+  const unsigned long long io = (unsigned long long)d.rows * d.c * (1 + plan_dt_size(d.dst_dt));
   return io + (unsigned long long)d.c * (has_shift ? 9 : 8);
 }
 

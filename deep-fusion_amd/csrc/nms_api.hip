@@ -3,13 +3,10 @@
 // the order of the submits that share the handle's scratch.  The kernels are in nms.cuh.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdio>
-#include <cstring>
-#include <new>
 #include <vector>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "nms.cuh"
 #include "nms_plan.h"
 
@@ -34,9 +31,6 @@ struct dfx_nms {
 
 namespace {
 
-// submits since the library was loaded, by the path that ran (dfx_debug_nms_launches)
-std::atomic<long long> g_launches[2];
-
 void release(dfx_nms *h) {
   if (!h) return;
   DeviceGuard dg(h->device);
@@ -45,24 +39,18 @@ void release(dfx_nms *h) {
   delete h;
 }
 
+// submits since the library was loaded, by the path that ran (dfx_debug_nms_launches)
+LaunchCounts<2> g_launches;
+
 }  // namespace
 
 extern "C" {
 
 int dfx_nms_create(const dfx_nms_desc *desc, dfx_nms_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "nms_create: null argument");
-  *out = nullptr;
+  dfx_nms *h = nullptr;
+  const int rc = open_create("nms", desc, out, &h, [](const dfx_nms_desc &d) { return validated("nms", nms_validate, d); });
+  if (rc) return rc;
   const dfx_nms_desc &d = *desc;
-  const char *why = "";
-  const int rc = nms_validate(d, &why);
-  if (rc) return fail(rc, "nms: %s", why);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "nms_create: no HIP device (this library has no CPU path)");
-  dfx_nms *h = new (std::nothrow) dfx_nms();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   // AUTO RULE (include/dfx.h DFX_NMS_AUTO_NOTE)
   h->path = nms_path(d);
   NmsArgs &a = h->args;
@@ -134,9 +122,9 @@ int dfx_nms_submit(dfx_nms_t *h, const dfx_nms_io *io, dfx_stream_t s) {
   if (four % 4) return fail(DFX_ERR_INVALID, "nms_submit: a pointer to 4-byte elements is not 4-byte aligned");
   for (int o = 0; o < n_out; ++o) {
     for (int i = 0; i < n_in; ++i)
-      if (nms_overlap(out_p[o], out_n[o], in_p[i], in_n[i])) return fail(DFX_ERR_INVALID, "nms_submit: an output overlaps an input");
+      if (plan_overlap(out_p[o], out_n[o], in_p[i], in_n[i])) return fail(DFX_ERR_INVALID, "nms_submit: an output overlaps an input");
     for (int p = o + 1; p < n_out; ++p)
-      if (nms_overlap(out_p[o], out_n[o], out_p[p], out_n[p])) return fail(DFX_ERR_INVALID, "nms_submit: two outputs overlap");
+      if (plan_overlap(out_p[o], out_n[o], out_p[p], out_n[p])) return fail(DFX_ERR_INVALID, "nms_submit: two outputs overlap");
   }
   DeviceGuard dg(h->device);
   const hipStream_t st = (hipStream_t)s;
@@ -157,7 +145,7 @@ int dfx_nms_submit(dfx_nms_t *h, const dfx_nms_io *io, dfx_stream_t s) {
   if (path == DFX_NMS_GENERIC) {  // one launch, nothing of the handle's: independent of every other submit
     launch_nms_generic(a, image_grid, st);
     HIP_TRY(hipGetLastError());
-    g_launches[DFX_NMS_GENERIC].fetch_add(1, std::memory_order_relaxed);
+    g_launches.hit(DFX_NMS_GENERIC);
     return DFX_OK;
   }
   // three launches through the handle's scratch: serialised (dfx.h; TwoLaunchOrder in dfx_internal.h)
@@ -177,23 +165,17 @@ int dfx_nms_submit(dfx_nms_t *h, const dfx_nms_io *io, dfx_stream_t s) {
   // (once a launch is out the scratch has a writer in flight: every way out goes through leave())
   rc = h->order.leave(st);
   if (e != hipSuccess) return fail(DFX_ERR_HIP, "nms_submit: %s", hipGetErrorString(e));
-  if (rc == DFX_OK) g_launches[DFX_NMS_MASK].fetch_add(1, std::memory_order_relaxed);
+  if (rc == DFX_OK) g_launches.hit(DFX_NMS_MASK);
   return rc;
 }
 
 // test hook: how many submits have run on each path so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_nms_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_nms_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_nms_launches(int64_t out[2]) { return g_launches.read("nms", out); }
 
 int dfx_nms_query(const dfx_nms_t *h, dfx_nms_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "nms_query: null argument");
-  memset(info, 0, sizeof(*info));
+  if (const int rc = open_query("nms", h, info)) return rc;
   const bool mask = h->path == DFX_NMS_MASK;
   const dfx_nms_desc &d = h->d;
-  info->path = h->path;
   info->tiles = mask ? nms_tiles(d.n) : 0;
   info->grid_prep = mask ? nms_prep_grid(d.bs, d.n) : 0;
   info->grid_mask = mask ? nms_mask_grid(d.bs, d.n) : 0;
@@ -203,10 +185,8 @@ int dfx_nms_query(const dfx_nms_t *h, dfx_nms_info *info) {
   info->block_scan = mask ? NMS_SCAN_THREADS : NMS_GENERIC_THREADS;
   info->lds_bytes = nms_lds_bytes(h->path);
   info->launches = nms_launches(h->path);
-  info->device = h->device;
   info->scratch_bytes = mask ? h->layout.bytes : 0;
   info->algorithmic_bytes = nms_algorithmic_bytes(d);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/dfx.h"
+#include "plan_common.h"
 
 #if defined(__HIPCC__)
 #define NMS_HD __host__ __device__ inline
@@ -121,9 +122,6 @@ inline unsigned long long nms_deltas_extent(const dfx_nms_desc &d) {
 inline unsigned long long nms_anchors_extent(const dfx_nms_desc &d) { return (unsigned long long)d.n_anchors * 16; }
 inline unsigned long long nms_keep_extent(const dfx_nms_desc &d) { return ((unsigned long long)(d.bs - 1) * (unsigned)d.keep_ld + (unsigned)d.max_out) * 4; }
 inline unsigned long long nms_boxes_out_extent(const dfx_nms_desc &d) { return (unsigned long long)d.bs * d.max_out * 16; }
-inline bool nms_overlap(uintptr_t a, unsigned long long abytes, uintptr_t b, unsigned long long bbytes) {
-  return a < b + bbytes && b < a + abytes;
-}
 
 // what one submit must read and write (without boxes_out, which a submit may leave out)
 inline unsigned long long nms_algorithmic_bytes(const dfx_nms_desc &d) {

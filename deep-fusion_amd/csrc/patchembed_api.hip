@@ -5,14 +5,12 @@
 // prefix and no token layout.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <atomic>
 #include <cstdio>
-#include <cstring>
 #include <new>
 #include <vector>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "patchembed.cuh"
 #include "patchembed_pack.h"
 #include "patchembed_plan.h"
@@ -45,14 +43,17 @@ struct dfx_patchembed {
 
 namespace {
 
+void release(dfx_patchembed *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  h->host.release();
+  (void)hipFree(h->d_img);
+  delete h;
+}
+
 // launches since the library was loaded, by the kernel that ran; process-wide, because submit does not write to the
 // handle (dfx_debug_patchembed_launches)
-std::atomic<long long> g_launches[2];
-
-long long grid_cap() {
-  const char *e = tuning_value("DFX_PATCHEMBED_GRID");  // testing aid
-  return e ? std::max(1ll, atoll(e)) : 0;
-}
+LaunchCounts<2> g_launches;
 
 void set_name(dfx_patchembed *h) {
   const dfx_patchembed_desc &d = h->d;
@@ -62,13 +63,6 @@ void set_name(dfx_patchembed *h) {
              !h->weights_set.load() ? "(no weights)" : h->route ? "fast" : "exact", tab);
   else
     snprintf(h->kernel_name, sizeof(h->kernel_name), "patchembed_generic<%s,%s>%s", dt_name(d.src_dt), dt_name(d.dst_dt), tab);
-}
-
-void release(dfx_patchembed *h) {
-  DeviceGuard dg(h->device);
-  h->host.release();
-  (void)hipFree(h->d_img);
-  delete h;
 }
 
 // packs everything below the table section from the handle's copies, uploads it and proves the route
@@ -93,37 +87,23 @@ int pack_and_prove(dfx_patchembed *h) {
 extern "C" {
 
 int dfx_patchembed_create(const dfx_patchembed_desc *desc, dfx_patchembed_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "patchembed_create: null argument");
-  *out = nullptr;
+  dfx_patchembed *h = nullptr;
+  int cus = 0;
+  const int rc = open_create("patchembed", desc, out, &h, [](const dfx_patchembed_desc &d) { return validated("patchembed", pe_validate, d); }, &cus, release);
+  if (rc) return rc;
   const dfx_patchembed_desc &d = *desc;
-  const char *why = "";
-  const int rc = pe_validate(d, &why);
-  if (rc) return fail(rc, "patchembed: %s", why);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "patchembed_create: no HIP device (this library has no CPU path)");
-  dfx_patchembed *h = new (std::nothrow) dfx_patchembed();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
-    delete h;
-    return fail(DFX_ERR_HIP, "patchembed_create: cannot query the device");
-  }
-  const int cus = std::max(1, prop.multiProcessorCount);
   // AUTO RULE (include/dfx.h DFX_PATCHEMBED_AUTO_NOTE)
   h->path = pe_path(d);
   h->granule = pe_granule(d);
   const char *fb = tuning_value("DFX_PATCHEMBED_BM");  // testing / tuning aid: 64 | 128, anything else is ignored
   h->bm = pe_bm(d, cus, fb ? atoi(fb) : 0);
-  const long long cap = grid_cap();
+  const long long cap = grid_cap("DFX_PATCHEMBED_GRID");
   h->grid[h->path] = pe_grid(d, h->path, h->bm, cus, cap);
   h->grid[DFX_PATCHEMBED_GENERIC] = pe_grid(d, DFX_PATCHEMBED_GENERIC, h->bm, cus, cap);
   h->im = pe_image(d);
   const hipError_t e = hipMalloc((void **)&h->d_img, h->im.bytes);
   if (e != hipSuccess) {
-    delete h;
+    release(h);
     return fail(DFX_ERR_HIP, "patchembed_create: device image: %s", hipGetErrorString(e));
   }
   try {
@@ -165,7 +145,7 @@ int dfx_patchembed_set_weights(dfx_patchembed_t *h, const int8_t *wei, const voi
   try {
     h->wperm.resize((size_t)d.oc * (size_t)pe_k(d));
     h->scales.assign(scales, scales + d.nscales);
-    if (d.bia_dt != DFX_UNDEF) h->bia.assign((const unsigned char *)bia, (const unsigned char *)bia + (size_t)d.oc * (size_t)lin_dt_size(d.bia_dt));
+    if (d.bia_dt != DFX_UNDEF) h->bia.assign((const unsigned char *)bia, (const unsigned char *)bia + (size_t)d.oc * (size_t)plan_dt_size(d.bia_dt));
   } catch (const std::bad_alloc &) {
     return fail(DFX_ERR_HIP, "out of host memory");
   }
@@ -211,7 +191,7 @@ int dfx_patchembed_set_prefix(dfx_patchembed_t *h, const void *rows) {
   const dfx_patchembed_desc &d = h->d;
   if (d.tok_offset < 1) return fail(DFX_ERR_INVALID, "patchembed_set_prefix: the handle has no prefix rows (tok_offset is 0)");
   DeviceGuard dg(h->device);
-  HIP_TRY(hipMemcpy(h->d_img + h->im.off_prefix, rows, (size_t)d.tok_offset * (size_t)d.oc * (size_t)lin_dt_size(d.dst_dt), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->d_img + h->im.off_prefix, rows, (size_t)d.tok_offset * (size_t)d.oc * (size_t)plan_dt_size(d.dst_dt), hipMemcpyHostToDevice));
   h->prefix_set.store(1);
   return DFX_OK;
 }
@@ -221,11 +201,11 @@ int dfx_patchembed_submit(dfx_patchembed_t *h, const void *src_dev, void *dst_de
   const dfx_patchembed_desc &d = h->d;
   if (!h->weights_set.load()) return fail(DFX_ERR_STATE, "patchembed_submit: dfx_patchembed_set_weights not called");
   if (d.table && !h->table_set.load()) return fail(DFX_ERR_STATE, "patchembed_submit: dfx_patchembed_set_table not called");
-  const unsigned esz = (unsigned)lin_dt_size(d.dst_dt);
+  const unsigned esz = (unsigned)plan_dt_size(d.dst_dt);
   const uintptr_t src = (uintptr_t)src_dev, dst = (uintptr_t)dst_dev;
   if (dst % esz) return fail(DFX_ERR_INVALID, "patchembed_submit: dst is not aligned to its element");
   const unsigned long long first = (unsigned long long)(h->prefix_set.load() ? 0 : d.tok_offset) * d.dst_ld * esz;  // the first byte written
-  if (lin_overlap(src, pe_src_extent(d), dst + first, pe_dst_extent(d) - first)) return fail(DFX_ERR_INVALID, "patchembed_submit: dst overlaps src");
+  if (plan_overlap(src, pe_src_extent(d), dst + first, pe_dst_extent(d) - first)) return fail(DFX_ERR_INVALID, "patchembed_submit: dst overlaps src");
   DeviceGuard dg(h->device);
   // the granule's loads need an aligned src: others take the generic kernel for this submit, as dfx_linear does
   const int path = h->granule && src % (unsigned)h->granule == 0 ? h->path : DFX_PATCHEMBED_GENERIC;
@@ -240,10 +220,7 @@ int dfx_patchembed_submit(dfx_patchembed_t *h, const void *src_dev, void *dst_de
   const int rc = path == DFX_PATCHEMBED_TILE
                      ? launch_patchembed_tile(a, h->bm, h->granule, h->grid[path], pe_lds_bytes(path, h->bm), (hipStream_t)s, h->route != 0)
                      : launch_patchembed_generic(a, h->grid[path], (hipStream_t)s);
-  if (rc != 0) return fail(DFX_ERR_UNSUPPORTED, "patchembed_submit: no kernel instance for this op");
-  HIP_TRY(hipGetLastError());
-  g_launches[path].fetch_add(1, std::memory_order_relaxed);
-  return DFX_OK;
+  return g_launches.launched("patchembed", rc, path);
 }
 
 int dfx_patchembed_submit_host(dfx_patchembed_t *h, const void *src_host, void *dst_host) {
@@ -252,16 +229,12 @@ int dfx_patchembed_submit_host(dfx_patchembed_t *h, const void *src_host, void *
   if (!h->weights_set.load()) return fail(DFX_ERR_STATE, "patchembed_submit_host: dfx_patchembed_set_weights not called");
   if (d.table && !h->table_set.load()) return fail(DFX_ERR_STATE, "patchembed_submit_host: dfx_patchembed_set_table not called");
   DeviceGuard dg(h->device);
-  return h->host.run(src_host, (size_t)pe_src_extent(d), dst_host, (size_t)d.bs * (size_t)d.img_rows * (size_t)d.dst_ld * (size_t)lin_dt_size(d.dst_dt),
+  return h->host.run(src_host, (size_t)pe_src_extent(d), dst_host, (size_t)d.bs * (size_t)d.img_rows * (size_t)d.dst_ld * (size_t)plan_dt_size(d.dst_dt),
                      [h](const void *sp, void *dp, dfx_stream_t st) { return dfx_patchembed_submit(h, sp, dp, st); });
 }
 
 // test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_patchembed_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_patchembed_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_patchembed_launches(int64_t out[2]) { return g_launches.read("patchembed", out); }
 
 // test hook: the requant route as the handle's weights and table prove it (numbering of dfx_debug_conv_requant)
 int dfx_debug_patchembed_requant(const dfx_patchembed_t *h, int32_t out[1]) {
@@ -272,22 +245,17 @@ int dfx_debug_patchembed_requant(const dfx_patchembed_t *h, int32_t out[1]) {
 }
 
 int dfx_patchembed_query(const dfx_patchembed_t *h, dfx_patchembed_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "patchembed_query: null argument");
-  memset(info, 0, sizeof(*info));
-  info->path = h->path;
+  if (const int rc = open_query("patchembed", h, info)) return rc;
   info->grid = h->grid[h->path];
   info->block = LIN_THREADS;
   info->lds_bytes = pe_lds_bytes(h->path, h->bm);
-  info->device = h->device;
   info->granule = h->granule;
   info->algorithmic_ops = pe_algorithmic_ops(h->d);
   info->algorithmic_bytes = pe_algorithmic_bytes(h->d, h->prefix_set.load() != 0);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_patchembed_destroy(dfx_patchembed_t *h) {
-  if (!h) return DFX_OK;
   release(h);
   return DFX_OK;
 }

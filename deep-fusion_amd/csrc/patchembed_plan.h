@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "linear_plan.h"
+#include "plan_common.h"
 
 namespace dfx {
 
@@ -132,14 +133,13 @@ struct PeImage {
   LinImage lin;
   size_t off_ktab, off_table, off_prefix, bytes;
 };
-inline size_t pe_up16(size_t v) { return (v + 15) / 16 * 16; }
 inline PeImage pe_image(const dfx_patchembed_desc &d) {
   PeImage im;
   im.lin = lin_image(d.oc, pe_k(d));
   im.off_ktab = im.lin.off_table;
-  im.off_table = im.off_ktab + pe_up16(pe_ktab_entries(d) * 4);
+  im.off_table = im.off_ktab + plan_up16(pe_ktab_entries(d) * 4);
   im.off_prefix = im.off_table + (d.table ? (size_t)pe_tokens(d) * (size_t)pe_table_ld(d.oc) * 4 : 0);
-  im.bytes = im.off_prefix + pe_up16((size_t)d.tok_offset * (size_t)d.oc * (size_t)lin_dt_size(d.dst_dt));
+  im.bytes = im.off_prefix + plan_up16((size_t)d.tok_offset * (size_t)d.oc * (size_t)plan_dt_size(d.dst_dt));
   if (im.bytes == 0) im.bytes = 16;
   return im;
 }
@@ -148,7 +148,7 @@ inline unsigned long long pe_algorithmic_ops(const dfx_patchembed_desc &d) {
   return 2ull * (unsigned long long)pe_rows(d) * (unsigned long long)d.oc * (unsigned long long)pe_k(d);
 }
 inline unsigned long long pe_algorithmic_bytes(const dfx_patchembed_desc &d, bool prefix) {
-  const unsigned esz = (unsigned)lin_dt_size(d.dst_dt);
+  const unsigned esz = (unsigned)plan_dt_size(d.dst_dt);
   return (unsigned long long)pe_rows(d) * pe_k(d) + (unsigned long long)d.oc * pe_k(d) + (unsigned long long)pe_rows(d) * d.oc * esz +
          (d.table ? 4ull * pe_tokens(d) * d.oc : d.bia_dt != DFX_UNDEF ? 4ull * d.oc : 0) + 4ull * d.nscales +
          (prefix ? (unsigned long long)d.bs * d.tok_offset * d.oc * esz : 0);
@@ -160,7 +160,7 @@ inline unsigned long long pe_src_extent(const dfx_patchembed_desc &d) {
 }
 inline unsigned long long pe_dst_extent(const dfx_patchembed_desc &d) {
   const unsigned long long last = (unsigned long long)(d.bs - 1) * d.img_rows + d.tok_offset + pe_tokens(d) - 1;  // the last token's row
-  return (last * d.dst_ld + d.oc) * (unsigned)lin_dt_size(d.dst_dt);
+  return (last * d.dst_ld + d.oc) * (unsigned)plan_dt_size(d.dst_dt);
 }
 
 }  // namespace dfx

@@ -3,13 +3,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include <vector>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "resize.cuh"
 #include "resize_plan.h"
 
@@ -32,6 +30,14 @@ struct dfx_resize {
 
 namespace {
 
+void release(dfx_resize *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  (void)hipFree(h->d_tables);
+  h->host.release();
+  delete h;
+}
+
 constexpr int kMaxBlocks = 256 * 8;  // grid-stride kernels: 8 workgroups per CU
 // Band length (measured, profiles/resize/): 8 output rows for bilinear, where a long band rebuilds fewer horizontal
 // interpolations; 2 for nearest, which has only a repeated source load to save.  Halved while the launch would have
@@ -44,9 +50,7 @@ constexpr long long kMaxElems = 1ll << 40;
 
 // launches since the library was loaded, by the kernel that ran ([DFX_RESIZE_BAND], [DFX_RESIZE_GENERIC]); process-wide,
 // because submit does not write to the handle (dfx_debug_resize_launches)
-std::atomic<long long> g_launches[2];
-
-const char *dt_name(int dt) { return dt == DFX_F32 ? "f32" : dt == DFX_S32 ? "s32" : dt == DFX_S8 ? "s8" : "u8"; }
+LaunchCounts<2> g_launches;
 
 int validate_resize(const dfx_resize_desc &d) {
   if (d.bs < 1 || d.c < 1) return fail(DFX_ERR_INVALID, "resize: bs and c must be at least 1");
@@ -89,27 +93,21 @@ int grid_for(long long items) {
 extern "C" {
 
 int dfx_resize_create(const dfx_resize_desc *desc, dfx_resize_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "resize_create: null argument");
-  *out = nullptr;
-  const dfx_resize_desc &d = *desc;
-  int rc = validate_resize(d);
-  if (rc) return rc;
-  const bool covered = band_class(d);
-  if (d.force_path == DFX_RESIZE_BAND && !covered)
-    return fail(DFX_ERR_UNSUPPORTED,
-                "resize_create: shape outside the band kernel's class (c * element size a multiple of 16; one image below 2^31 bytes)");
+  dfx_resize *h = nullptr;
   ResizeAxis ty, tx;
-  if (!resize_axis_plan(d.ih, d.oh, d.algo, d.coord, ty) || !resize_axis_plan(d.iw, d.ow, d.algo, d.coord, tx))
-    return fail(DFX_ERR_INVALID, "resize_create: no plan for this descriptor");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "resize_create: no HIP device (this library has no CPU path)");
-  dfx_resize *h = new (std::nothrow) dfx_resize();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
+  const int rc = open_create("resize", desc, out, &h, [&](const dfx_resize_desc &d) {
+    if (const int bad = validate_resize(d)) return bad;
+    if (d.force_path == DFX_RESIZE_BAND && !band_class(d))
+      return fail(DFX_ERR_UNSUPPORTED,
+                  "resize_create: shape outside the band kernel's class (c * element size a multiple of 16; one image below 2^31 bytes)");
+    if (!resize_axis_plan(d.ih, d.oh, d.algo, d.coord, ty) || !resize_axis_plan(d.iw, d.ow, d.algo, d.coord, tx))
+      return fail(DFX_ERR_INVALID, "resize_create: no plan for this descriptor");
+    return (int)DFX_OK;
+  });
+  if (rc) return rc;
+  const dfx_resize_desc &d = *desc;
   // AUTO RULE (include/dfx.h): the band kernel everywhere in its class
-  h->path = (covered && d.force_path != DFX_RESIZE_GENERIC) ? DFX_RESIZE_BAND : DFX_RESIZE_GENERIC;
+  h->path = (band_class(d) && d.force_path != DFX_RESIZE_GENERIC) ? DFX_RESIZE_BAND : DFX_RESIZE_GENERIC;
 
   // one device buffer: the four index tables, then the four weight tables
   const size_t oh = (size_t)d.oh, ow = (size_t)d.ow, words = 4 * (oh + ow);
@@ -123,8 +121,7 @@ int dfx_resize_create(const dfx_resize_desc *desc, dfx_resize_t **out) {
   hipError_t e = hipMalloc(&h->d_tables, words * 4);
   if (e == hipSuccess) e = hipMemcpy(h->d_tables, img.data(), words * 4, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    (void)hipFree(h->d_tables);
-    delete h;
+    release(h);
     return fail(DFX_ERR_HIP, "resize_create: table upload: %s", hipGetErrorString(e));
   }
   ResizeArgs a = {};
@@ -182,18 +179,11 @@ int dfx_resize_submit(dfx_resize_t *h, const void *src_dev, const void *add_dev,
   a.add = (const unsigned char *)add_dev;
   a.dst = (unsigned char *)dst_dev;
   const int rc = band ? launch_resize_band(a, h->band_grid, (hipStream_t)s) : launch_resize_generic(a, h->generic_grid, (hipStream_t)s);
-  if (rc != 0) return fail(DFX_ERR_UNSUPPORTED, "resize_submit: no kernel instance for this op");
-  HIP_TRY(hipGetLastError());
-  g_launches[band ? DFX_RESIZE_BAND : DFX_RESIZE_GENERIC].fetch_add(1, std::memory_order_relaxed);
-  return DFX_OK;
+  return g_launches.launched("resize", rc, band ? DFX_RESIZE_BAND : DFX_RESIZE_GENERIC);
 }
 
 // test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_resize_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_resize_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_resize_launches(int64_t out[2]) { return g_launches.read("resize", out); }
 
 int dfx_resize_submit_host(dfx_resize_t *h, const void *src_host, const void *add_host, void *dst_host) {
   if (!h || !src_host || !dst_host) return fail(DFX_ERR_INVALID, "resize_submit_host: null argument");
@@ -209,26 +199,18 @@ int dfx_resize_submit_host(dfx_resize_t *h, const void *src_host, const void *ad
 }
 
 int dfx_resize_query(const dfx_resize_t *h, dfx_resize_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "resize_query: null argument");
-  memset(info, 0, sizeof(*info));
+  if (const int rc = open_query("resize", h, info)) return rc;
   const bool band = h->path == DFX_RESIZE_BAND;
-  info->path = h->path;
   info->grid = band ? h->band_grid : h->generic_grid;
   info->block = 256;
   info->lds_bytes = 0;
-  info->device = h->device;
   info->rows_per_lane = band ? h->band.rows : 1;
   info->algorithmic_bytes = (uint64_t)src_bytes(h->d) + (uint64_t)dst_bytes(h->d) * (h->d.add ? 2 : 1);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_resize_destroy(dfx_resize_t *h) {
-  if (!h) return DFX_OK;
-  DeviceGuard dg(h->device);
-  (void)hipFree(h->d_tables);
-  h->host.release();
-  delete h;
+  release(h);
   return DFX_OK;
 }
 

@@ -3,12 +3,9 @@
 // The kernels are in roialign.cuh.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdio>
-#include <cstring>
-#include <new>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "roialign.cuh"
 #include "roialign_plan.h"
 
@@ -28,27 +25,24 @@ struct dfx_roialign {
 
 namespace {
 
+void release(dfx_roialign *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  delete h;
+}
+
 // submits since the library was loaded, by the kernel that ran (dfx_debug_roialign_launches)
-std::atomic<long long> g_launches[2];
+LaunchCounts<2> g_launches;
 
 }  // namespace
 
 extern "C" {
 
 int dfx_roialign_create(const dfx_roialign_desc *desc, dfx_roialign_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "roialign_create: null argument");
-  *out = nullptr;
+  dfx_roialign *h = nullptr;
+  const int rc = open_create("roialign", desc, out, &h, [](const dfx_roialign_desc &d) { return validated("roialign", roi_validate, d); });
+  if (rc) return rc;
   const dfx_roialign_desc &d = *desc;
-  const char *why = "";
-  const int rc = roi_validate(d, &why);
-  if (rc) return fail(rc, "roialign: %s", why);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "roialign_create: no HIP device (this library has no CPU path)");
-  dfx_roialign *h = new (std::nothrow) dfx_roialign();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   // AUTO RULE (include/dfx.h DFX_ROIALIGN_AUTO_NOTE)
   h->path = roi_path(d);
   RoiArgs &a = h->args;
@@ -97,7 +91,7 @@ int dfx_roialign_submit(dfx_roialign_t *h, const dfx_roialign_io *io, dfx_stream
   if (d.dt == DFX_F32) four |= (uintptr_t)io->dst;
   if (four % 4) return fail(DFX_ERR_INVALID, "roialign_submit: a pointer to 4-byte elements is not 4-byte aligned");
   for (int i = 0; i < n_in; ++i)
-    if (roi_overlap((uintptr_t)io->dst, roi_dst_extent(d), in_p[i], in_n[i])) return fail(DFX_ERR_INVALID, "roialign_submit: dst overlaps an input");
+    if (plan_overlap((uintptr_t)io->dst, roi_dst_extent(d), in_p[i], in_n[i])) return fail(DFX_ERR_INVALID, "roialign_submit: dst overlaps an input");
   DeviceGuard dg(h->device);
   const hipStream_t st = (hipStream_t)s;
   // 16-byte loads and stores need aligned buffers: others take the generic kernel for this submit, as in dfx_nms
@@ -111,36 +105,28 @@ int dfx_roialign_submit(dfx_roialign_t *h, const dfx_roialign_io *io, dfx_stream
   if (path == DFX_ROIALIGN_TILE) launch_roialign_tile(a, d.dt, roi_tile_grid(d), st);
   else launch_roialign_generic(a, d.dt, roi_generic_grid(d), st);
   HIP_TRY(hipGetLastError());
-  g_launches[path].fetch_add(1, std::memory_order_relaxed);
+  g_launches.hit(path);
   return DFX_OK;
 }
 
 // test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_roialign_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_roialign_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_roialign_launches(int64_t out[2]) { return g_launches.read("roialign", out); }
 
 int dfx_roialign_query(const dfx_roialign_t *h, dfx_roialign_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "roialign_query: null argument");
-  memset(info, 0, sizeof(*info));
+  if (const int rc = open_query("roialign", h, info)) return rc;
   const dfx_roialign_desc &d = h->d;
   const bool tile = h->path == DFX_ROIALIGN_TILE;
-  info->path = h->path;
   info->grid = roi_grid(d, h->path);
   info->block = ROI_THREADS;
   info->lds_bytes = roi_lds_bytes(h->path);
   info->launches = 1;
-  info->device = h->device;
   info->rows_per_group = tile ? roi_rows_per_group(d) : 0;
   info->algorithmic_bytes = roi_algorithmic_bytes(d);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_roialign_destroy(dfx_roialign_t *h) {
-  delete h;
+  release(h);
   return DFX_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/dfx.h"
+#include "plan_common.h"
 
 namespace dfx {
 
@@ -37,9 +38,6 @@ inline unsigned long long roi_dst_extent(const dfx_roialign_desc &d) {
   return ((px - 1) * (unsigned)d.dst_ld + (unsigned)d.c) * roi_esize(d.dt);
 }
 inline unsigned long long roi_boxes_extent(const dfx_roialign_desc &d) { return roi_rows(d) * 16; }
-inline bool roi_overlap(uintptr_t a, unsigned long long abytes, uintptr_t b, unsigned long long bbytes) {
-  return a < b + bbytes && b < a + abytes;
-}
 
 // the tile kernel's class (the pointers' alignment is checked per submit)
 inline bool roi_tile_class(const dfx_roialign_desc &d) {

@@ -4,13 +4,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <new>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "select.cuh"
 #include "select_plan.h"
 
@@ -37,9 +34,6 @@ struct dfx_select {
 
 namespace {
 
-// submits since the library was loaded, by the path that ran (dfx_debug_select_launches)
-std::atomic<long long> g_launches[2];
-
 void release(dfx_select *h) {
   if (!h) return;
   DeviceGuard dg(h->device);
@@ -48,26 +42,23 @@ void release(dfx_select *h) {
   delete h;
 }
 
+// submits since the library was loaded, by the path that ran (dfx_debug_select_launches)
+LaunchCounts<2> g_launches;
+
 }  // namespace
 
 extern "C" {
 
 int dfx_select_create(const dfx_select_desc *desc, dfx_select_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "select_create: null argument");
-  *out = nullptr;
+  dfx_select *h = nullptr;
+  const int rc = open_create("select", desc, out, &h, [](const dfx_select_desc &d) {
+    if (const int bad = validated("select", select_validate, d)) return bad;
+    if (d.force_path == DFX_SELECT_HIST && !select_hist_class(d))
+      return fail(DFX_ERR_UNSUPPORTED, "select_create: descriptor outside the histogram path's class (src_ld a multiple of 16)");
+    return (int)DFX_OK;
+  });
+  if (rc) return rc;
   const dfx_select_desc &d = *desc;
-  const char *why = "";
-  const int rc = select_validate(d, &why);
-  if (rc) return fail(rc, "select: %s", why);
-  if (d.force_path == DFX_SELECT_HIST && !select_hist_class(d))
-    return fail(DFX_ERR_UNSUPPORTED, "select_create: descriptor outside the histogram path's class (src_ld a multiple of 16)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "select_create: no HIP device (this library has no CPU path)");
-  dfx_select *h = new (std::nothrow) dfx_select();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   // AUTO RULE (include/dfx.h DFX_SELECT_AUTO_NOTE)
   h->path = select_path(d);
   const long long px = (long long)d.h * d.w;
@@ -137,9 +128,9 @@ int dfx_select_submit(dfx_select_t *h, const void *src_dev, void *idx_dev, void 
   }
   for (int o = 0; o < n_out; ++o) {
     for (int i = 0; i < n_in; ++i)
-      if (select_overlap(out_p[o], out_n[o], in_p[i], in_n[i])) return fail(DFX_ERR_INVALID, "select_submit: an output overlaps src or a gather source");
+      if (plan_overlap(out_p[o], out_n[o], in_p[i], in_n[i])) return fail(DFX_ERR_INVALID, "select_submit: an output overlaps src or a gather source");
     for (int p = o + 1; p < n_out; ++p)
-      if (select_overlap(out_p[o], out_n[o], out_p[p], out_n[p])) return fail(DFX_ERR_INVALID, "select_submit: two outputs overlap");
+      if (plan_overlap(out_p[o], out_n[o], out_p[p], out_n[p])) return fail(DFX_ERR_INVALID, "select_submit: two outputs overlap");
   }
   DeviceGuard dg(h->device);
   const hipStream_t st = (hipStream_t)s;
@@ -158,7 +149,7 @@ int dfx_select_submit(dfx_select_t *h, const void *src_dev, void *idx_dev, void 
   if (path == DFX_SELECT_GENERIC) {  // one launch, nothing of the handle's: independent of every other submit
     launch_select_generic(a, image_grid, st);
     HIP_TRY(hipGetLastError());
-    g_launches[DFX_SELECT_GENERIC].fetch_add(1, std::memory_order_relaxed);
+    g_launches.hit(DFX_SELECT_GENERIC);
     return DFX_OK;
   }
   // four launches through the handle's scratch: serialised (dfx.h; TwoLaunchOrder in dfx_internal.h)
@@ -182,22 +173,16 @@ int dfx_select_submit(dfx_select_t *h, const void *src_dev, void *idx_dev, void 
   // (once a launch is out the scratch has a writer in flight: every way out goes through leave())
   rc = h->order.leave(st);
   if (e != hipSuccess) return fail(DFX_ERR_HIP, "select_submit: %s", hipGetErrorString(e));
-  if (rc == DFX_OK) g_launches[DFX_SELECT_HIST].fetch_add(1, std::memory_order_relaxed);
+  if (rc == DFX_OK) g_launches.hit(DFX_SELECT_HIST);
   return rc;
 }
 
 // test hook: how many submits have run on each path so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_select_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_select_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_select_launches(int64_t out[2]) { return g_launches.read("select", out); }
 
 int dfx_select_query(const dfx_select_t *h, dfx_select_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "select_query: null argument");
-  memset(info, 0, sizeof(*info));
+  if (const int rc = open_query("select", h, info)) return rc;
   const bool hist = h->path == DFX_SELECT_HIST;
-  info->path = h->path;
   info->chunks = h->args.chunks;
   info->chunk_pixels = h->args.chunk_px;
   info->grid = hist ? h->plan.grid : select_image_grid(h->d.bs);
@@ -206,10 +191,8 @@ int dfx_select_query(const dfx_select_t *h, dfx_select_info *info) {
   info->block_image = SELECT_SORT_THREADS;
   info->lds_bytes = select_lds_bytes(h->path);
   info->launches = select_launches(h->path);
-  info->device = h->device;
   info->scratch_bytes = hist ? h->layout.bytes : 0;
   info->algorithmic_bytes = select_algorithmic_bytes(h->d);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 

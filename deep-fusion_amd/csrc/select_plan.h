@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/dfx.h"
+#include "plan_common.h"
 
 #if defined(__HIPCC__)
 #define SELECT_HD __host__ __device__ inline
@@ -151,9 +152,6 @@ inline unsigned long long select_gather_src_extent(const dfx_select_desc &d, int
 }
 inline unsigned long long select_gather_dst_extent(const dfx_select_desc &d, int i) {
   return (unsigned long long)d.bs * d.k * (unsigned)d.row_bytes[i];
-}
-inline bool select_overlap(uintptr_t a, unsigned long long abytes, uintptr_t b, unsigned long long bbytes) {
-  return a < b + bbytes && b < a + abytes;
 }
 
 // what one submit must read and write: the valid src elements, idx, count, and with_val / the gather rows

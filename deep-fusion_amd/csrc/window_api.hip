@@ -3,15 +3,11 @@
 // window_plan.h), launches.  The kernels are in window.cuh.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
 #include <cstdio>
-#include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "window.cuh"
 #include "window_plan.h"
 
@@ -31,16 +27,16 @@ struct dfx_window {
 
 namespace {
 
+void release(dfx_window *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  (void)hipFree(h->d_map);
+  delete h;
+}
+
 // launches since the library was loaded, by the kernel that ran; process-wide, because submit does not write to the
 // handle (dfx_debug_window_launches)
-std::atomic<long long> g_launches[2];
-
-const char *dt_name(int dt) { return dt == DFX_F32 ? "f32" : dt == DFX_S32 ? "s32" : dt == DFX_S8 ? "s8" : "u8"; }
-
-long long grid_cap() {
-  const char *e = tuning_value("DFX_WINDOW_GRID");  // testing aid
-  return e ? std::max(1ll, atoll(e)) : 0;
-}
+LaunchCounts<2> g_launches;
 
 void set_name(dfx_window *h) {
   const dfx_window_desc &d = h->d;
@@ -57,22 +53,16 @@ void set_name(dfx_window *h) {
 extern "C" {
 
 int dfx_window_create(const dfx_window_desc *desc, dfx_window_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "window_create: null argument");
-  *out = nullptr;
+  dfx_window *h = nullptr;
+  const int rc = open_create("window", desc, out, &h, [](const dfx_window_desc &d) {
+    if (const int bad = validated("window", window_validate, d)) return bad;
+    if (d.force_path != -1 && !window_in_class(d, d.force_path))
+      return fail(DFX_ERR_UNSUPPORTED, "window_create: descriptor outside the forced path's class (row: c, grid_ld and win_ld times the "
+                                       "element size multiples of 16)");
+    return (int)DFX_OK;
+  });
+  if (rc) return rc;
   const dfx_window_desc &d = *desc;
-  const char *why = "";
-  int rc = window_validate(d, &why);
-  if (rc) return fail(rc, "window: %s", why);
-  if (d.force_path != -1 && !window_in_class(d, d.force_path))
-    return fail(DFX_ERR_UNSUPPORTED, "window_create: descriptor outside the forced path's class (row: c, grid_ld and win_ld times the "
-                                     "element size multiples of 16)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "window_create: no HIP device (this library has no CPU path)");
-  dfx_window *h = new (std::nothrow) dfx_window();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   // AUTO RULE (include/dfx.h DFX_WINDOW_AUTO_NOTE)
   h->path = window_path(d);
   std::vector<int32_t> map;
@@ -80,11 +70,10 @@ int dfx_window_create(const dfx_window_desc *desc, dfx_window_t **out) {
   hipError_t e = hipMalloc((void **)&h->d_map, map.size() * sizeof(int32_t));
   if (e == hipSuccess) e = hipMemcpy(h->d_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    (void)hipFree(h->d_map);
-    delete h;
+    release(h);
     return fail(DFX_ERR_HIP, "window_create: row map: %s", hipGetErrorString(e));
   }
-  const long long cap = grid_cap();
+  const long long cap = grid_cap("DFX_WINDOW_GRID");
   h->grid[h->path] = window_grid(d, h->path, cap);
   h->grid[DFX_WINDOW_GENERIC] = window_grid(d, DFX_WINDOW_GENERIC, cap);
   set_name(h);
@@ -95,10 +84,10 @@ int dfx_window_create(const dfx_window_desc *desc, dfx_window_t **out) {
 int dfx_window_submit(dfx_window_t *h, const void *src_dev, void *dst_dev, dfx_stream_t s) {
   if (!h || !src_dev || !dst_dev) return fail(DFX_ERR_INVALID, "window_submit: null argument");
   const dfx_window_desc &d = h->d;
-  const int es = window_dt_size(d.dt);
+  const int es = plan_dt_size(d.dt);
   const uintptr_t src = (uintptr_t)src_dev, dst = (uintptr_t)dst_dev;
   if ((src | dst) % es) return fail(DFX_ERR_INVALID, "window_submit: a 4-byte tensor is not 4-byte aligned");
-  if (window_overlap(src, window_src_extent(d), dst, window_dst_extent(d)))
+  if (plan_overlap(src, window_src_extent(d), dst, window_dst_extent(d)))
     return fail(DFX_ERR_INVALID, "window_submit: dst overlaps src (a permutation cannot run in place)");
   DeviceGuard dg(h->device);
   // 16-byte loads and stores need aligned buffers: others take the generic kernel for this submit, as lnorm does
@@ -116,36 +105,22 @@ int dfx_window_submit(dfx_window_t *h, const void *src_dev, void *dst_dev, dfx_s
   a.esize = es;
   a.lanes = path == DFX_WINDOW_ROW ? (int)window_lanes(d) : 0;
   a.pad = es == 1 ? (d.pad_value & 0xffu) * 0x01010101u : d.pad_value;
-  if (launch_window(a, path, h->grid[path], (hipStream_t)s) != 0) return fail(DFX_ERR_UNSUPPORTED, "window_submit: no kernel instance for this op");
-  HIP_TRY(hipGetLastError());
-  g_launches[path].fetch_add(1, std::memory_order_relaxed);
-  return DFX_OK;
+  return g_launches.launched("window", launch_window(a, path, h->grid[path], (hipStream_t)s), path);
 }
 
 // test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_window_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_window_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_window_launches(int64_t out[2]) { return g_launches.read("window", out); }
 
 int dfx_window_query(const dfx_window_t *h, dfx_window_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "window_query: null argument");
-  memset(info, 0, sizeof(*info));
-  info->path = h->path;
+  if (const int rc = open_query("window", h, info)) return rc;
   info->grid = h->grid[h->path];
   info->block = WINDOW_THREADS;
-  info->device = h->device;
   info->algorithmic_bytes = window_algorithmic_bytes(h->d);
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_window_destroy(dfx_window_t *h) {
-  if (!h) return DFX_OK;
-  DeviceGuard dg(h->device);
-  (void)hipFree(h->d_map);
-  delete h;
+  release(h);
   return DFX_OK;
 }
 

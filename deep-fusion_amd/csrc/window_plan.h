@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/dfx.h"
+#include "plan_common.h"
 
 namespace dfx {
 
@@ -20,7 +21,6 @@ constexpr int WINDOW_UNROLL = 4;                     // row kernel: 16-byte grou
 constexpr long long WINDOW_MAX_ELEMS = 1ll << 40;    // window-side rows * the larger leading dimension, inclusive
 
 inline bool window_dt_ok(int dt) { return dt == DFX_U8 || dt == DFX_S8 || dt == DFX_S32 || dt == DFX_F32; }
-inline int window_dt_size(int dt) { return (dt == DFX_F32 || dt == DFX_S32) ? 4 : 1; }
 inline bool window_path_ok(int p) { return p == DFX_WINDOW_ROW || p == DFX_WINDOW_GENERIC; }
 
 // the padded map (valid once h, w, wh, ww have passed window_validate)
@@ -93,14 +93,14 @@ inline long long window_pad_tokens(const dfx_window_desc &d) { return (long long
 
 // the class of a path, as far as the descriptor decides it (pointer alignment is checked per submit)
 inline bool window_row_class(const dfx_window_desc &d) {
-  const long long es = window_dt_size(d.dt);
+  const long long es = plan_dt_size(d.dt);
   return ((long long)d.c * es) % 16 == 0 && (d.grid_ld * es) % 16 == 0 && (d.win_ld * es) % 16 == 0;
 }
 inline bool window_in_class(const dfx_window_desc &d, int path) {
   return path == DFX_WINDOW_ROW ? window_row_class(d) : path == DFX_WINDOW_GENERIC;
 }
 // row kernel: consecutive lanes that move one token
-inline long long window_lanes(const dfx_window_desc &d) { return (long long)d.c * window_dt_size(d.dt) / 16; }
+inline long long window_lanes(const dfx_window_desc &d) { return (long long)d.c * plan_dt_size(d.dt) / 16; }
 
 // the handle's path.  AUTO RULE (include/dfx.h DFX_WINDOW_AUTO_NOTE): the row kernel is unmeasured, so nothing takes it on
 // auto; it runs where force_path asks for it.
@@ -125,23 +125,16 @@ inline int window_grid(const dfx_window_desc &d, int path, long long cap) {
   return (int)(blocks < 1 ? 1 : blocks);
 }
 
-// bytes from a buffer's first to behind its last touched byte: rows `ld` elements apart, `cols` touched per row
-inline unsigned long long window_extent(long long rows, long long ld, int cols, int esize) {
-  return ((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned)cols) * (unsigned)esize;
-}
 inline unsigned long long window_src_extent(const dfx_window_desc &d) {
-  return window_extent((long long)d.bs * window_src_rows(d), window_src_ld(d), d.c, window_dt_size(d.dt));
+  return plan_extent((long long)d.bs * window_src_rows(d), window_src_ld(d), d.c, plan_dt_size(d.dt));
 }
 inline unsigned long long window_dst_extent(const dfx_window_desc &d) {
-  return window_extent((long long)d.bs * window_dst_rows(d), window_dst_ld(d), d.c, window_dt_size(d.dt));
-}
-inline bool window_overlap(uintptr_t a, unsigned long long abytes, uintptr_t b, unsigned long long bbytes) {
-  return a < b + bbytes && b < a + abytes;
+  return plan_extent((long long)d.bs * window_dst_rows(d), window_dst_ld(d), d.c, plan_dt_size(d.dt));
 }
 
 // what one submit must read and write: the valid bytes of the tokens read (pad tokens are not), of the tokens written, the map
 inline unsigned long long window_algorithmic_bytes(const dfx_window_desc &d) {
-  const unsigned long long token = (unsigned long long)d.c * window_dt_size(d.dt);
+  const unsigned long long token = (unsigned long long)d.c * plan_dt_size(d.dt);
   const unsigned long long grid = (unsigned long long)d.bs * window_grid_rows(d), win = (unsigned long long)d.bs * window_win_rows(d);
   return (grid + (d.dir == DFX_WINDOW_PARTITION ? win : grid)) * token + 4ull * (unsigned long long)window_dst_rows(d);
 }

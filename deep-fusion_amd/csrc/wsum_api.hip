@@ -3,16 +3,13 @@
 // (all planned in wsum_plan.h), launches.  The kernels are in wsum.cuh.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
-#include "dfx_internal.h"
+#include "path_op.h"
 #include "wsum.cuh"
 #include "wsum_plan.h"
 
@@ -37,49 +34,43 @@ struct dfx_wsum {
 
 namespace {
 
+void release(dfx_wsum *h) {
+  if (!h) return;
+  DeviceGuard dg(h->device);
+  (void)hipFree(h->d_image);
+  h->host.release();
+  delete h;
+}
+
 // launches since the library was loaded, by the kernel that ran ([DFX_WSUM_VEC], [DFX_WSUM_GENERIC]); process-wide,
 // because submit does not write to the handle (dfx_debug_wsum_launches)
-std::atomic<long long> g_launches[2];
-
-const char *dt_name(int dt) { return dt == DFX_F32 ? "f32" : dt == DFX_S32 ? "s32" : dt == DFX_S8 ? "s8" : "u8"; }
+LaunchCounts<2> g_launches;
 
 size_t tensor_bytes(const dfx_wsum_desc &d, int dt) { return (size_t)wsum_elems(d) * dt_size(dt); }
-
-long long grid_cap() {
-  const char *e = tuning_value("DFX_WSUM_GRID");  // testing aid
-  return e ? std::max(1ll, atoll(e)) : 0;
-}
 
 }  // namespace
 
 extern "C" {
 
 int dfx_wsum_create(const dfx_wsum_desc *desc, dfx_wsum_t **out) {
-  if (!desc || !out) return fail(DFX_ERR_INVALID, "wsum_create: null argument");
-  *out = nullptr;
+  dfx_wsum *h = nullptr;
+  const int rc = open_create("wsum", desc, out, &h, [](const dfx_wsum_desc &d) {
+    if (const int bad = validated("wsum", wsum_validate, d)) return bad;
+    if (d.force_path == DFX_WSUM_VEC && !wsum_vec_class(d))
+      return fail(DFX_ERR_UNSUPPORTED,
+                  "wsum_create: shape outside the vec kernel's class (c a multiple of 16; per-channel constants and table within 64 KiB)");
+    return (int)DFX_OK;
+  });
+  if (rc) return rc;
   const dfx_wsum_desc &d = *desc;
-  const char *why = "";
-  int rc = wsum_validate(d, &why);
-  if (rc) return fail(rc, "wsum: %s", why);
-  const bool covered = wsum_vec_class(d);
-  if (d.force_path == DFX_WSUM_VEC && !covered)
-    return fail(DFX_ERR_UNSUPPORTED,
-                "wsum_create: shape outside the vec kernel's class (c a multiple of 16; per-channel constants and table within 64 KiB)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(DFX_ERR_NO_DEVICE, "wsum_create: no HIP device (this library has no CPU path)");
-  dfx_wsum *h = new (std::nothrow) dfx_wsum();
-  if (!h) return fail(DFX_ERR_HIP, "out of host memory");
-  h->d = d;
   for (int i = d.n_inputs; i < DFX_WSUM_MAX_INPUTS; ++i) h->d.src_dt[i] = h->d.nscales[i] = 0;
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   // AUTO RULE (include/dfx.h DFX_WSUM_AUTO_NOTE)
   h->path = wsum_path(d);
   h->img = wsum_image(d);
   if (h->img.bytes) {
     const hipError_t e = hipMalloc((void **)&h->d_image, (size_t)h->img.bytes);
     if (e != hipSuccess) {
-      delete h;
+      release(h);
       return fail(DFX_ERR_HIP, "wsum_create: constants: %s", hipGetErrorString(e));
     }
   }
@@ -95,7 +86,7 @@ int dfx_wsum_create(const dfx_wsum_desc *desc, dfx_wsum_t **out) {
   a.relu = d.post_relu; a.rm = d.round_mode; a.dst_dt = d.dst_dt; a.lut_in_dt = d.lut_in_dt;
   a.image_bytes = (int)h->img.bytes;
   a.lut_off = h->img.lut_off < 0 ? 0 : (int)h->img.lut_off;
-  const long long cap = grid_cap();
+  const long long cap = grid_cap("DFX_WSUM_GRID");
   h->generic_grid = wsum_grid(wsum_items(d, DFX_WSUM_GENERIC), cap);
   if (h->path == DFX_WSUM_VEC) h->vec_grid = wsum_grid(wsum_items(d, DFX_WSUM_VEC), cap);
 
@@ -165,18 +156,11 @@ int dfx_wsum_submit(dfx_wsum_t *h, const void *const *srcs_dev, void *dst_dev, d
   a.dst = (unsigned char *)dst_dev;
   a.total = wsum_items(d, vec ? DFX_WSUM_VEC : DFX_WSUM_GENERIC);
   const int rc = vec ? launch_wsum_vec(a, h->vec_grid, (hipStream_t)s) : launch_wsum_generic(a, h->generic_grid, (hipStream_t)s);
-  if (rc != 0) return fail(DFX_ERR_UNSUPPORTED, "wsum_submit: no kernel instance for this op");
-  HIP_TRY(hipGetLastError());
-  g_launches[vec ? DFX_WSUM_VEC : DFX_WSUM_GENERIC].fetch_add(1, std::memory_order_relaxed);
-  return DFX_OK;
+  return g_launches.launched("wsum", rc, vec ? DFX_WSUM_VEC : DFX_WSUM_GENERIC);
 }
 
 // test hook: how many submits have launched each kernel so far (shows the per-submit fallback, which query cannot)
-int dfx_debug_wsum_launches(int64_t out[2]) {
-  if (!out) return fail(DFX_ERR_INVALID, "debug_wsum_launches: null argument");
-  for (int k = 0; k < 2; ++k) out[k] = g_launches[k].load(std::memory_order_relaxed);
-  return DFX_OK;
-}
+int dfx_debug_wsum_launches(int64_t out[2]) { return g_launches.read("wsum", out); }
 
 int dfx_wsum_submit_host(dfx_wsum_t *h, const void *const *srcs_host, void *dst_host) {
   if (!h || !srcs_host || !dst_host) return fail(DFX_ERR_INVALID, "wsum_submit_host: null argument");
@@ -192,27 +176,19 @@ int dfx_wsum_submit_host(dfx_wsum_t *h, const void *const *srcs_host, void *dst_
 }
 
 int dfx_wsum_query(const dfx_wsum_t *h, dfx_wsum_info *info) {
-  if (!h || !info) return fail(DFX_ERR_INVALID, "wsum_query: null argument");
-  memset(info, 0, sizeof(*info));
+  if (const int rc = open_query("wsum", h, info)) return rc;
   const bool vec = h->path == DFX_WSUM_VEC;
-  info->path = h->path;
   info->grid = vec ? h->vec_grid : h->generic_grid;
   info->block = WSUM_THREADS;
   info->lds_bytes = vec ? (int)h->img.bytes : 0;
-  info->device = h->device;
   uint64_t bytes = tensor_bytes(h->d, h->d.dst_dt);
   for (int i = 0; i < h->d.n_inputs; ++i) bytes += tensor_bytes(h->d, h->d.src_dt[i]);
   info->algorithmic_bytes = bytes;
-  memcpy(info->kernel_name, h->kernel_name, sizeof(info->kernel_name));
   return DFX_OK;
 }
 
 int dfx_wsum_destroy(dfx_wsum_t *h) {
-  if (!h) return DFX_OK;
-  DeviceGuard dg(h->device);
-  (void)hipFree(h->d_image);
-  h->host.release();
-  delete h;
+  release(h);
   return DFX_OK;
 }
 

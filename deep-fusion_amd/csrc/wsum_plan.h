@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/dfx.h"
+#include "plan_common.h"
 
 namespace dfx {
 
@@ -20,7 +21,6 @@ constexpr long long WSUM_MAX_LDS = 64 * 1024;       // the staged constants of t
 constexpr long long WSUM_AUTO_MIN_ELEMS = 1ll << 19; // auto takes the vec kernel from this many elements on (128 workgroups)
 
 inline bool wsum_src_dt_ok(int dt) { return dt == DFX_F32 || dt == DFX_S32 || dt == DFX_S8 || dt == DFX_U8; }
-inline int wsum_dt_size(int dt) { return (dt == DFX_F32 || dt == DFX_S32) ? 4 : 1; }
 
 // DFX_OK, or the code dfx_wsum_create returns with *why set to the reason
 inline int wsum_validate(const dfx_wsum_desc &d, const char **why) {
@@ -102,9 +102,9 @@ enum {
 };
 inline int wsum_alias(int n, const uintptr_t *src, const int *src_dt, uintptr_t dst, int dst_dt, unsigned long long elems) {
   int kind = WSUM_ALIAS_NONE;
-  const unsigned long long dbytes = elems * (unsigned)wsum_dt_size(dst_dt);
+  const unsigned long long dbytes = elems * (unsigned)plan_dt_size(dst_dt);
   for (int i = 0; i < n; ++i) {
-    const unsigned long long sbytes = elems * (unsigned)wsum_dt_size(src_dt[i]);
+    const unsigned long long sbytes = elems * (unsigned)plan_dt_size(src_dt[i]);
     if (src[i] == dst && sbytes == dbytes) {
       kind = WSUM_ALIAS_IN_PLACE;
       continue;

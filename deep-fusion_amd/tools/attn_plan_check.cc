@@ -35,9 +35,9 @@ static dfx_attn_desc dense(int b0, int b1, int tq, int tk, int d, int dv) {
   a.batch0 = b0; a.batch1 = b1; a.tq = tq; a.tk = tk; a.d = d; a.dv = dv;
   a.q_dt = DFX_S8; a.k_dt = DFX_S8; a.v_dt = DFX_S8; a.dst_dt = DFX_S8; a.round_mode = DFX_ROUND_NEAREST; a.nscales = 1; a.force_path = -1;
   a.prob_scale = 255.0f;
-  a.ldq = attn_up16(d); a.q_s1 = a.ldq * tq; a.q_s0 = a.q_s1 * b1;
-  a.ldk = attn_up16(d); a.k_s1 = a.ldk * tk; a.k_s0 = a.k_s1 * b1;
-  a.ldv = attn_up16(dv); a.v_s1 = a.ldv * tk; a.v_s0 = a.v_s1 * b1;
+  a.ldq = plan_up16(d); a.q_s1 = a.ldq * tq; a.q_s0 = a.q_s1 * b1;
+  a.ldk = plan_up16(d); a.k_s1 = a.ldk * tk; a.k_s0 = a.k_s1 * b1;
+  a.ldv = plan_up16(dv); a.v_s1 = a.ldv * tk; a.v_s0 = a.v_s1 * b1;
   a.ldo = dv; a.o_s1 = a.ldo * tq; a.o_s0 = a.o_s1 * b1;
   return a;
 }
@@ -181,7 +181,7 @@ int main(int argc, char **argv) {
       EXPECT(bmm_b_elems(bl) == 1023ull * (1ull << 30) + 1023ull * (1ull << 20) + 15ull * (1ull << 16) + 16 && bmm_b_elems(bo) == bmm_b_elems(bl));
       const uintptr_t far = (uintptr_t)1 << 47;
       const unsigned long long ob = 4 * bmm_c_elems(bo);
-      EXPECT(bmm_overlap(far, ob, far + ob - 1, 1) && !bmm_overlap(far, ob, far + ob, 16) && !bmm_overlap(far, ob, far - 16, 16) && bmm_overlap(far, ob, far - 16, 17));
+      EXPECT(plan_overlap(far, ob, far + ob - 1, 1) && !plan_overlap(far, ob, far + ob, 16) && !plan_overlap(far, ob, far - 16, 16) && plan_overlap(far, ob, far - 16, 17));
     }
     EXPECT(attn_strips(d) == 1ll << 25 && attn_grid(d, 256, 0) == 2048 && attn_grid(d, 256, 1ll << 40) == 2048);
     EXPECT(attn_algorithmic_ops(d) == 2ull * (1ull << 38) * 2);

@@ -177,7 +177,7 @@ int main(int argc, char **argv) {
     d.lda -= 1008; d.c_s1 -= 1; EXPECT(rc(d) == DFX_ERR_INVALID);    // (C's matrices would meet)
     const uintptr_t far = (uintptr_t)1 << 47;
     const unsigned long long cb = 4 * ((1ull << 40) - 1024 + 16);
-    EXPECT(bmm_overlap(far, cb, far + cb - 1, 1) && !bmm_overlap(far, cb, far + cb, 16) && !bmm_overlap(far, cb, far - 16, 16) && bmm_overlap(far, cb, far - 16, 17));
+    EXPECT(plan_overlap(far, cb, far + cb - 1, 1) && !plan_overlap(far, cb, far + cb, 16) && !plan_overlap(far, cb, far - 16, 16) && plan_overlap(far, cb, far - 16, 17));
   }
   // ---- INVALID before UNSUPPORTED; the MFMA class
   {
@@ -253,7 +253,7 @@ int main(int argc, char **argv) {
     EXPECT(bmm_lds_bytes(d, DFX_BMM_MFMA) == BMM_NN_LDS && BMM_NN_LDS == 12288);
     d = dense(65535, 65535, 1, 1, 1, 1);
     EXPECT(rc(d) == DFX_OK && bmm_grid(d, DFX_BMM_MFMA, 256, 0) == 256 * BMM_GRID_PER_CU);
-    EXPECT(bmm_overlap(100, 10, 109, 1) && !bmm_overlap(100, 10, 110, 1) && !bmm_overlap(110, 1, 100, 10));
+    EXPECT(plan_overlap(100, 10, 109, 1) && !plan_overlap(100, 10, 110, 1) && !plan_overlap(110, 1, 100, 10));
   }
   if (g_bad) {
     printf("bmm_plan_check: %d checks failed\n", g_bad);

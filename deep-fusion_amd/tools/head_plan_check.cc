@@ -112,7 +112,7 @@ int main() {
     for (int k = 1; k <= 8; ++k)
       for (int ld = 8; ld <= 200; ++ld) {
         const dfx_head_desc d = topk(7, 8, ld, dt, k, DFX_S32);
-        const int es = head_dt_size(dt);
+        const int es = plan_dt_size(dt);
         EXPECT(head_pixel_class(d) == (es == 1 && k == 1 && ld % 16 == 0 && ld <= 160));
         EXPECT(head_row_class(d) == ((ld * es) % 16 == 0));
         EXPECT(head_in_class(d, DFX_HEAD_GENERIC) && head_in_class(d, DFX_HEAD_PIXEL) == head_pixel_class(d) &&
@@ -175,18 +175,19 @@ int main() {
   EXPECT(head_lds_bytes(softmax(4, 21, 32, DFX_U8, DFX_U8, 21), DFX_HEAD_PIXEL) == 1024 && head_lds_bytes(softmax(4, 21, 32, DFX_U8, DFX_U8, 21), DFX_HEAD_GENERIC) == 0);
   EXPECT(head_lds_bytes(topk(4, 21, 32, DFX_U8, 1, DFX_U8), DFX_HEAD_ROW) == 0);
   // ---- extents, overlap, bytes
-  EXPECT(head_extent(1, 32, 21, 1) == 21 && head_extent(3, 32, 21, 4) == (2 * 32 + 21) * 4);
-  EXPECT(head_extent(1ll << 35, 32, 32, 4) == (1ull << 42));
+  EXPECT(plan_extent(1, 32, 21, 1) == 21 && plan_extent(3, 32, 21, 4) == (2 * 32 + 21) * 4);
+  EXPECT(plan_extent(1ll << 35, 32, 32, 4) == (1ull << 42));
   // the documented maximum rows * ld = 2^40 at both ends of the pitch's range, 4-byte elements; the pitches of tests/far_offsets.py
-  EXPECT(head_extent(1ll << 40, 1, 1, 4) == (1ull << 42) && head_extent(513, 2147483647, 65535, 4) == (512ull * 2147483647ull + 65535) * 4);
-  EXPECT(head_extent(5, (1 << 30) + 4160, 21, 1) == (1ull << 32) + 4 * 4160 + 21 && head_extent(3, (1 << 29) + 1040, 5, 4) == (1ull << 32) + 8320 + 20);
+  EXPECT(plan_extent(1ll << 40, 1, 1, 4) == (1ull << 42) && plan_extent(513, 2147483647, 65535, 4) == (512ull * 2147483647ull + 65535) * 4);
+  EXPECT(plan_extent(5, (1 << 30) + 4160, 21, 1) == (1ull << 32) + 4 * 4160 + 21 && plan_extent(3, (1 << 29) + 1040, 5, 4) == (1ull << 32) + 8320 + 20);
+  EXPECT(plan_extent(3, (1ll << 31) + 4160, 40, 1) == (1ull << 32) + 8320 + 40);  // (a pitch above 2^31: the shared extent takes 64-bit pitches)
   EXPECT(head_algorithmic_bytes(topk(1ll << 40, 1, 1, DFX_F32, 1, DFX_S32)) == 8 * (1ull << 40));
   {
     const uintptr_t far = (uintptr_t)1 << 47;  // an operand of 2^42 bytes against a neighbour on either side
-    EXPECT(head_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !head_overlap(far, 1ull << 42, far + (1ull << 42), 16) &&
-           !head_overlap(far, 1ull << 42, far - 16, 16) && head_overlap(far, 1ull << 42, far - 16, 17));
+    EXPECT(plan_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !plan_overlap(far, 1ull << 42, far + (1ull << 42), 16) &&
+           !plan_overlap(far, 1ull << 42, far - 16, 16) && plan_overlap(far, 1ull << 42, far - 16, 17));
   }
-  EXPECT(head_overlap(100, 10, 109, 5) && !head_overlap(100, 10, 110, 5) && !head_overlap(110, 5, 100, 10) && head_overlap(100, 10, 90, 11));
+  EXPECT(plan_overlap(100, 10, 109, 5) && !plan_overlap(100, 10, 110, 5) && !plan_overlap(110, 5, 100, 10) && plan_overlap(100, 10, 90, 11));
   EXPECT(head_algorithmic_bytes(topk(70, 21, 32, DFX_U8, 1, DFX_U8)) == 70 * 21 + 70);
   EXPECT(head_algorithmic_bytes(topk(3, 1000, 1000, DFX_F32, 5, DFX_S32)) == 3 * 1000 * 4 + 3 * 5 * 4);
   EXPECT(head_algorithmic_bytes(softmax(70, 21, 32, DFX_S8, DFX_F32, 32)) == 70 * 21 + 70 * 21 * 4);

@@ -207,15 +207,15 @@ int main(int argc, char **argv) {
     EXPECT(lin_algorithmic_bytes(f) == 10 * 20 + 30 * 20 + 10 * 30 * 4 + 4 * 30 + 4 * 30);
     f.dst_dt = DFX_U8; f.lut_in_dt = DFX_U8;
     EXPECT(lin_algorithmic_bytes(f) == 10 * 20 + 30 * 20 + 10 * 30 + 4 * 30 + 4 * 30 + 256);
-    EXPECT(lin_extent(10, 32, 20, 1) == 9 * 32 + 20 && lin_extent(10, 40, 30, 4) == (9 * 40 + 30) * 4);
-    EXPECT(lin_overlap(100, 10, 109, 1) && !lin_overlap(100, 10, 110, 1) && !lin_overlap(110, 1, 100, 10) && lin_overlap(105, 1, 100, 10));
+    EXPECT(plan_extent(10, 32, 20, 1) == 9 * 32 + 20 && plan_extent(10, 40, 30, 4) == (9 * 40 + 30) * 4);
+    EXPECT(plan_overlap(100, 10, 109, 1) && !plan_overlap(100, 10, 110, 1) && !plan_overlap(110, 1, 100, 10) && plan_overlap(105, 1, 100, 10));
     // the documented maximum, rows * ld = 2^40: extents (4-byte elements: 2^42 bytes), tiles, items and grids at full range
-    EXPECT(lin_extent(1ll << 20, 1ll << 20, 1ll << 20, 4) == 1ull << 42 && lin_extent(1ll << 40, 1, 1, 4) == 1ull << 42);
-    EXPECT(lin_extent(2, 1ll << 39, 40, 4) == ((1ull << 39) + 40) * 4 && lin_extent(1ll << 33, 128, 40, 1) == (1ull << 40) - 128 + 40);
-    EXPECT(lin_extent(3, (1ll << 31) + 4160, 72, 1) == (1ull << 32) + 8320 + 72);  // (the pitches of tests/far_offsets.py)
+    EXPECT(plan_extent(1ll << 20, 1ll << 20, 1ll << 20, 4) == 1ull << 42 && plan_extent(1ll << 40, 1, 1, 4) == 1ull << 42);
+    EXPECT(plan_extent(2, 1ll << 39, 40, 4) == ((1ull << 39) + 40) * 4 && plan_extent(1ll << 33, 128, 40, 1) == (1ull << 40) - 128 + 40);
+    EXPECT(plan_extent(3, (1ll << 31) + 4160, 72, 1) == (1ull << 32) + 8320 + 72);  // (the pitches of tests/far_offsets.py)
     const uintptr_t far = (uintptr_t)1 << 47;  // an operand of 2^42 bytes against a neighbour on either side
-    EXPECT(lin_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !lin_overlap(far, 1ull << 42, far + (1ull << 42), 8) &&
-           !lin_overlap(far, 1ull << 42, far - 8, 8) && lin_overlap(far, 1ull << 42, far - 8, 9) && lin_overlap(far + (1ull << 32) + 64, 408, far, (1ull << 32) + 8392));
+    EXPECT(plan_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !plan_overlap(far, 1ull << 42, far + (1ull << 42), 8) &&
+           !plan_overlap(far, 1ull << 42, far - 8, 8) && plan_overlap(far, 1ull << 42, far - 8, 9) && plan_overlap(far + (1ull << 32) + 64, 408, far, (1ull << 32) + 8392));
     const dfx_linear_desc most = desc(1ll << 40, 1, 1, 1, 1), wide = desc(1ll << 33, 96, 128, 96, 128);
     EXPECT(rc(most) == DFX_OK && rc(wide) == DFX_OK);
     EXPECT(lin_mtiles(1ll << 40, 64) == 1ll << 34 && lin_mtiles(1ll << 40, 128) == 1ll << 33 && lin_mtiles((1ll << 40) - 1, 128) == 1ll << 33);

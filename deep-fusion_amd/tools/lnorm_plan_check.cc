@@ -139,7 +139,7 @@ int main() {
     for (int sld = 96; sld <= 130; ++sld)
       for (int dld = 96; dld <= 130; ++dld) {
         const dfx_lnorm_desc d = desc(7, 96, sld, dld, DFX_S8, dst_dt);
-        const int es = lnorm_dt_size(dst_dt);
+        const int es = plan_dt_size(dst_dt);
         EXPECT(lnorm_row_class(d) == (sld % 16 == 0 && (dld * es) % 16 == 0));
         EXPECT(lnorm_in_class(d, DFX_LNORM_GENERIC) && lnorm_in_class(d, DFX_LNORM_ROW) == lnorm_row_class(d) && !lnorm_in_class(d, 2));
         // the auto rule: the row kernel only in its class and only where lnorm_row_auto() admits the point
@@ -178,20 +178,21 @@ int main() {
   EXPECT(lnorm_lds_bytes(desc(4, 16384, 16384, 16384), DFX_LNORM_ROW) == 0);
   EXPECT(lnorm_param_bytes(1) == 144 && lnorm_param_bytes(16) == 144 && lnorm_param_bytes(17) == 288 && lnorm_param_bytes(16384) == 9 * 16384);
   // ---- extents, overlap, bytes
-  EXPECT(lnorm_extent(1, 32, 21, 1) == 21 && lnorm_extent(3, 32, 21, 4) == (2 * 32 + 21) * 4);
-  EXPECT(lnorm_extent(1ll << 35, 32, 32, 4) == (1ull << 42));
+  EXPECT(plan_extent(1, 32, 21, 1) == 21 && plan_extent(3, 32, 21, 4) == (2 * 32 + 21) * 4);
+  EXPECT(plan_extent(1ll << 35, 32, 32, 4) == (1ull << 42));
   // the documented maximum rows * ld = 2^40 at both ends of the pitch's range, 4-byte elements; the pitches of tests/far_offsets.py
-  EXPECT(lnorm_extent(1ll << 40, 1, 1, 4) == (1ull << 42) && lnorm_extent(1ll << 26, 16384, 16384, 4) == (1ull << 42));
-  EXPECT(lnorm_extent(513, 2147483647, 16384, 4) == (512ull * 2147483647ull + 16384) * 4 && rc(desc(512, 16384, 2147483647, 2147483647)) == DFX_OK);
-  EXPECT(lnorm_extent(5, (1 << 30) + 4160, 40, 1) == (1ull << 32) + 4 * 4160 + 40 && lnorm_extent(3, (1 << 29) + 1040, 40, 4) == (1ull << 32) + 8320 + 160);
+  EXPECT(plan_extent(1ll << 40, 1, 1, 4) == (1ull << 42) && plan_extent(1ll << 26, 16384, 16384, 4) == (1ull << 42));
+  EXPECT(plan_extent(513, 2147483647, 16384, 4) == (512ull * 2147483647ull + 16384) * 4 && rc(desc(512, 16384, 2147483647, 2147483647)) == DFX_OK);
+  EXPECT(plan_extent(5, (1 << 30) + 4160, 40, 1) == (1ull << 32) + 4 * 4160 + 40 && plan_extent(3, (1 << 29) + 1040, 40, 4) == (1ull << 32) + 8320 + 160);
+  EXPECT(plan_extent(3, (1ll << 31) + 4160, 40, 1) == (1ull << 32) + 8320 + 40);  // (a pitch above 2^31: the shared extent takes 64-bit pitches)
   EXPECT(lnorm_algorithmic_bytes(desc(1ll << 40, 1, 1, 1, DFX_U8, DFX_F32), false) == 5 * (1ull << 40) + 8);
   {
     const uintptr_t far = (uintptr_t)1 << 47;  // an operand of 2^42 bytes against a neighbour on either side, and one between its rows
-    EXPECT(lnorm_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !lnorm_overlap(far, 1ull << 42, far + (1ull << 42), 16) &&
-           !lnorm_overlap(far, 1ull << 42, far - 16, 16) && lnorm_overlap(far, 1ull << 42, far - 16, 17) &&
-           lnorm_overlap(far + (1ull << 32) + 64, 240, far, (1ull << 32) + 16680));
+    EXPECT(plan_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !plan_overlap(far, 1ull << 42, far + (1ull << 42), 16) &&
+           !plan_overlap(far, 1ull << 42, far - 16, 16) && plan_overlap(far, 1ull << 42, far - 16, 17) &&
+           plan_overlap(far + (1ull << 32) + 64, 240, far, (1ull << 32) + 16680));
   }
-  EXPECT(lnorm_overlap(100, 10, 109, 5) && !lnorm_overlap(100, 10, 110, 5) && !lnorm_overlap(110, 5, 100, 10) && lnorm_overlap(100, 10, 90, 11));
+  EXPECT(plan_overlap(100, 10, 109, 5) && !plan_overlap(100, 10, 110, 5) && !plan_overlap(110, 5, 100, 10) && plan_overlap(100, 10, 90, 11));
   EXPECT(lnorm_algorithmic_bytes(desc(70, 96, 96, 96), false) == 70 * 96 * 2 + 8 * 96);
   EXPECT(lnorm_algorithmic_bytes(desc(70, 96, 112, 128, DFX_U8, DFX_F32), true) == 70 * 96 * 5 + 9 * 96);
   if (g_bad) {

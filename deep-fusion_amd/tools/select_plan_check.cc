@@ -192,7 +192,7 @@ static void check_validate() {
   CHECK(select_idx_extent(d, 4) == (100ull + 100) * 4 && select_idx_extent(d, 1) == 200);
   d.n_gather = 1; d.row_bytes[0] = 8; d.pixel_stride_bytes[0] = 12;
   CHECK(select_gather_src_extent(d, 0) == 69ull * 12 + 8 && select_gather_dst_extent(d, 0) == 2ull * 100 * 8);
-  CHECK(select_overlap(100, 10, 109, 1) && !select_overlap(100, 10, 110, 1) && !select_overlap(100, 10, 90, 10) && select_overlap(100, 10, 90, 11));
+  CHECK(plan_overlap(100, 10, 109, 1) && !plan_overlap(100, 10, 110, 1) && !plan_overlap(100, 10, 90, 10) && plan_overlap(100, 10, 90, 11));
   CHECK(select_algorithmic_bytes(d) == 2ull * 35 * 21 + 2 * 100 * 4 + 2 * 4 + 2ull * 2 * 100 * 8);
   CHECK(select_sort_size(1) == 64 && select_sort_size(64) == 64 && select_sort_size(65) == 128 && select_sort_size(4096) == 4096);
   CHECK(select_key8(0x80, DFX_S8) == 0 && select_key8(0x7f, DFX_S8) == 255 && select_key8(0xff, DFX_U8) == 255 && select_key8(select_key8(0x91, DFX_S8), DFX_S8) == 0x91);

@@ -205,7 +205,7 @@ int main() {
       for (int gld = c; gld <= c + 17; ++gld)
         for (int wld = c; wld <= c + 17; wld += 3) {
           const dfx_window_desc d = desc(P, 2, 10, 13, c, 7, 7, 0, 0, 0, dt, gld, wld);
-          const int es = window_dt_size(dt);
+          const int es = plan_dt_size(dt);
           EXPECT(window_row_class(d) == ((c * es) % 16 == 0 && (gld * es) % 16 == 0 && (wld * es) % 16 == 0));
           EXPECT(window_in_class(d, DFX_WINDOW_GENERIC) && window_in_class(d, DFX_WINDOW_ROW) == window_row_class(d) && !window_in_class(d, 2));
           EXPECT(window_path(d) == (window_row_class(d) && window_row_auto(d) ? DFX_WINDOW_ROW : DFX_WINDOW_GENERIC));
@@ -241,21 +241,21 @@ int main() {
     EXPECT(window_src_extent(r) == (587ull * 192 + 64) * 4 && window_dst_extent(r) == (383ull * 80 + 64) * 4);
     EXPECT(window_algorithmic_bytes(p) == (384ull + 588) * 64 + 4 * 294 && window_algorithmic_bytes(r) == 2ull * 384 * 256 + 4 * 192);
   }
-  EXPECT(window_extent(1, 32, 21, 1) == 21 && window_extent(3, 32, 21, 4) == (2 * 32 + 21) * 4);
+  EXPECT(plan_extent(1, 32, 21, 1) == 21 && plan_extent(3, 32, 21, 4) == (2 * 32 + 21) * 4);
   // 64-bit offsets: rows * ld = 2^40 with 4-byte elements, and the pitches of tests/far_offsets.py (three rows)
-  EXPECT(window_extent(1ll << 36, 16, 16, 4) == (1ull << 42) && window_extent(3, (1ll << 40) / 3, 16, 4) == (2 * ((1ull << 40) / 3) + 16) * 4);
-  EXPECT(window_extent(3, (1ll << 31) + 4160, 16, 1) == (1ull << 32) + 8320 + 16 && window_extent(3, ((1ll << 31) + 4160) / 4, 4, 4) == (1ull << 32) + 8320 + 16);
+  EXPECT(plan_extent(1ll << 36, 16, 16, 4) == (1ull << 42) && plan_extent(3, (1ll << 40) / 3, 16, 4) == (2 * ((1ull << 40) / 3) + 16) * 4);
+  EXPECT(plan_extent(3, (1ll << 31) + 4160, 16, 1) == (1ull << 32) + 8320 + 16 && plan_extent(3, ((1ll << 31) + 4160) / 4, 4, 4) == (1ull << 32) + 8320 + 16);
   {
     const dfx_window_desc f = desc(P, 1, 1, 3, 16, 1, 3, 0, 0, 0, DFX_S8, 16, (1ll << 31) + 4160);
     EXPECT(rc(f) == DFX_OK && window_dst_extent(f) == (1ull << 32) + 8336 && window_src_extent(f) == 48);
     const dfx_window_desc big = desc(P, 1 << 14, 2048, 2048, 4, 2, 2, 0, 0, 0, DFX_F32, 16, 16);
     EXPECT(rc(big) == DFX_OK && window_dst_extent(big) == (((1ull << 36) - 1) * 16 + 4) * 4 && window_algorithmic_bytes(big) == (2ull << 36) * 16 + (4ull << 22));
     const uintptr_t far = (uintptr_t)1 << 47;  // an operand of 2^42 bytes against a neighbour on either side, and one between its rows
-    EXPECT(window_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !window_overlap(far, 1ull << 42, far + (1ull << 42), 16) &&
-           !window_overlap(far, 1ull << 42, far - 16, 16) && window_overlap(far, 1ull << 42, far - 16, 17) &&
-           window_overlap(far + (1ull << 32) + 64, 240, far, (1ull << 32) + 8336));
+    EXPECT(plan_overlap(far, 1ull << 42, far + (1ull << 42) - 1, 1) && !plan_overlap(far, 1ull << 42, far + (1ull << 42), 16) &&
+           !plan_overlap(far, 1ull << 42, far - 16, 16) && plan_overlap(far, 1ull << 42, far - 16, 17) &&
+           plan_overlap(far + (1ull << 32) + 64, 240, far, (1ull << 32) + 8336));
   }
-  EXPECT(window_overlap(100, 10, 109, 5) && !window_overlap(100, 10, 110, 5) && !window_overlap(110, 5, 100, 10) && window_overlap(100, 10, 90, 11));
+  EXPECT(plan_overlap(100, 10, 109, 5) && !plan_overlap(100, 10, 110, 5) && !plan_overlap(110, 5, 100, 10) && plan_overlap(100, 10, 90, 11));
   if (g_bad) {
     printf("window_plan_check: %d checks FAILED\n", g_bad);
     return 1;
